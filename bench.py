@@ -1,13 +1,25 @@
 #!/usr/bin/env python3
 """HSIMAE pretraining fwd+bwd throughput on MI355X (BASELINE.json metric), one process per GPU.
 
-    python bench.py [--gpus N --steps K --warmup W] [--model base|large|huge] [--precision bf16|fp8]
+    python bench.py [--gpus N --steps K --warmup W] [--model base|large|huge] [--precision bf16|fp8] [--full]
+                    [--dump-outputs DIR]
 
 `--gpus N` with N > 1 starts its own N ranks (`python -m torch.distributed.run --nproc-per-node N ... bench.py ...`) from a
 parent process that never touches the GPU; under an external launcher (RANK / WORLD_SIZE in the environment) the
 process is one of those ranks.  A step = one forward + backward of HSIMAE over a per-GPU batch of synthetic cubes already
 resident in HBM (mask ratio 0.75), including the RCCL gradient all-reduce when N > 1.  Rank 0 prints ONE JSON line;
-`value` is the whole-job patches/s over the wall-clock bracket (barrier + synchronize on both sides, MAX over ranks).
+`value` is the whole-job patches/s over the wall-clock bracket (barrier + synchronize on both sides, MAX over ranks), and
+`ms_per_step` is that bracket over the K timed steps.
+
+A plain run sets up, runs the W warm-up and K timed steps and prints the line: `roofline` and `step_ms` below come from the
+timed steps themselves.  `--full` adds everything that takes runs of its own after the timed region: `encoder_mfma_frac`,
+`roofline_kernel*`, `roofline_decoder*`, `optimizer_step_ms`, `input_pipeline`, `cpu_baseline` (trimmed by --no-extras /
+--no-cpu-baseline) and, where the gradient reducer runs, `comm` and the `--verify` self-check.
+
+`--dump-outputs DIR` writes, right after the timed steps, what the last timed step returned to its caller as float32 .npy
+files: loss, pred and mask (HSIMAE.forward) and grad.<parameter name> (the backward), at most 64 MB in all; an array that does
+not fit its share is a fixed, seeded sample of its elements.  Inputs, weights and mask draws are seeded, so two builds run
+with the same arguments can be compared file by file.
 
   roofline             SURVEY 8(d): the path is MFMA-bound; achieved = algorithmic fwd+bwd TFLOP/s per GPU of the step
                        (no recompute credit) against the dense bf16 (fp8: MX-scaled fp8) MFMA peak; `traffic` = HBM bytes
@@ -561,6 +573,37 @@ def pct(sorted_vals, q):
     return sorted_vals[i]
 
 
+# --dump-outputs budget in float32 elements (64 MB in all): pred and mask 16 MB each, the gradients 24 MB together, and on top of
+# that a gradient of up to 1024 elements (bias, norm) always whole: at most 533 x 4 KB
+DUMP_IMG_ELEMS = 4 << 20
+DUMP_GRAD_ELEMS = 6 << 20
+DUMP_GRAD_WHOLE = 1024
+
+
+def _sample(a, limit):
+    """`a` whole when it has at most `limit` elements, else a fixed sample of `limit` of them (seeded: the same positions for the same
+    shape in every run, so that two builds are compared element for element)."""
+    import numpy as np
+    if a.size <= limit:
+        return a
+    idx = np.sort(np.random.default_rng(0).choice(a.size, limit, replace=False))
+    return a.reshape(-1)[idx]
+
+
+def dump_outputs(path, loss, pred, mask, model):
+    """What the last timed step handed its caller, as DIR/<name>.npy in float32: the loss, pred and mask that HSIMAE.forward returned
+    and every parameter gradient the backward left in `.grad` (grad.<parameter name>)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    grads = [(n, p.grad) for n, p in model.named_parameters() if p.grad is not None]
+    frac = min(1.0, DUMP_GRAD_ELEMS / max(1, sum(g.numel() for _, g in grads)))
+    arrays = [("loss", loss, 1), ("pred", pred, DUMP_IMG_ELEMS), ("mask", mask, DUMP_IMG_ELEMS)]
+    arrays += [("grad." + n, g, max(int(g.numel() * frac), min(g.numel(), DUMP_GRAD_WHOLE))) for n, g in grads]
+    for name, t, limit in arrays:
+        np.save(os.path.join(path, name + ".npy"), _sample(t.detach().float().cpu().numpy(), limit))
+    return len(arrays)
+
+
 # --------------------------------------------------------------------------- one rank
 def dry_run(args, world, rank):
     """Launcher / protocol check without a GPU (tests/test_bench_launcher.py): gloo ranks, barrier, MAX reduce, one line."""
@@ -634,15 +677,20 @@ def main():
     ap.add_argument("--model", default="base", choices=sorted(MODELS))
     ap.add_argument("--precision", default=None, choices=["bf16", "fp8"],
                     help="GEMM operand type of the encoder linears (default: bf16; huge: fp8)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="only the step timing (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also the legs that take runs of their own: kernel / encoder / decoder replays, "
+                         "optimizer, input pipeline, CPU baseline, and the reducer's comm timing and self-check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss / pred / mask / parameter gradients to DIR/<name>.npy (float32, <= 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the replays, optimizer, input-pipeline and CPU legs")
     ap.add_argument("--force-ddp", action="store_true", help="run the RCCL gradient reducer even with one rank (test)")
     ap.add_argument("--init-pg-only", action="store_true", help="experiment: create the RCCL process group but do not use it")
     ap.add_argument("--dry-run", action="store_true", help="launcher / protocol check on CPU with gloo (no GPU work)")
     ap.add_argument("--verify", dest="verify", action="store_true", default=None,
-                    help="data-parallel self-check after the timed steps (default: on whenever the gradient reducer runs): one extra "
-                         "step in deterministic mode, its bucketed + overlapped reduction compared with ONE plain all-reduce of the "
-                         "same step's local gradients, hashes of the reduced buffer / grid sequence / collective order all-gathered; "
+                    help="data-parallel self-check after the timed steps (default: on with --full whenever the gradient reducer "
+                         "runs): one extra step in deterministic mode, its bucketed + overlapped reduction compared with ONE plain "
+                         "all-reduce of the same step's local gradients, hashes of the reduced buffer / grid sequence / collective order all-gathered; "
                          "rank 0 prints dp_consistent and the bucket list")
     ap.add_argument("--no-verify", dest="verify", action="store_false")
     ap.add_argument("--watchdog", type=float, default=420.0,
@@ -650,6 +698,8 @@ def main():
     ap.add_argument("--cpu-probe", type=int, default=0, help=argparse.SUPPRESS)      # child of cpu_baseline(): threads to probe
     ap.add_argument("--probe-bands", type=int, default=96, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.cpu_probe:
         rate, _, _ = _oracle_rate(args.probe_bands, 32, 3 if args.probe_bands == 96 else 6, 9, args.cpu_probe, 0.0)
@@ -657,7 +707,7 @@ def main():
         return
 
     if args.verify is None:
-        args.verify = True                            # (only acts where a reducer exists: world > 1 or --force-ddp)
+        args.verify = args.full                       # (only acts where a reducer exists: world > 1 or --force-ddp)
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args, sys.argv[1:]))
 
@@ -716,9 +766,9 @@ def main():
 
     def step():
         model.zero_grad(set_to_none=True)
-        loss, _, _ = model(imgs, mask_ratio=0.75)
+        loss, pred, mask = model(imgs, mask_ratio=0.75)
         loss.backward()
-        return loss
+        return loss, pred, mask
 
     for _ in range(args.warmup):
         step()
@@ -731,9 +781,11 @@ def main():
     t0 = time.perf_counter()
     marks[0].record()
     for i in range(args.steps):
-        loss = step()
+        loss, pred, mask = step()
         marks[i + 1].record()
         grids.append((model.len_t, model.len_l))
+        if i + 1 < args.steps:
+            pred = mask = None                        # only the last step's outputs outlive it (--dump-outputs)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -744,6 +796,11 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
     last_loss = float(loss.item())
+    if args.dump_outputs and rank == 0:
+        # before any --full leg: those run more steps (and optimizer steps) over the same gradients and weights
+        n = dump_outputs(args.dump_outputs, loss, pred, mask, model)
+        _log(f"{n} outputs of the last timed step written to {args.dump_outputs}")
+    pred = mask = None
     if rank == 0:
         h, hd = swiglu_hidden(D, 4.0), swiglu_hidden(64, 4.0)
         lt0, ll0 = HSIMAE.grid_candidates(bands // 8, 9, 0.75)[0]
@@ -789,7 +846,7 @@ def main():
         # be lost with it: after --watchdog seconds rank 0 prints the line as it stands and leaves.
         watchdog = _Watchdog(args.watchdog, out)
     comm = None
-    if use_ddp:
+    if use_ddp and args.full:
         # what the gradient exchange costs this configuration: the same step with the reducer detached (no collectives,
         # no callbacks), timed on every rank over a few steps; exposed = step(ddp) - step(no reduce)
         red = model._reducer
@@ -828,7 +885,7 @@ def main():
         prev_det = model._deterministic
         model.deterministic = True
         rng = (random.getstate(), torch.get_rng_state(), torch.cuda.get_rng_state(dev))
-        lv = float(step().item()); torch.cuda.synchronize()
+        lv = float(step()[0].item()); torch.cuda.synchronize()
         g_b, launched_v, grid_v = model._flat_grad.clone(), list(red.launched), (model.len_t, model.len_l)
         random.setstate(rng[0]); torch.set_rng_state(rng[1]); torch.cuda.set_rng_state(rng[2], dev)
         model._reducer = None
@@ -853,7 +910,7 @@ def main():
         if effective_note:
             out["config"]["precision_note"] = effective_note
         _log(f"step timing done: {dt / args.steps * 1e3:.3f} ms/step")
-        if not args.no_extras:
+        if args.full and not args.no_extras:
             enc_ms = encoder_only_ms(model, imgs)
             _log(f"encoder-only {enc_ms:.3f} ms")
             enc_tf = N * fl_enc / (enc_ms * 1e-3) / 1e12

@@ -209,7 +209,7 @@ def test_bench_two_gpus_prints_one_line_with_comm():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2",
-                        "--no-cpu-baseline", "--no-extras"], capture_output=True, text=True, timeout=900, cwd=root)
+                        "--full", "--no-cpu-baseline", "--no-extras"], capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
