@@ -480,6 +480,7 @@ extern "C" unsigned hs_variant_bits_pack();
 extern "C" unsigned hs_variant_bits_fused_dec();
 extern "C" unsigned hs_variant_bits_fused_enc();
 extern "C" unsigned hs_variant_bits_loader();
+extern "C" unsigned hs_variant_bits_scene();
 #ifndef HS_KERNEL_SOURCE_HASH
 #define HS_KERNEL_SOURCE_HASH 0ULL
 #endif
@@ -497,7 +498,7 @@ int hsimae_version(void) { return HSIMAE_VERSION; }
 int hsimae_build_info(hsimae_build_info_t* out) {
     if (!out) return HSIMAE_ENULL;
     out->abi_version = HSIMAE_VERSION;
-    out->variant_bits = hs_variant_bits() | hs_variant_bits_gemm() | hs_variant_bits_attn() | hs_variant_bits_attn_wide() | hs_variant_bits_wgrad() | hs_variant_bits_elem() | hs_variant_bits_pack() | hs_variant_bits_fused_dec() | hs_variant_bits_fused_enc() | hs_variant_bits_loader();
+    out->variant_bits = hs_variant_bits() | hs_variant_bits_gemm() | hs_variant_bits_attn() | hs_variant_bits_attn_wide() | hs_variant_bits_wgrad() | hs_variant_bits_elem() | hs_variant_bits_pack() | hs_variant_bits_fused_dec() | hs_variant_bits_fused_enc() | hs_variant_bits_loader() | hs_variant_bits_scene();
     out->kernel_source_hash = HS_KERNEL_SOURCE_HASH;
     out->flags_hash = HS_BUILD_FLAGS_HASH;
     out->default_flags = HS_BUILD_DEFAULT_FLAGS;
@@ -979,6 +980,23 @@ int hsimae_cube_gather(const hsimae_cube_params* p, void* stream) {
     if (p->N <= 0) return HSIMAE_OK;
     if (!p->scenes || !p->scene_off || !p->scene_w || !p->cut || !p->index || !p->out) return HSIMAE_ENULL;
     return hs_cube_gather(*p, S(stream));
+}
+int hsimae_scene_windows(const hsimae_scene_params* p, void* stream) {
+    if (!p) return HSIMAE_ENULL;
+    if (p->N < 0 || p->H <= 0 || p->W <= 0 || p->C <= 0) return HSIMAE_EDIMS;
+    if (p->N == 0) return HSIMAE_OK;
+    if (!p->scene || !p->out) return HSIMAE_ENULL;
+    if (!p->pixels && (p->p0 < 0 || p->p0 + p->N > (int64_t)p->H * p->W)) return HSIMAE_EDIMS;
+    return hs_scene_windows(*p, S(stream));
+}
+int hsimae_class_argmax(const hsimae_scene_params* p, const float* logits, int32_t ld, int32_t num_class, int32_t first, int64_t* map,
+                        void* stream) {
+    if (!p) return HSIMAE_ENULL;
+    if (p->N < 0 || p->H <= 0 || p->W <= 0 || first < 0 || first >= num_class || num_class > 256 || ld < num_class) return HSIMAE_EDIMS;
+    if (p->N == 0) return HSIMAE_OK;
+    if (!logits || !map) return HSIMAE_ENULL;
+    if (!p->pixels && (p->p0 < 0 || p->p0 + p->N > (int64_t)p->H * p->W)) return HSIMAE_EDIMS;
+    return hs_class_argmax(*p, logits, ld, num_class, first, map, S(stream));
 }
 int hsimae_ln_bwd(const hsimae_lnbwd_params* p, void* stream) { return p ? hs_ln_bwd(*p, S(stream)) : HSIMAE_ENULL; }
 int hsimae_ln_fwd(const float* x, const float* gamma, const float* beta, float* out, int32_t M, int32_t d, void* stream) {

@@ -20,6 +20,7 @@ typedef hsimae_patch_params PatchParams;
 typedef hsimae_assemble_params AssembleParams;
 typedef hsimae_loss_params LossParams;
 typedef hsimae_cube_params CubeParams;
+typedef hsimae_scene_params SceneParams;
 
 int hs_gemm(const GemmParams& p, int akind, int epi, hipStream_t s);
 int hs_gemm_tiled(const GemmParams& p, int akind, int epi, int bm, int kc, hipStream_t s);   // tile sweep hook
@@ -37,6 +38,8 @@ int hs_assemble_bwd(const AssembleParams& p, hipStream_t s);
 int hs_loss(const LossParams& p, hipStream_t s);
 int hs_loss_partials(int N, int T);
 int hs_cube_gather(const CubeParams& p, hipStream_t s);
+int hs_scene_windows(const SceneParams& p, hipStream_t s);
+int hs_class_argmax(const SceneParams& p, const float* logits, int ld, int num_class, int first, int64_t* map, hipStream_t s);
 int hs_agg_pool(const float* latent, float* pooled, int N, int T, int L, int D, hipStream_t s);
 int hs_head_bwd(const float* g, const float* pooled, const float* w, float* gw, float* gb, float* dlat, int N, int C, int T, int L,
                 int D, hipStream_t s);

@@ -19,6 +19,7 @@ from __future__ import annotations
 
 import ctypes as C
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -117,6 +118,94 @@ class DualViT(HSIMAE):
                             bias=bias.data_ptr(), out=out.data_ptr(), ldo=npad)
         _lib.check(lib.hsimae_gemm(C.byref(p), _lib.A_F32, _lib.E_F32, stream), "hsimae_gemm")
         return out[:, :self.num_class], pooled
+
+    # ------------------------------------------------------------------ whole-scene inference (Model_Finetuning.py:243-300)
+    # hsimae_encode's arena takes ~4 MB per window at Base width (~8 MB at Large): the default chunk is the largest one whose
+    # arena fits this budget, and never more than `batch_size` pixels
+    SCENE_WORKSPACE_BUDGET = 8 << 30
+
+    def _scene_chunk(self, batch_size):
+        lib, cfg = _lib.load(), self._config()
+        T, L = self.input_size[0], self.input_size[1] ** 2
+        lo, hi = 1, int(batch_size)
+        while lo < hi:                                    # largest n <= batch_size within the budget (at least 1)
+            mid = (lo + hi + 1) // 2
+            if 0 <= lib.hsimae_workspace_bytes(C.byref(cfg), mid, T, L) <= self.SCENE_WORKSPACE_BUDGET:
+                lo = mid
+            else:
+                hi = mid - 1
+        return lo
+
+    def predict_scene(self, scene, pixels=None, batch_size=8192, return_logits=False):
+        """Per-pixel classification map of a whole scene (what `test_model` computes from `data_cubes`, :268-283), from the
+        scene itself: `scene` [H, W, C] fp32 / fp64 (numpy or tensor; the `HSI_data` of get_data_set_dual after GWPCA / norm)
+        is uploaded once; per chunk of pixels, on the current stream: the symmetric-padded 9 x 9 windows (hsimae_scene_windows),
+        the unmasked encoder (hsimae_encode), the AGG head, and label = 1 + argmax(logits[:, 1:]) written in place into a
+        device-resident map (hsimae_class_argmax).  The host waits once, for the final copy.
+        Evaluates as in eval mode (no DropPath), without autograd.  `pixels`: row-major pixel indices r * W + c to classify
+        (default: all); the map is 0 elsewhere.  `batch_size` caps the pixels per chunk; the chunk is also kept small enough
+        for the encoder's workspace to fit SCENE_WORKSPACE_BUDGET bytes.
+        -> int64 [H, W] map (CPU), and with return_logits=True also fp32 [n, num_class] logits (CPU) in pixel order."""
+        if isinstance(scene, torch.Tensor):
+            s = scene
+        else:
+            s = torch.from_numpy(np.asarray(scene))
+        if s.dim() != 3:
+            raise ValueError(f"scene must be [H, W, C], got shape {tuple(s.shape)}")
+        H, W, Cb = (int(v) for v in s.shape)
+        if s.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"scene must be float32 or float64, got {s.dtype}")
+        if Cb % 8:
+            raise ValueError(f"scene has {Cb} bands: the band count must be a multiple of 8 (b_patch_size)")
+        if Cb != self.patch_embed.bands:
+            raise ValueError(f"scene has {Cb} bands, the model was built for bands={self.patch_embed.bands}")
+        if H <= 0 or W <= 0:
+            raise ValueError(f"empty scene {tuple(s.shape)}")
+        if int(batch_size) < 1:
+            raise ValueError(f"batch_size must be >= 1, got {batch_size}")
+        pix = None
+        if pixels is not None:
+            pix = torch.as_tensor(pixels).detach().cpu()
+            if pix.dim() != 1 or pix.dtype.is_floating_point or pix.dtype == torch.bool:
+                raise ValueError("pixels must be a 1-D array of integer pixel indices (r * W + c)")
+            pix = pix.to(torch.int64).contiguous()
+            if pix.numel() and (int(pix.min()) < 0 or int(pix.max()) >= H * W):
+                raise ValueError(f"pixel index out of range [0, {H * W}): min {int(pix.min())}, max {int(pix.max())}")
+        dev = self.cls_head.weight.device
+        if dev.type != "cuda":
+            raise RuntimeError("hsimae_amd runs on MI355X only (no CPU fallback): move the model to a GPU")
+        n_total = H * W if pix is None else pix.numel()
+        lib = _lib.load()
+        T, L = self.input_size[0], self.input_size[1] ** 2
+        chunk = max(1, min(self._scene_chunk(batch_size), n_total))
+        with torch.no_grad(), torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            s = s.to(dev).contiguous()
+            pix_d = None if pix is None else pix.to(dev)
+            labels = torch.zeros(H * W, dtype=torch.int64, device=dev)
+            logits_all = torch.empty(n_total, self.num_class, dtype=torch.float32, device=dev) if return_logits else None
+            # the encoder's input, band-fastest as the reference's HSIdataset yields it: [chunk, 9, 9, C] viewed [chunk, 1, C, 9, 9]
+            win = torch.empty(chunk, 9, 9, Cb, dtype=torch.float32, device=dev).permute(0, 3, 1, 2).unsqueeze(1)
+            n1 = torch.arange(T, dtype=torch.float32, device=dev).expand(chunk, T).contiguous()   # increasing noise: identity order
+            n2 = torch.arange(L, dtype=torch.float32, device=dev).expand(chunk, L).contiguous()
+            for k0 in range(0, n_total, chunk):
+                n = min(chunk, n_total - k0)
+                sp = _lib.SceneParams(scene=s.data_ptr(), scene_f64=int(s.dtype == torch.float64), H=H, W=W, C=Cb,
+                                      p0=k0 if pix_d is None else 0, pixels=None if pix_d is None else pix_d.data_ptr() + 8 * k0,
+                                      N=n, out=win.data_ptr(), sn=win.stride(0), sb=win.stride(2), sh=win.stride(3),
+                                      sw=win.stride(4))
+                _lib.check(lib.hsimae_scene_windows(C.byref(sp), stream), "hsimae_scene_windows")
+                _, _, _, st = self._run_forward(win[:n], 0.0, (n1[:n], n2[:n]), (T, L), want_latent=True, encoder_only=True)
+                logits, _ = self.head(st["latent"])
+                st.release()
+                _lib.check(lib.hsimae_class_argmax(C.byref(sp), logits.data_ptr(), logits.stride(0), self.num_class, 1,
+                                                   labels.data_ptr(), stream), "hsimae_class_argmax")
+                if logits_all is not None:
+                    logits_all[k0:k0 + n].copy_(logits)
+            out = labels.view(H, W).cpu()
+        if return_logits:
+            return out, logits_all.cpu()
+        return out
 
     # ------------------------------------------------------------------ stochastic depth (Models.py:235-263, 687-731)
     def drop_rates(self):

@@ -187,3 +187,27 @@ def test_model(data_cubes, test_gt, gt, save_dir, model_name, depth=12, dim=96, 
     pred[np.asarray(gt) == 0] = 0
     oa, aa, kappa, ca = scores(np.asarray(test_gt).reshape(-1), pred.reshape(-1))
     return oa, aa, kappa, ca, pred_all
+
+
+def test_model_scene(scene, test_gt, gt, save_dir, model_name, depth=12, dim=96, s_depth=6, device="cuda:0", batch_size=8192):
+    """`test_model` from the scene itself: `scene` is the [H, W, C] `HSI_data` the reference cuts `data_cubes` from
+    (Utils/Preprocessing.py:189-213, after GWPCA / norm), fp32 or fp64.  The same model, loaded the same way; the windows are
+    cut on the device (HSIViT.predict_scene, at most `batch_size` pixels per chunk) instead of being built on the host.
+    -> (oa, aa, kappa, per-class recall, prediction map shaped like `gt`), as test_model returns them."""
+    device = torch.device(device)
+    if len(scene.shape) != 3:
+        raise ValueError(f"scene must be [H, W, C], got shape {tuple(scene.shape)}")
+    c = int(scene.shape[2])
+    n_class = int(np.max(gt) + 1)
+    model = HSIViT(img_size=9, patch_size=3, in_chans=1, bands=c, b_patch_size=8, num_class=n_class, embed_dim=dim, depth=depth,
+                   num_heads=dim // 16, s_depth=s_depth, sep_pos_embed=True, use_learnable_pos_emb=False).to(device)
+    model_dict = model.state_dict()
+    loaded = torch.load(os.path.join(save_dir, model_name), map_location=device)
+    model_dict.update({k: v for k, v in loaded.items() if k in model_dict})
+    model.load_state_dict(model_dict)
+    model.eval()
+    pred = model.predict_scene(scene, batch_size=batch_size).numpy().reshape(np.asarray(gt).shape)
+    pred_all = pred.copy()
+    pred[np.asarray(gt) == 0] = 0
+    oa, aa, kappa, ca = scores(np.asarray(test_gt).reshape(-1), pred.reshape(-1))
+    return oa, aa, kappa, ca, pred_all

@@ -52,8 +52,9 @@ extern "C" {
  * refuse a library that answers differently (hsimae_amd/_lib.py does).  104 (round 5): HSIMAE_ENOFORWARD, schedule recorded
  * by the forward; 103 -> 104 also covers round 4's incompatible change of the weight-gradient parameter block (t[8] -> t[16]), which had
  * shipped without a bump.  105 (round 6): hsimae_build_info; hsimae_attn_params lost the fused-projection fields
- * (proj_w .. rowscale) with the whole-sample d = 128 attention kernels they drove (superseded by the fused attention half). */
-#define HSIMAE_VERSION 105
+ * (proj_w .. rowscale) with the whole-sample d = 128 attention kernels they drove (superseded by the fused attention half).
+ * 106: hsimae_scene_params, hsimae_scene_windows, hsimae_class_argmax (whole-scene inference). */
+#define HSIMAE_VERSION 106
 int hsimae_version(void);
 /* What the loaded library was built from (round 6).  `variant_bits` has one bit per compile-time switch that makes a kernel
  * compute WRONG results on purpose (timing ablations: HS_ABL_*, HS_EXP_*, HS_EXPERIMENT_*) or adds instrumentation
@@ -437,6 +438,27 @@ typedef struct {
     float* out; int64_t sn, sb, sh, sw;
 } hsimae_cube_params;
 int hsimae_cube_gather(const hsimae_cube_params* p, void* stream);
+
+/* ------------------------------------------------------------------ whole-scene inference (Model_Finetuning.py:243-300) */
+/* A chunk of pixels of one scene [H][W][C] (row-major, fp32 or fp64, the `HSI_data` of Utils/Preprocessing.py:189-213 after
+ * GWPCA / norm).  Pixel k of the chunk is `pixels[k]` when `pixels` (int64, device) is given, else `p0 + k`; a pixel index is
+ * the row-major r * W + c.  Indices outside [0, H*W) are the caller's error: such a window is written as zeros and such a
+ * label is not written.
+ * hsimae_scene_windows: out[k, 0, b, i, j] = (float) scene[sym(r - 4 + i, H)][sym(c - 4 + j, W)][b] through the element strides
+ *   sn, sb, sh, sw (band-fastest, the view the reference's HSIdataset yields: sb = 1, sw = C, sh = 9 * C), sym = numpy's
+ *   'symmetric' pad of 4 (m = p mod 2H; m < H ? m : 2H - 1 - m, valid for any H >= 1).  fp64 -> fp32 rounds to nearest even
+ *   (torch.tensor(x, dtype=float32)): bit-exact with the reference's windows (:209-213 + Model_Finetuning.py:49-50).
+ * hsimae_class_argmax: map[pixel_k] = first + argmax(logits[k, first:num_class]) as int64, logits rows `ld` floats apart;
+ *   ties go to the lowest index and NaN counts as the maximum (torch.argmax).  `scene` and `out` are not used.
+ *   1 <= num_class - first, num_class <= 256. */
+typedef struct {
+    const void* scene; int32_t scene_f64; int32_t H, W, C;
+    int64_t p0; const int64_t* pixels; int32_t N;
+    float* out; int64_t sn, sb, sh, sw;
+} hsimae_scene_params;
+int hsimae_scene_windows(const hsimae_scene_params* p, void* stream);
+int hsimae_class_argmax(const hsimae_scene_params* p, const float* logits, int32_t ld, int32_t num_class, int32_t first, int64_t* map,
+                        void* stream);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus
