@@ -498,6 +498,10 @@ __global__ __launch_bounds__(256, (EPI == E_LN_BWD || BM <= 64) ? 2 : 1) void ge
                     }
                 }
                 if constexpr (EPI == E_BF16) {
+                    if (nv < 8) {                              // [n_valid, N): exact zeros whatever the image's padding rows hold
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) if (e >= nv) v[e] = 0.f;
+                    }
                     *reinterpret_cast<bf16x8*>(reinterpret_cast<bf16_t*>(p.out) + (size_t)row * p.ldo + col) = cvt8(v);
                 } else if constexpr (EPI == E_F32 || EPI == E_RES_F32 || EPI == E_POS_F32) {
                     if (!cvalid) continue;
@@ -888,6 +892,8 @@ int hs_gemm(const GemmParams& p, int akind, int epi, hipStream_t s) {
     if (p.M <= 0) return HS_OK;
     if (p.K % 32 || p.N % 16 || p.lda % 8 || p.ldo % 8) return HS_EDIMS;
     if ((epi == E_F32 || epi == E_RES_F32 || epi == E_POS_F32) && p.n_valid % 8) return HS_EDIMS;
+    // the LayerNorm prologue reads whole octets of columns [0, ln_width): a partial octet or a width past K would read pad columns as data
+    if (akind == A_F32_LN && (p.ln_width < 0 || p.ln_width % 8 || p.ln_width > p.K)) return HS_EDIMS;
 #define CASE(AK, EP) \
     if (akind == AK && epi == EP) return launch_kc<AK, EP>(p, s);
     CASE(A_F32_LN, E_BF16)
@@ -921,6 +927,7 @@ int hs_gemm(const GemmParams& p, int akind, int epi, hipStream_t s) {
         if (p.prec == HSIMAE_PREC_FP8) return HS_EUNSUPPORTED;
         if (p.N != 128 || p.n_valid != 128 || !p.lnx || !p.res || !p.gamma || !p.dgamma || !p.dbeta || p.ldr % 4 || p.ldo % 4)
             return HS_EUNSUPPORTED;
+        if (p.u_out) return HS_EUNSUPPORTED;        // the one-chunk epilogue stores no bf16 copy (only the k-outer forms at 256 / 512 do)
         return launch_kc<A_BF16, E_LN_BWD>(p, s);
     }
     CASE(A_F32, E_SWIGLU_BWD)

@@ -200,8 +200,13 @@ enum { HSIMAE_E_BF16 = 0, HSIMAE_E_F32 = 1, HSIMAE_E_RES_F32 = 2, HSIMAE_E_POS_F
        HSIMAE_E_SWIGLU_BWD = 5,
        /* E_LN_BWD: the product is dL/d(LayerNorm output); the epilogue applies the LayerNorm backward (autograd of
           Models.py:304 `x + attn(norm1(x))` w.r.t. x) in place of a separate pass: out = res + LNbwd(acc; lnx, gamma)
-          (+ out when `accumulate`), dgamma / dbeta accumulated with atomics.  Needs N == n_valid == 128 (one chunk). */
+          (+ out when `accumulate`; out may be res), dgamma / dbeta accumulated with atomics, or committed in 64-bit fixed
+          point when det_acc is set.  Needs N == n_valid, N = 128, 256 or 512 (bf16) or 256 / 512 (fp8).  u_out (a bf16 copy
+          of out, ld = ldu) is written at N = 256 / 512 only; at N = 128 a non-NULL u_out is refused (HSIMAE_EUNSUPPORTED). */
        HSIMAE_E_LN_BWD = 6 };
+/* Columns [n_valid, N) of the output (N a multiple of 16, n_valid <= N): E_F32 / E_RES_F32 / E_POS_F32 leave them untouched
+   (n_valid must be a multiple of 8); E_BF16 and E_SWIGLU (out and both halves of h13) write them as exact zeros;
+   E_SWIGLU_BWD and E_LN_BWD use all N columns.  Nothing past N in a row, nor past M rows, is written.  M = 0 is a no-op. */
 typedef struct {
     const void* A; int32_t lda;
     int32_t M, N, K;
@@ -220,20 +225,22 @@ typedef struct {
        out_rowscale multiplies (product + bias) before the residual is added in E_RES_F32.  NULL = 1. */
     const float* a_rowscale; const float* out_rowscale;
     /* prec = HSIMAE_PREC_FP8: the MX block-scaled e4m3 form of the same product (fp32 accumulate, same epilogues except
-       E_LN_BWD / E_POS_F32).  A is quantised on the fly; W8 / S8 (and W8b / S8b for the second matrix of E_SWIGLU) are the
+       E_POS_F32, and E_LN_BWD at N = 256 / 512 only).  A is quantised on the fly; W8 / S8 (and W8b / S8b for the second matrix of E_SWIGLU) are the
        e4m3 image and its e8m0 scale image of the weight as produced by hsimae_pack_matrix with desc.fp8 = 1
        (K padded to a multiple of 128).  W / W2 are ignored.  prec = 0: bf16, the fields below are ignored. */
     int32_t prec;
     const uint8_t* W8; const uint8_t* S8; const uint8_t* W8b; const uint8_t* S8b;
     /* A_F32_LN: number of leading columns the LayerNorm runs over when the rows are stored wider than the model width
-       (K = storage width, a multiple of 32; the columns past ln_width are read as zeros and stay zeros); 0 = K. */
+       (K = storage width, a multiple of 32; the columns past ln_width are not read, they stage and u_out-store as zeros); 0 = K.
+       Must be a multiple of 8 and <= K (HSIMAE_EDIMS otherwise). */
     int32_t ln_width;
     const float* det_base; int64_t* det_acc;      /* E_LN_BWD: deterministic dgamma / dbeta commits, as in hsimae_lnbwd_params */
 } hsimae_gemm_params;
 int hsimae_gemm(const hsimae_gemm_params* p, int32_t a_kind, int32_t epilogue, void* stream);
 /* The same kernel with the row-panel height (bm: 64 or 128) and the depth of an A chunk (kc: 128 or 256; ignored by the
- * LayerNorm prologue, which stages all of K) forced instead of chosen by shape; 0 = the shape rule.  Measurement hook
- * (scripts/gemm_sweep.py): results are identical for every tiling. */
+ * LayerNorm prologue, which stages all of K, by fp8, which stages 512, and by E_LN_BWD, which ignores both) forced instead of
+ * chosen by shape; 0 = the shape rule.  Measurement hook (scripts/gemm_sweep.py): every tiling runs the same k-steps in the
+ * same order into the same accumulators, so results are bit-identical for every tiling (tests/test_gpu_gemm.py). */
 int hsimae_gemm_tiled(const hsimae_gemm_params* p, int32_t a_kind, int32_t epilogue, int32_t bm, int32_t kc, void* stream);
 
 /* One fp32 matrix -> packed image (placement n_off/k_off lets q|k|v or w1|w3 share an image). */
