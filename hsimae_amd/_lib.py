@@ -66,6 +66,10 @@ class AttnParams(C.Structure):
                 ("dqkv", vp), ("kv_off", i32)]
 
 
+class AttnBlockWeights(C.Structure):
+    _fields_ = [(n, vp) for n in ("n1w", "n1b", "bqkv", "pb", "qkv", "p", "qkvT", "pT")]
+
+
 class MlpWeights(C.Structure):
     _fields_ = [("n2w", vp), ("n2b", vp), ("w1b", vp), ("w3b", vp), ("w2b", vp),
                 ("w1", vp), ("w3", vp), ("w2", vp), ("w2T", vp), ("w13T", vp), ("hidden", i32)]
@@ -155,6 +159,9 @@ SYMBOLS = {
     "hsimae_dec_block_bwd": (C.c_int, [C.POINTER(DecBlockWeights), C.POINTER(DecBlockGrads), vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp]),
     "hsimae_attn_fwd": (C.c_int, [C.POINTER(AttnParams), vp]),
     "hsimae_attn_bwd": (C.c_int, [C.POINTER(AttnParams), vp]),
+    "hsimae_attn_block_fwd": (C.c_int, [C.POINTER(AttnBlockWeights), vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "hsimae_attn_block_bwd": (C.c_int, [C.POINTER(AttnBlockWeights), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32,
+                                        i32, i32, i32, i32, vp]),
     "hsimae_wgrad": (C.c_int, [C.POINTER(WgradParams), vp]),
     "hsimae_wgrad_msplit": (i32, [i32, i64]),
     "hsimae_ln_bwd": (C.c_int, [C.POINTER(LnBwdParams), vp]),
@@ -175,7 +182,7 @@ SYMBOLS = {
     "hsimae_decode_backward": (C.c_int, [C.POINTER(Config), C.POINTER(IO), vp, vp, vp, BUCKET_CB, vp, vp]),
 }
 
-ABI_VERSION = 106       # HSIMAE_VERSION of include/hsimae_hip.h these ctypes structs mirror (a CPU test compares the two)
+ABI_VERSION = 107       # HSIMAE_VERSION of include/hsimae_hip.h these ctypes structs mirror (a CPU test compares the two)
 PREC_BF16, PREC_FP8 = 0, 1
 A_BF16, A_F32, A_F32_LN = 0, 1, 2
 E_BF16, E_F32, E_RES_F32, E_POS_F32, E_SWIGLU, E_SWIGLU_BWD, E_LN_BWD = 0, 1, 2, 3, 4, 5, 6

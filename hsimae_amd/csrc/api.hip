@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <mutex>
 #include <unordered_map>
+#include <initializer_list>
 
 using namespace hsplan;
 
@@ -962,6 +963,58 @@ int hsimae_dec_block_bwd(const hsimae_dec_block_weights* w, const hsimae_dec_blo
 }
 int hsimae_attn_fwd(const hsimae_attn_params* p, void* stream) { return p ? hs_attn_fwd(*p, S(stream)) : HSIMAE_ENULL; }
 int hsimae_attn_bwd(const hsimae_attn_params* p, void* stream) { return p ? hs_attn_bwd(*p, S(stream)) : HSIMAE_ENULL; }
+// The fused attention halves (attn.hip blk128_*, attn_wide.hip blk256_*), the kernels block_fwd / block_bwd launch at d = 128 / 256.
+static int attn_block_check(const hsimae_attn_block_weights* w, int d, int heads, int Ts, int nsamples, int mode, int len_l,
+                            std::initializer_list<const void*> rows) {
+    if (!w || !w->n1w || !w->n1b || !w->bqkv || !w->pb || !w->qkv || !w->p || !w->qkvT || !w->pT) return HSIMAE_ENULL;
+    if (!((d == 128 && heads == 8) || (d == 256 && heads == 16))) return HSIMAE_EUNSUPPORTED;
+    if (mode < 0 || mode > 2) return HSIMAE_EUNSUPPORTED;
+    if (Ts < 1 || (mode != 0 && len_l < 1)) return HSIMAE_EDIMS;
+    if (Ts > 32) return HSIMAE_EUNSUPPORTED;
+    if (d == 256 && !hs_attn_block256_fusable(d, heads, Ts, nsamples)) return HSIMAE_EUNSUPPORTED;     // 32-bit offsets
+    for (const void* r : rows) {
+        if (!r) return HSIMAE_ENULL;
+        if (reinterpret_cast<uintptr_t>(r) & 15) return HSIMAE_EALIGN;
+    }
+    return HSIMAE_OK;
+}
+int hsimae_attn_block_fwd(const hsimae_attn_block_weights* w, const float* x, hs_bf16* u, hs_bf16* qkv, hs_bf16* o, float* lse,
+                          float* x1, const float* rowscale, int32_t d, int32_t heads, int32_t Ts, int32_t nsamples, int32_t mode,
+                          int32_t len_l, void* stream) {
+    if (nsamples < 0) return HSIMAE_EDIMS;
+    if (nsamples == 0) return HSIMAE_OK;
+    CK(attn_block_check(w, d, heads, Ts, nsamples, mode, len_l, {x, u, o, lse, x1}));
+    if (qkv && (reinterpret_cast<uintptr_t>(qkv) & 15)) return HSIMAE_EALIGN;
+    if (d == 128)
+        return hs_attn_block_fwd(x, w->n1w, w->n1b, w->qkv, w->bqkv, w->p, w->pb, u, qkv, o, lse, x1, rowscale, Ts, nsamples, mode, len_l,
+                                 S(stream));
+    if (!qkv) return HSIMAE_EUNSUPPORTED;                // blk256_fwd always saves q|k|v (its backward reads them)
+    return hs_attn_block256_fwd(x, w->n1w, w->n1b, w->qkv, w->bqkv, w->p, w->pb, u, qkv, o, lse, x1, rowscale, Ts, nsamples, mode, len_l,
+                                S(stream));
+}
+int hsimae_attn_block_bwd(const hsimae_attn_block_weights* w, const hs_bf16* qkv, const hs_bf16* u, const hs_bf16* o, const float* lse,
+                          const hs_bf16* dx1b, const float* dx1, const float* x, hs_bf16* dqkv, float* dx, float* dgamma, float* dbeta,
+                          int64_t* det_acc, int32_t accumulate, int32_t d, int32_t heads, int32_t Ts, int32_t nsamples, int32_t mode,
+                          int32_t len_l, void* stream) {
+    if (nsamples < 0) return HSIMAE_EDIMS;
+    if (nsamples == 0) return HSIMAE_OK;
+    CK(attn_block_check(w, d, heads, Ts, nsamples, mode, len_l, {u, o, lse, dx1b, dx1, x, dqkv, dx}));
+    if (!dgamma || !dbeta) return HSIMAE_ENULL;
+    if (qkv && (reinterpret_cast<uintptr_t>(qkv) & 15)) return HSIMAE_EALIGN;
+    if (!qkv && d != 128) return HSIMAE_EUNSUPPORTED;    // recomputing q|k|v from u: blk128_bwd_kernel<RC> only
+    if (det_acc && dbeta != dgamma + d) return HSIMAE_EDIMS;
+    hipStream_t s = S(stream);
+    // deterministic: the kernel commits dgamma | dbeta into det_acc[0, 2 d) (offsets from dgamma), converted and added below
+    if (det_acc) CK((int)hipMemsetAsync(det_acc, 0, sizeof(int64_t) * 2 * d, s));
+    long long* acc = reinterpret_cast<long long*>(det_acc);
+    if (d == 128)
+        CK(hs_attn_block_bwd(qkv, u, w->qkv, w->bqkv, o, lse, dx1b, dx1, x, w->n1w, w->pT, w->qkvT, dqkv, dx, dgamma, dbeta, dgamma, acc,
+                             Ts, nsamples, mode, len_l, accumulate, s));
+    else
+        CK(hs_attn_block256_bwd(qkv, lse, dx1b, dx1, x, w->n1w, w->pT, w->qkvT, dqkv, dx, dgamma, dbeta, dgamma, acc, Ts, nsamples, mode,
+                                len_l, accumulate, s));
+    return det_acc ? hs_det_convert(det_acc, dgamma, 2 * d, s) : HSIMAE_OK;
+}
 int hsimae_wgrad(const hsimae_wgrad_params* p, void* stream) { return p ? hs_wgrad(*p, S(stream)) : HSIMAE_ENULL; }
 int32_t hsimae_wgrad_msplit(int32_t tiles, int64_t M) { return wgrad_msplit(tiles, M); }
 int hsimae_agg_pool(const float* latent, float* pooled, int32_t N, int32_t T, int32_t L, int32_t D, void* stream) {

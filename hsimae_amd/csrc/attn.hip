@@ -694,7 +694,7 @@ int launch_blk128(const Blk128Args& a, hipStream_t s) {
     if (!attr_set) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(blk128_fwd_kernel<NT, SPW>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)L::TOTAL); attr_set = true; }
     // persistent, one 8-wave workgroup per CU: the weights (64 registers) + the attention state need ~156 registers;
-    // forced to 128 (two workgroups per CU) the kernel spills 24-68 of them and is 20 % slower.  HSIMAE_BLK128_WGS overrides.
+    // forced to 128 (two workgroups per CU) the kernel spills 24-68 of them and is 20 % slower.  At most 256 workgroups.
     static int wgs = 0;
     if (!wgs) wgs = 256;
     const int groups = (a.nsamples + SPW - 1) / SPW;
@@ -1233,6 +1233,18 @@ template <bool BWD>
 int dispatch(const AttnParams& p, hipStream_t s) {
     if (p.nsamples <= 0) return HS_OK;
     if (p.d != p.heads * p.hd || p.ld % 8 || p.ldo % 4) return HS_EDIMS;
+    // the class of token i is i / len_l (mode 1) or i % len_l (mode 2), any Ts; anything but modes 0 / 1 / 2 is not a mask
+    if (p.mode < 0 || p.mode > 2) return HS_EUNSUPPORTED;
+    if (p.Ts < 1 || (p.mode != 0 && p.len_l < 1)) return HS_EDIMS;
+    // k / v are read and written as 16-byte pieces at base + kv_off (+ 2 kv_off), three column ranges that must not overlap or
+    // run past the row; o rows hold d columns
+    if (p.kv_off && (p.kv_off < p.d || p.kv_off % 8)) return HS_EDIMS;
+    if (p.kv_off < 0 || (int64_t)p.ld < 2 * (int64_t)KVO(p) + p.d || p.ldo < p.d) return HS_EDIMS;
+    if (!p.qkv || !p.o) return HS_ENULL;
+    if (BWD) {
+        if (p.lddo < p.d || p.lddo % 8) return HS_EDIMS;     // dO rows are staged as 16-byte pieces, as q|k|v
+        if (!p.dout || !p.dqkv) return HS_ENULL;
+    }
     if (BWD && !p.lse) return HS_EUNSUPPORTED;               // the backward needs the forward's logsumexp
     const int nt = (p.Ts + 15) / 16;
     if (p.hd == 16) {

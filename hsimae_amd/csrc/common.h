@@ -56,6 +56,7 @@ static inline unsigned hs_variant_bits() {
 #define HS_EDIMS (-1)
 #define HS_EUNSUPPORTED (-2)
 #define HS_EALIGN (-3)
+#define HS_ENULL (-4)
 
 __device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
     // D[16x16] += A[16x32] * B[32x16].  lane l: A[row l&15][k 8(l>>4)+j], B[k 8(l>>4)+j][col l&15];

@@ -53,8 +53,10 @@ extern "C" {
  * by the forward; 103 -> 104 also covers round 4's incompatible change of the weight-gradient parameter block (t[8] -> t[16]), which had
  * shipped without a bump.  105 (round 6): hsimae_build_info; hsimae_attn_params lost the fused-projection fields
  * (proj_w .. rowscale) with the whole-sample d = 128 attention kernels they drove (superseded by the fused attention half).
- * 106: hsimae_scene_params, hsimae_scene_windows, hsimae_class_argmax (whole-scene inference). */
-#define HSIMAE_VERSION 106
+ * 106: hsimae_scene_params, hsimae_scene_windows, hsimae_class_argmax (whole-scene inference).
+ * 107: hsimae_attn_block_weights, hsimae_attn_block_fwd / _bwd (the fused attention halves, per kernel); hsimae_attn_fwd / _bwd
+ * refuse invalid mode, len_l, Ts, kv_off, ld and lddo values they used to launch with. */
+#define HSIMAE_VERSION 107
 int hsimae_version(void);
 /* What the loaded library was built from (round 6).  `variant_bits` has one bit per compile-time switch that makes a kernel
  * compute WRONG results on purpose (timing ablations: HS_ABL_*, HS_EXP_*, HS_EXPERIMENT_*) or adds instrumentation
@@ -278,7 +280,19 @@ int hsimae_enc_mlp_bwd(const float* x1, const float* dy, float* dx1, hs_bf16* u2
                        hs_bf16* dx1b, int32_t M, int32_t d, const hsimae_mlp_weights* w, float* g_n2w, float* g_n2b,
                        const float* rs_mlp, const float* rs_attn, int32_t plane_rows, void* stream);
 
-/* Masked multi-head attention over one sample's tokens (Models.py:192-215) and its backward. */
+/* Masked multi-head attention over one sample's tokens (Models.py:192-215) and its backward.
+ * Rows are sample-major: token t of sample s is row s * Ts + t, rows [0, nsamples * Ts).  Token i attends to token j when both
+ * are in the same class: mode 0 one class, mode 1 class = i / len_l, mode 2 class = i % len_l (len_l >= 1; Ts need not be a
+ * multiple of it).  Head h owns columns [h hd, (h + 1) hd) of q, k, v, o; q at column 0 of a qkv row, k at kv_off, v at 2 kv_off.
+ * Scores are q k^T / sqrt(hd).  hd = 16 serves Ts <= 112, hd = 8 Ts <= 224 (else HSIMAE_EUNSUPPORTED).
+ * forward : o [rows][ldo], columns [0, d) (nothing past d is written); lse [rows][heads] when non-NULL: the logsumexp of the
+ *           row's scores in LOG2 units, log2 sum_j 2^(s_ij log2 e) (what the backward takes back).
+ * backward: from dout = dL/do [rows][lddo] and the forward's lse (and o) -> dqkv [rows][ld]: dq, dk, dv in columns [0, d),
+ *           [kv_off, kv_off + d), [2 kv_off, 2 kv_off + d); the columns between them and past 2 kv_off + d are not written
+ *           (they keep what the caller put there).  dqkv may not alias qkv or dout.
+ * Refused: d != heads * hd, ld % 8, ldo % 4, ld < 2 kv_off + d, ldo < d, Ts < 1, len_l < 1 in mode 1 / 2, kv_off not 0 and
+ * (< d or not a multiple of 8), backward: lddo < d or lddo % 8 (HSIMAE_EDIMS); mode not 0 / 1 / 2 (HSIMAE_EUNSUPPORTED);
+ * qkv / o NULL, backward: dout / dqkv NULL (HSIMAE_ENULL), lse NULL (HSIMAE_EUNSUPPORTED).  nsamples <= 0 is a no-op. */
 typedef struct {
     const hs_bf16* qkv; int32_t ld;
     int32_t d, heads, hd;
@@ -294,6 +308,38 @@ typedef struct {
 } hsimae_attn_params;
 int hsimae_attn_fwd(const hsimae_attn_params* p, void* stream);
 int hsimae_attn_bwd(const hsimae_attn_params* p, void* stream);
+
+/* The attention half of an encoder Block (Models.py:304 `x + drop_path(attn(norm1(x)))`, Attention.forward :192-219) in one
+   persistent kernel each way, as hsimae_forward / hsimae_backward run it at d = 128 with 8 heads (blk128_*) and d = 256 with 16
+   heads (blk256_*) — exposed per kernel for the parity tests.  Any other (d, heads) is HSIMAE_EUNSUPPORTED.  Rows are unpadded
+   and sample-major (row s * Ts + t), 1 <= Ts <= 32; mode / len_l as in hsimae_attn_params; at d = 256 nsamples * Ts * 3 d
+   must stay below 2^31.  Every row pointer must be 16-byte aligned (HSIMAE_EALIGN).  Nothing outside rows [0, nsamples * Ts)
+   nor past the columns named below is written.
+   Weights: fp32 n1w / n1b (LayerNorm-1), bqkv = bq | bk | bv [3 d], pb [d]; bf16 images as hsimae_pack_matrix makes them:
+   qkv = Wq | Wk | Wv [3 d][d], p = Wp [d][d], qkvT = (Wq | Wk | Wv)^T [d][3 d], pT = Wp^T [d][d] (KS = K / 32). */
+typedef struct {
+    const float *n1w, *n1b, *bqkv, *pb;
+    const hs_bf16 *qkv, *p, *qkvT, *pT;
+} hsimae_attn_block_weights;
+/* forward: x [rows][d] fp32 -> u = LN1(x) bf16 [rows][d]; q|k|v bf16 [rows][3 d] (q | k | v, bias added; NULL: not written,
+   d = 128 only — the backward then recomputes them from u); o bf16 [rows][d] (the attention output); lse fp32 [rows][heads]
+   (log2-domain logsumexp, as in hsimae_attn_params); x1 = x + rowscale * (o Wp^T + pb) fp32 [rows][d].  rowscale [rows]:
+   optional DropPath factors, NULL = 1. */
+int hsimae_attn_block_fwd(const hsimae_attn_block_weights* w, const float* x, hs_bf16* u, hs_bf16* qkv, hs_bf16* o, float* lse,
+                          float* x1, const float* rowscale, int32_t d, int32_t heads, int32_t Ts, int32_t nsamples, int32_t mode,
+                          int32_t len_l, void* stream);
+/* backward: dO = dx1b Wp (bf16, formed inside), the attention backward, du = dq|dk|dv Wqkv and the LayerNorm-1 backward.
+   Inputs: the forward's q|k|v, u, o, lse and x; dx1b = bf16 of dL/d(attn branch output) with the DropPath factor folded in;
+   dx1 = dL/dx1 fp32 (the residual path).  qkv NULL: recompute q|k|v from u (d = 128 only; HSIMAE_EUNSUPPORTED at d = 256).
+   Outputs: dqkv bf16 [rows][3 d] = dq | dk | dv (whole rows); dx fp32 [rows][d] = dx1 + LN1-backward(du) (+ what dx held when
+   `accumulate`); dgamma / dbeta [d] fp32: the LayerNorm-1 parameter gradients ADDED to what they hold (float
+   atomics).  det_acc: optional int64 scratch [2 d] (contents irrelevant); when given, dbeta must be dgamma + d (HSIMAE_EDIMS
+   otherwise), the sums are committed in 64-bit fixed point (bit-reproducible) and the call converts them itself: dgamma /
+   dbeta come back final.  Same refusals as the forward. */
+int hsimae_attn_block_bwd(const hsimae_attn_block_weights* w, const hs_bf16* qkv, const hs_bf16* u, const hs_bf16* o, const float* lse,
+                          const hs_bf16* dx1b, const float* dx1, const float* x, hs_bf16* dqkv, float* dx, float* dgamma, float* dbeta,
+                          int64_t* det_acc, int32_t accumulate, int32_t d, int32_t heads, int32_t Ts, int32_t nsamples, int32_t mode,
+                          int32_t len_l, void* stream);
 
 /* One fused decoder Block (Models.py:303-306 at width 64, 8 heads of 8, SwiGLU hidden 164..192 — hp = 192, the image height
    the kernels are compiled for; any other hidden width returns HSIMAE_EUNSUPPORTED; sequences of 16..112 tokens),
