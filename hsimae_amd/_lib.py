@@ -123,6 +123,11 @@ class SceneParams(C.Structure):
                 ("out", vp), ("sn", i64), ("sb", i64), ("sh", i64), ("sw", i64)]
 
 
+class GwpcaParams(C.Structure):
+    _fields_ = [("scene", vp), ("scene_f64", i32), ("H", i32), ("W", i32), ("C", i32), ("nc", i32), ("group", i32), ("whiten", i32),
+                ("minmax", vp), ("mean", vp), ("lambda_", vp), ("proj", vp), ("group_off", vp)]
+
+
 class BuildInfo(C.Structure):
     _fields_ = [("abi_version", i32), ("variant_bits", C.c_uint32), ("kernel_source_hash", C.c_uint64), ("flags_hash", C.c_uint64),
                 ("default_flags", i32), ("reserved", i32)]
@@ -174,6 +179,9 @@ SYMBOLS = {
     "hsimae_cube_gather": (C.c_int, [C.POINTER(CubeParams), vp]),
     "hsimae_scene_windows": (C.c_int, [C.POINTER(SceneParams), vp]),
     "hsimae_class_argmax": (C.c_int, [C.POINTER(SceneParams), vp, i32, i32, i32, vp, vp]),
+    "hsimae_gwpca_workspace_bytes": (i64, [C.POINTER(GwpcaParams)]),
+    "hsimae_gwpca_fit": (C.c_int, [C.POINTER(GwpcaParams), vp, vp]),
+    "hsimae_gwpca_apply": (C.c_int, [C.POINTER(GwpcaParams), vp, i32, vp]),
     "hsimae_encode": (C.c_int, [C.POINTER(Config), C.POINTER(IO), vp]),
     "hsimae_encode_backward": (C.c_int, [C.POINTER(Config), C.POINTER(IO), vp, vp, BUCKET_CB, vp, vp]),
     "hsimae_agg_pool": (C.c_int, [vp, vp, i32, i32, i32, i32, vp]),
@@ -182,7 +190,7 @@ SYMBOLS = {
     "hsimae_decode_backward": (C.c_int, [C.POINTER(Config), C.POINTER(IO), vp, vp, vp, BUCKET_CB, vp, vp]),
 }
 
-ABI_VERSION = 107       # HSIMAE_VERSION of include/hsimae_hip.h these ctypes structs mirror (a CPU test compares the two)
+ABI_VERSION = 108       # HSIMAE_VERSION of include/hsimae_hip.h these ctypes structs mirror (a CPU test compares the two)
 PREC_BF16, PREC_FP8 = 0, 1
 A_BF16, A_F32, A_F32_LN = 0, 1, 2
 E_BF16, E_F32, E_RES_F32, E_POS_F32, E_SWIGLU, E_SWIGLU_BWD, E_LN_BWD = 0, 1, 2, 3, 4, 5, 6

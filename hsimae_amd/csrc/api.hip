@@ -482,6 +482,7 @@ extern "C" unsigned hs_variant_bits_fused_dec();
 extern "C" unsigned hs_variant_bits_fused_enc();
 extern "C" unsigned hs_variant_bits_loader();
 extern "C" unsigned hs_variant_bits_scene();
+extern "C" unsigned hs_variant_bits_gwpca();
 #ifndef HS_KERNEL_SOURCE_HASH
 #define HS_KERNEL_SOURCE_HASH 0ULL
 #endif
@@ -499,7 +500,7 @@ int hsimae_version(void) { return HSIMAE_VERSION; }
 int hsimae_build_info(hsimae_build_info_t* out) {
     if (!out) return HSIMAE_ENULL;
     out->abi_version = HSIMAE_VERSION;
-    out->variant_bits = hs_variant_bits() | hs_variant_bits_gemm() | hs_variant_bits_attn() | hs_variant_bits_attn_wide() | hs_variant_bits_wgrad() | hs_variant_bits_elem() | hs_variant_bits_pack() | hs_variant_bits_fused_dec() | hs_variant_bits_fused_enc() | hs_variant_bits_loader() | hs_variant_bits_scene();
+    out->variant_bits = hs_variant_bits() | hs_variant_bits_gemm() | hs_variant_bits_attn() | hs_variant_bits_attn_wide() | hs_variant_bits_wgrad() | hs_variant_bits_elem() | hs_variant_bits_pack() | hs_variant_bits_fused_dec() | hs_variant_bits_fused_enc() | hs_variant_bits_loader() | hs_variant_bits_scene() | hs_variant_bits_gwpca();
     out->kernel_source_hash = HS_KERNEL_SOURCE_HASH;
     out->flags_hash = HS_BUILD_FLAGS_HASH;
     out->default_flags = HS_BUILD_DEFAULT_FLAGS;
@@ -1050,6 +1051,13 @@ int hsimae_class_argmax(const hsimae_scene_params* p, const float* logits, int32
     if (!logits || !map) return HSIMAE_ENULL;
     if (!p->pixels && (p->p0 < 0 || p->p0 + p->N > (int64_t)p->H * p->W)) return HSIMAE_EDIMS;
     return hs_class_argmax(*p, logits, ld, num_class, first, map, S(stream));
+}
+int64_t hsimae_gwpca_workspace_bytes(const hsimae_gwpca_params* p) { return p ? hs_gwpca_workspace_bytes(*p) : (int64_t)HSIMAE_ENULL; }
+int hsimae_gwpca_fit(const hsimae_gwpca_params* p, void* workspace, void* stream) {
+    return p ? hs_gwpca_fit(*p, workspace, S(stream)) : HSIMAE_ENULL;
+}
+int hsimae_gwpca_apply(const hsimae_gwpca_params* p, void* out, int32_t out_f64, void* stream) {
+    return p ? hs_gwpca_apply(*p, out, out_f64, S(stream)) : HSIMAE_ENULL;
 }
 int hsimae_ln_bwd(const hsimae_lnbwd_params* p, void* stream) { return p ? hs_ln_bwd(*p, S(stream)) : HSIMAE_ENULL; }
 int hsimae_ln_fwd(const float* x, const float* gamma, const float* beta, float* out, int32_t M, int32_t d, void* stream) {

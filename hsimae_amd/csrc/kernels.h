@@ -40,6 +40,9 @@ int hs_loss_partials(int N, int T);
 int hs_cube_gather(const CubeParams& p, hipStream_t s);
 int hs_scene_windows(const SceneParams& p, hipStream_t s);
 int hs_class_argmax(const SceneParams& p, const float* logits, int ld, int num_class, int first, int64_t* map, hipStream_t s);
+int64_t hs_gwpca_workspace_bytes(const hsimae_gwpca_params& p);
+int hs_gwpca_fit(const hsimae_gwpca_params& p, void* workspace, hipStream_t s);
+int hs_gwpca_apply(const hsimae_gwpca_params& p, void* out, int out_f64, hipStream_t s);
 int hs_agg_pool(const float* latent, float* pooled, int N, int T, int L, int D, hipStream_t s);
 int hs_head_bwd(const float* g, const float* pooled, const float* w, float* gw, float* gb, float* dlat, int N, int C, int T, int L,
                 int D, hipStream_t s);

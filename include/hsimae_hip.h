@@ -55,8 +55,9 @@ extern "C" {
  * (proj_w .. rowscale) with the whole-sample d = 128 attention kernels they drove (superseded by the fused attention half).
  * 106: hsimae_scene_params, hsimae_scene_windows, hsimae_class_argmax (whole-scene inference).
  * 107: hsimae_attn_block_weights, hsimae_attn_block_fwd / _bwd (the fused attention halves, per kernel); hsimae_attn_fwd / _bwd
- * refuse invalid mode, len_l, Ts, kv_off, ld and lddo values they used to launch with. */
-#define HSIMAE_VERSION 107
+ * refuse invalid mode, len_l, Ts, kv_off, ld and lddo values they used to launch with.
+ * 108: hsimae_gwpca_params, hsimae_gwpca_workspace_bytes, hsimae_gwpca_fit, hsimae_gwpca_apply (group-wise PCA of a raw scene). */
+#define HSIMAE_VERSION 108
 int hsimae_version(void);
 /* What the loaded library was built from (round 6).  `variant_bits` has one bit per compile-time switch that makes a kernel
  * compute WRONG results on purpose (timing ablations: HS_ABL_*, HS_EXP_*, HS_EXPERIMENT_*) or adds instrumentation
@@ -512,6 +513,41 @@ typedef struct {
 int hsimae_scene_windows(const hsimae_scene_params* p, void* stream);
 int hsimae_class_argmax(const hsimae_scene_params* p, const float* logits, int32_t ld, int32_t num_class, int32_t first, int64_t* map,
                         void* stream);
+
+/* ------------------------------------------------------------------ group-wise PCA of a raw scene (Utils/GroupWisePCA.py) */
+/* `applyGWPCA` on the device: x = (X - min X) / (max X - min X) over the whole scene [H][W][C] (row-major, fp32 or fp64; an
+ * fp32 scene is widened to fp64 exactly, where the reference would stay in fp32), the band axis halved `group / 2` times
+ * (`split_data`: c -> c / 2, c - c / 2; 103 bands -> 25, 26, 26, 26), and per group, with n = H * W and k = nc / group: mean,
+ * covariance with divisor n - 1, eigenpairs in descending order, negative eigenvalues clipped to 0, every retained
+ * eigenvector signed so that its entry of largest magnitude (the first one on a tie) is positive, y = (x - mean) . v_j, with
+ * `whiten` times 1 / max(sqrt(lambda_j), 2^-52).  out[H][W][nc]: group g's k components at columns g k .. g k + k - 1.
+ * Arithmetic is fp64 throughout.  Stated deviations from the reference: (1) the covariance is accumulated centred, in a second
+ * pass after the mean, not as X^T X - n mean mean^T (that subtraction costs the reference 3 digits on data in [0, 1]);
+ * (2) this is the exact PCA, what scikit-learn >= 1.5 computes for any scene (`covariance_eigh` when n >= 10 w, LAPACK `full`
+ * otherwise); the 1.3 the reference pins sends a large scene through its randomized solver, an approximation of the same PCA.
+ * The eigen-solve is a cyclic Jacobi iteration on the device (to off-diagonal norm <= 2^-52 trace, at most 30 sweeps), so
+ * the fit never waits for the host.  Every reduction is combined in a fixed order: two runs are bit-identical.
+ *
+ * The model block is device memory of the caller: minmax[2] = (min, max); mean[C] of the normalised bands; lambda[C], ALL
+ * eigenvalues of each group in descending order at the group's band offsets; proj[C][k], row b = band b's coefficients of its
+ * group's k components, whitening folded in; group_off[5], the groups' band offsets, entries past `group` = C.
+ * The fit routine writes the block, the apply routine reads it; the apply routine may be given another scene with the same C, so that one fit
+ * transforms many scenes.  The workspace query returns the bytes the fit needs for these dimensions
+ * (or a negative code); its contents are scratch.  `out` is fp64 (out_f64 != 0) or fp32 rounded to nearest even.
+ *
+ * Refusals: H, W, C or nc <= 0, H * W < 2, nc not a multiple of group, nc / group larger than the narrowest group or than
+ * H * W -> HSIMAE_EDIMS; group not 1, 2 or 4, a group wider than 128 bands -> HSIMAE_EUNSUPPORTED; params, scene, a model
+ * pointer, workspace or out NULL -> HSIMAE_ENULL; scene or a model pointer not aligned to its element, workspace or out not
+ * 16-byte aligned -> HSIMAE_EALIGN.  max X == min X and non-finite values cannot be seen without a host wait: as in the
+ * reference the output is then NaN (all of it), and the kernels still terminate (sweep cap). */
+typedef struct {
+    const void* scene; int32_t scene_f64; int32_t H, W, C;
+    int32_t nc, group, whiten;
+    double* minmax; double* mean; double* lambda; double* proj; int32_t* group_off;
+} hsimae_gwpca_params;
+int64_t hsimae_gwpca_workspace_bytes(const hsimae_gwpca_params* p);
+int hsimae_gwpca_fit(const hsimae_gwpca_params* p, void* workspace, void* stream);
+int hsimae_gwpca_apply(const hsimae_gwpca_params* p, void* out, int32_t out_f64, void* stream);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus
