@@ -110,6 +110,23 @@ def build_asan(force: bool = False) -> str:
     return ASAN_LIB
 
 
+SCHED_PROBE = os.path.join(HERE, "plan_sched_asan")
+
+
+def build_sched_probe(force: bool = False) -> str:
+    """csrc/plan_sched_main.cpp, a program that prints the schedule planner's decisions (csrc/plan.h plan_block / plan_dec), under
+    the same sanitizers with their runtimes linked in, so that it runs as it is.  CPU only; tests/test_sched_plan_cpu.py runs it."""
+    src = os.path.join(CSRC, "plan_sched_main.cpp")
+    deps = [src, os.path.join(CSRC, "plan.h"), os.path.join(HERE, "..", "include", "hsimae_hip.h")]
+    if force or _stale(SCHED_PROBE, deps):
+        cmd = [os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
+               "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan", src, "-o", SCHED_PROBE]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode:
+            raise RuntimeError(f"sanitizer build failed:\n{r.stderr[-4000:]}")
+    return SCHED_PROBE
+
+
 def asan_runtime() -> str:
     """Path of libasan for LD_PRELOAD (the interpreter itself is not instrumented)."""
     r = subprocess.run([os.environ.get("CXX", "g++"), "-print-file-name=libasan.so"], capture_output=True, text=True)
@@ -119,5 +136,6 @@ def asan_runtime() -> str:
 if __name__ == "__main__":
     if "--asan" in sys.argv:
         print(build_asan(force="--force" in sys.argv))
+        print(build_sched_probe(force="--force" in sys.argv))
     else:
         print(build(force="--force" in sys.argv, verbose=True))

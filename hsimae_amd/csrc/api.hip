@@ -23,8 +23,7 @@ struct BlkP {            // resolved pointers of one block
     const float *n1w, *n1b, *bqkv, *pb, *n2w, *n2b, *w1b, *w3b, *w2b;
     const hs_bf16 *qkv, *p, *w1, *w3, *w2, *qkvT, *pT, *w13T, *w2T;
     const float *qf, *kf, *vf, *pf, *w1f, *w3f;     // fp32 master weights (row-major), staged as bf16 by the fused decoder backward
-    int prec;                                       // HSIMAE_PREC_FP8: the block's linears run on the MX e4m3 images below
-    struct I8 { const uint8_t* w; const uint8_t* s; } qkv8, p8, w1_8, w3_8, w2_8, qkvT8, pT8, w13T8, w2T8;
+    struct I8 { const uint8_t* w; const uint8_t* s; } qkv8, p8, w1_8, w3_8, w2_8, qkvT8, pT8, w13T8, w2T8;     // MX e4m3 images (BlockPlan::gemm_fp8)
 };
 
 BlkP resolve(const BlkOff& o, const BlkW& w, const float* P, const hs_bf16* wpk, const WLayout& WL) {
@@ -37,37 +36,12 @@ BlkP resolve(const BlkOff& o, const BlkW& w, const float* P, const hs_bf16* wpk,
     b.qf = P + o.qw; b.kf = P + o.kw; b.vf = P + o.vw; b.pf = P + o.pw; b.w1f = P + o.w1w; b.w3f = P + o.w3w;
     const uint8_t* base8 = reinterpret_cast<const uint8_t*>(fbase + WL.f32_elems);
     auto i8 = [&](const Img8& im) { BlkP::I8 r; r.w = base8 + im.w; r.s = base8 + im.s; return r; };
-    b.prec = HSIMAE_PREC_BF16;
     b.qkv8 = i8(w.qkv8); b.p8 = i8(w.p8); b.w1_8 = i8(w.w1_8); b.w3_8 = i8(w.w3_8); b.w2_8 = i8(w.w2_8);
     b.qkvT8 = i8(w.qkvT8); b.pT8 = i8(w.pT8); b.w13T8 = i8(w.w13T8); b.w2T8 = i8(w.w2T8);
     return b;
 }
-// ------------------------------------------------------------------ the schedule of a pass, decided ONCE, by its forward
-// Every choice between two kernel generations that changes what the forward leaves in the workspace for the backward — fused
-// or layer-at-a-time halves (which intermediates exist), q|k|v saved or recomputed, fp8 GEMMs or fused bf16 kernels — is read from
-// the environment exactly once per pass: by the forward entry point (sched_from_env), which records it for its workspace arena
-// (record_sched).  The backward entry points look the record up and follow it; they never read the environment.  A switch that
-// is flipped between a forward and its backward therefore has no effect on that pass (rounds 1-4 re-derived each decision where
-// it was needed, partly per call and partly latched in function statics: a forward that skipped the q|k|v store followed by a
-// backward that decided not to recompute read an unwritten buffer and returned HSIMAE_OK — VERDICT r04 item 5).
-// A backward on an arena no forward of this process has filled returns HSIMAE_ENOFORWARD.
-enum : uint32_t {
-    SC_FUSED_DEC = 1u << 0,        // HSIMAE_FUSED_DEC=0 clears: layer-at-a-time decoder
-    SC_DEC_SPLIT = 1u << 1,        // HSIMAE_DEC_SPLIT=0 clears: one-kernel decoder block forward
-    SC_FP8_UNFUSED = 1u << 2,      // HSIMAE_FP8_UNFUSED=1 sets: every linear of an fp8 encoder block on the MX GEMMs, no fused kernel
-    SC_FUSED_MLP = 1u << 3,        // HSIMAE_FUSED_MLP=0 clears: layer-at-a-time MLP half of the encoder blocks
-    SC_ATTN_BLOCK = 1u << 4,       // HSIMAE_FUSED_ATTN_BLOCK=0 clears: blk128_fwd
-    SC_ATTN_BLOCK256 = 1u << 5,    // HSIMAE_FUSED_ATTN_BLOCK256=0 clears: blk256_fwd
-    SC_ATTN_BLOCK_BWD = 1u << 6,   // HSIMAE_FUSED_ATTN_BLOCK_BWD=0 clears: blk128_bwd
-    SC_PROJ_BWD = 1u << 7,         // HSIMAE_FUSED_PROJ_BWD=0 clears: the projection's data gradient as its own GEMM
-    SC_LNBWD = 1u << 8,            // HSIMAE_FUSED_LNBWD=0 clears: du store + separate ln_bwd pass
-    SC_LNBWD_512 = 1u << 9,        // HSIMAE_FUSED_LNBWD_512=0 clears it at d = 512 only
-    SC_RECOMPUTE = 1u << 10,       // HSIMAE_ATTN_BWD_RECOMPUTE=0 clears: the forward saves q|k|v
-    SC_WGRAD_SLAB = 1u << 11,      // HSIMAE_WGRAD_SLAB=0 clears: float atomics in the 256 x 256-tile weight-gradient launches
-    SC_DEC_SLAB = 1u << 12,        // HSIMAE_DEC_SLAB=0 clears: float atomics in the fused decoder backward
-    SC_PLANAR = 1u << 13,          // HSIMAE_WGRAD_PLANAR=0 clears: g / dh1|dh3 of the fused MLP backward row-major instead of 64-column planes
-    SC_ATTN_BLOCK256_BWD = 1u << 14,   // HSIMAE_FUSED_ATTN_BLOCK256_BWD=0 clears: blk256_bwd (three launches instead)
-};
+// The schedule word of a pass (plan.h SC_*): read from the environment by its forward entry point, once, and recorded for the
+// workspace arena it fills; the backward entry points look the record up (HSIMAE_ENOFORWARD if there is none).
 uint32_t sched_from_env() {
     auto off = [](const char* name) { const char* e = getenv(name); return e && e[0] == '0'; };
     auto one = [](const char* name) { const char* e = getenv(name); return e && e[0] == '1'; };
@@ -122,17 +96,6 @@ int lookup_sched(const void* ws, bool need_enc, bool need_dec, uint32_t& enc, ui
     enc = it->second.enc; dec = it->second.dec;
     return HSIMAE_OK;
 }
-
-// encoder blocks under precision = FP8 (the decoder's blocks never are)
-BlkP resolve_enc(const Geo& g, uint32_t sc, const BlkOff& o, const BlkW& w, const float* P, const hs_bf16* wpk, const WLayout& WL) {
-    BlkP b = resolve(o, w, P, wpk, WL);
-    // fp8 where it pays: K >= 512.  At d = 256 the MX GEMMs (A quantised while it is staged) are no faster than the bf16 ones
-    // (Large: 37.8 vs 37.2 ms per step with the attention-half linears in fp8, r03_k), at d = 128 every linear sits inside a
-    // fused bf16 kernel; HSIMAE_FP8_UNFUSED=1 forces the MX GEMMs at every width (tests of the generic path).
-    b.prec = (g.prec == HSIMAE_PREC_FP8 && (g.D >= 512 || (sc & SC_FP8_UNFUSED))) ? HSIMAE_PREC_FP8 : HSIMAE_PREC_BF16;
-    return b;
-}
-
 
 // The two axis stacks (blocks_1 / blocks_2, Models.py:556-560) are independent until x1 + x2: the spectral
 // stack runs on a side stream so two kernels are resident at once (a single 864-workgroup launch leaves a
@@ -194,26 +157,8 @@ struct Emitter {
     }
 };
 
-// SC_FUSED_DEC clear: the layer-at-a-time decoder (A/B testing of the fused decoder kernels)
-bool fused_dec_enabled(const Geo& g, uint32_t sc) {
-    return (sc & SC_FUSED_DEC) && hs_dec_fused_supported(g.Dd, g.Hd, g.hdec, g.TL);
-}
-
-// Forward of one fused decoder block.  Default (round 3): the attention half with q / k / v in registers
-// (dec_attn_fwd_kernel, 16 waves per CU) + the MLP half as the row-panel kernel enc_mlp_fwd_kernel<64, 192>;
-// SC_DEC_SPLIT clear selects the one-kernel form (dec_block_fwd_kernel) for A/B tests.
-
-// precision = FP8 puts the MX e4m3 images on the linears that run as stand-alone GEMMs.  Where a fused bf16 kernel covers
-// the shape (the attention half at d = 128, the MLP half at d = 128 / 256) it is kept: the fused bf16 form beats the
-// layer-at-a-time fp8 form (round 2: Base 26.9 vs 19.4 ms, Large 44.1 vs 39.5 ms with every fused kernel switched off).
-// SC_FP8_UNFUSED restores that all-fp8 layer-at-a-time schedule (tests of the generic fp8 path at small widths).
-
-// SC_FUSED_MLP clear: the layer-at-a-time MLP half of the encoder blocks
-bool fused_mlp_enabled(int d, int h, uint32_t sc) {
-    return (sc & SC_FUSED_MLP) && hs_enc_mlp_fused_supported(d, h);
-}
-
-EncMlpPtrs mlp_ptrs(const BlkP& b, int h) {
+template <class B>                                     // BlkP, DecBlockPtrs or the ABI's hsimae_mlp_weights: the same member names
+EncMlpPtrs mlp_ptrs(const B& b, int h) {
     EncMlpPtrs m;
     m.n2w = b.n2w; m.n2b = b.n2b; m.w1b = b.w1b; m.w3b = b.w3b; m.w2b = b.w2b;
     m.w1 = b.w1; m.w3 = b.w3; m.w2 = b.w2; m.w2T = b.w2T; m.w13T = b.w13T; m.h = h;
@@ -232,38 +177,19 @@ DecBlockPtrs dec_ptrs(const BlkP& b, int h) {
 
 GemmParams gp() { GemmParams p; std::memset(&p, 0, sizeof(p)); return p; }
 
-int dec_block_fwd_fused(const BlkP& bp, const float* z, const BlkBuf& b, int N, int64_t Md, int TL, int Dd, int hdec, uint32_t sc, hipStream_t s) {
-    if ((sc & SC_DEC_SPLIT) && hs_enc_mlp_fused_supported(Dd, hdec)) {
-        CK(hs_dec_attn_fwd(z, b.x1, b.o, b.lse, N, TL, dec_ptrs(bp, hdec), s));
-        return hs_enc_mlp_fwd(b.x1, nullptr, b.x2, (int)Md, Dd, mlp_ptrs(bp, hdec), s);
-    }
-    return hs_dec_block_fwd(z, b.x1, b.x2, b.o, b.lse, N, TL, dec_ptrs(bp, hdec), s);
-}
-
-// The attention half's backward as ONE launch that recomputes q|k|v from u (attn.hip blk128_bwd_kernel<RC>): the same predicate
-// of the same recorded schedule word in the forward (which then does not store q|k|v) and in the backward.
-static bool attn_bwd_recompute(int d, int dp, int heads, int h, int Ts, bool f8u, uint32_t sc) {
-    if (!(sc & SC_PROJ_BWD) || !(sc & SC_LNBWD) || !(sc & SC_RECOMPUTE)) return false;
-    return !f8u && d == 128 && dp == d && fused_mlp_enabled(d, h, sc) && (sc & SC_ATTN_BLOCK) && (sc & SC_ATTN_BLOCK_BWD) &&
-           hs_attn_block_bwd_fusable(d, heads, Ts);
-}
-
 // One transformer Block forward (Models.py:303-306): 5 launches.
 // rs_a / rs_m: optional per-row DropPath factors of the attention / MLP branch (Models.py:304-305), NULL = none.
-int block_fwd(const BlkP& P, uint32_t sc, const float* x_in, const BlkBuf& b, int64_t M, int d, int heads, int h, int hp, int Ts,
-              int nsamples, int mode, int len_l, const float* res2, hipStream_t s, const float* rs_a = nullptr,
-              const float* rs_m = nullptr) {
+int block_fwd(const BlkP& P, const BlockPlan& pl, const float* x_in, const BlkBuf& b, int mode, int len_l, const float* res2,
+              hipStream_t s, const float* rs_a = nullptr, const float* rs_m = nullptr) {
     GemmParams p = gp();
-    const int dp = rup(d, 32);                        // storage width of the rows (plan.h Geo::Dp); the fused kernels need dp == d
-    const bool f8 = P.prec == HSIMAE_PREC_FP8;        // the stand-alone linears on MX e4m3 images
-    const bool f8u = f8 && (sc & SC_FP8_UNFUSED);     // ... and no fused kernel at all (HSIMAE_FP8_UNFUSED=1)
-    auto w8 = [&](GemmParams& q, const BlkP::I8& a) { if (f8) { q.prec = HSIMAE_PREC_FP8; q.W8 = a.w; q.S8 = a.s; } };
-    if (!f8u && (sc & SC_ATTN_BLOCK) && hs_attn_block_fusable(d, heads, Ts)) {
+    const int d = pl.d, dp = pl.dp, heads = pl.heads, h = pl.h, hp = pl.hp, Ts = pl.Ts, nsamples = pl.nsamples;
+    const int64_t M = pl.M;
+    auto w8 = [&](GemmParams& q, const BlkP::I8& a) { if (pl.gemm_fp8) { q.prec = HSIMAE_PREC_FP8; q.W8 = a.w; q.S8 = a.s; } };
+    if (pl.attn_fwd == ATTN_FWD_BLK128) {
         // LN1 + q|k|v + attention + projection + residual in one persistent kernel (attn.hip blk128_fwd_kernel)
-        CK(hs_attn_block_fwd(x_in, P.n1w, P.n1b, P.qkv, P.bqkv, P.p, P.pb, b.u, attn_bwd_recompute(d, dp, heads, h, Ts, f8u, sc) ? nullptr : b.qkv,
-                             b.o, b.lse, b.x1, rs_a, Ts, nsamples, mode, len_l, s));
-        if (fused_mlp_enabled(d, h, sc)) return hs_enc_mlp_fwd(b.x1, res2, b.x2, (int)M, d, mlp_ptrs(P, h), s, rs_m);
-    } else if (!f8 && dp == d && (sc & SC_ATTN_BLOCK256) && hs_attn_block256_fusable(d, heads, Ts, nsamples)) {
+        CK(hs_attn_block_fwd(x_in, P.n1w, P.n1b, P.qkv, P.bqkv, P.p, P.pb, b.u, pl.save_qkv ? b.qkv : nullptr, b.o, b.lse, b.x1, rs_a, Ts,
+                             nsamples, mode, len_l, s));
+    } else if (pl.attn_fwd == ATTN_FWD_BLK256) {
         // the same half at D = 256 (attn_wide.hip blk256_fwd_kernel: 16 waves = 16 heads, weights streamed from L2)
         CK(hs_attn_block256_fwd(x_in, P.n1w, P.n1b, P.qkv, P.bqkv, P.p, P.pb, b.u, b.qkv, b.o, b.lse, b.x1, rs_a, Ts, nsamples, mode,
                                 len_l, s));
@@ -282,49 +208,35 @@ int block_fwd(const BlkP& P, uint32_t sc, const float* x_in, const BlkBuf& b, in
     w8(p, P.p8);
     CK(hs_gemm(p, A_BF16, E_RES_F32, s));
     }
-    if (!f8u && fused_mlp_enabled(d, h, sc)) return hs_enc_mlp_fwd(b.x1, res2, b.x2, (int)M, d, mlp_ptrs(P, h), s, rs_m);
+    if (pl.mlp_fused) return hs_enc_mlp_fwd(b.x1, res2, b.x2, (int)M, d, mlp_ptrs(P, h), s, rs_m);
     p = gp();
     p.A = b.x1; p.lda = dp; p.M = (int)M; p.N = hp; p.K = dp; p.n_valid = h; p.W = P.w1; p.W2 = P.w3; p.bias = P.w1b;
     p.bias2 = P.w3b; p.gamma = P.n2w; p.beta = P.n2b; p.u_out = b.u2; p.ldu = dp; p.out = b.g; p.ldo = hp;
     p.h13 = b.h13; p.ldh = 2 * hp; p.hoff = hp; p.ln_width = d;
-    if (f8) { w8(p, P.w1_8); p.W8b = P.w3_8.w; p.S8b = P.w3_8.s; }
+    if (pl.gemm_fp8) { w8(p, P.w1_8); p.W8b = P.w3_8.w; p.S8b = P.w3_8.s; }
     CK(hs_gemm(p, A_F32_LN, E_SWIGLU, s));
     p = gp();
     p.A = b.g; p.lda = hp; p.M = (int)M; p.N = dp; p.K = hp; p.n_valid = d; p.W = P.w2; p.bias = P.w2b;
     p.res = b.x1; p.res2 = res2; p.ldr = dp; p.out = b.x2; p.ldo = dp; p.out_rowscale = rs_m;
     w8(p, P.w2_8);
-    CK(hs_gemm(p, A_BF16, E_RES_F32, s));
-    return HSIMAE_OK;
-}
-
-
-// d = 256 / 512 (rows of exactly two / four 128-column chunks): LayerNorm backward as the epilogue of the k-outer GEMM
-// (gemm.hip epilogue_ln_ko; d = 512 on 32-row panels, fp8 only: Huge fp8 49.9 -> 48.9 ms per step, but bf16 60.2 -> 61.5).
-// SC_LNBWD clear keeps the separate du store + ln_bwd pass, SC_LNBWD_512 clear keeps it at d = 512 only.
-static bool wide_ln_fused(int d, int dp, bool f8, uint32_t sc) {
-    return (sc & SC_LNBWD) && dp == d && (d == 256 || (d == 512 && f8 && (sc & SC_LNBWD_512)));
+    return hs_gemm(p, A_BF16, E_RES_F32, s);
 }
 
 // One Block backward: data grads (7 launches) + all weight/bias grads of the block (1 launch).
-int block_bwd(const BlkP& P, uint32_t sc, const BlkOff& o, float* grads, const float* x_in, const BlkBuf& b, int64_t M, int d,
-              int heads, int h, int hp, int Ts, int nsamples, int mode, int len_l, float* G0, const Scr& w,
-              float* dx_out, int accumulate, hipStream_t s, int concurrent = 1, const float* rs_a = nullptr,
-              const float* rs_m = nullptr, int64_t* det_acc = nullptr) {
+int block_bwd(const BlkP& P, const BlockPlan& pl, const BlkOff& o, float* grads, const float* x_in, const BlkBuf& b, int mode,
+              int len_l, float* G0, const Scr& w, float* dx_out, int accumulate, hipStream_t s, int concurrent = 1,
+              const float* rs_a = nullptr, const float* rs_m = nullptr, int64_t* det_acc = nullptr) {
     float* G1 = w.G1;
     GemmParams p = gp();
-    const int dp = rup(d, 32);                        // storage width (see block_fwd)
+    const int d = pl.d, dp = pl.dp, heads = pl.heads, h = pl.h, hp = pl.hp, Ts = pl.Ts, nsamples = pl.nsamples;
+    const int64_t M = pl.M;
     LnBwdParams l; std::memset(&l, 0, sizeof(l));
     l.M = (int)M; l.d = d; l.ld = dp; l.det_base = grads; l.det_acc = det_acc;
-    const bool f8 = P.prec == HSIMAE_PREC_FP8;
-    const bool f8u = f8 && (sc & SC_FP8_UNFUSED);
-    auto w8 = [&](GemmParams& q, const BlkP::I8& a) { if (f8) { q.prec = HSIMAE_PREC_FP8; q.W8 = a.w; q.S8 = a.s; } };
-    const bool fmlp = !f8u && fused_mlp_enabled(d, h, sc);
+    auto w8 = [&](GemmParams& q, const BlkP::I8& a) { if (pl.gemm_fp8) { q.prec = HSIMAE_PREC_FP8; q.W8 = a.w; q.S8 = a.s; } };
     bool g1b_done = false;
-    // g / dh1 / dh3 as 64-column planes (include/hsimae_hip.h, hsimae_wgrad_task): needs whole 32-row DMA chunks and 32-bit offsets
-    const int hp64 = rup(hp, 64);
-    const bool planar = fmlp && (sc & SC_PLANAR) && M % 32 == 0 && (M + kPlanePadRows) * 2 * (int64_t)(hp64 + 256) * 2 < (1ll << 32);
-    const int prow = planar ? (int)M + HS_PLANE_PAD_ROWS : 0;       // rows per plane (plan.h: the arena reserves kPlanePadRows)
-    if (fmlp) {
+    // g / dh1 / dh3 as 64-column planes (include/hsimae_hip.h, hsimae_wgrad_task) of prow rows (plan.h: the arena reserves kPlanePadRows)
+    const int hp64 = rup(hp, 64), prow = pl.plane_rows;
+    if (pl.mlp_fused) {
         // recompute u2 / h1 / h3 / g inside the tile; emits dx1 and the wgrad operands u2, dh1|dh3, g, bf16 dY and dx1
         CK(hs_enc_mlp_bwd(b.x1, G0, G1, b.u2, w.dh13, b.g, w.g0b, w.g1b, (int)M, d, mlp_ptrs(P, h), grads + o.n2w,
                           grads + o.n2b, s, rs_m, rs_a, HsDet{grads, reinterpret_cast<long long*>(det_acc)}, prow));
@@ -336,7 +248,7 @@ int block_bwd(const BlkP& P, uint32_t sc, const BlkOff& o, float* grads, const f
         p = gp();
         p.A = w.dh13; p.lda = 2 * hp; p.M = (int)M; p.N = dp; p.K = 2 * hp; p.n_valid = d; p.W = P.w13T;
         w8(p, P.w13T8);
-        if (wide_ln_fused(d, dp, f8, sc)) {   // LayerNorm-2 backward as the epilogue of the k-outer GEMM (the whole row is on chip)
+        if (pl.ln2_bwd == LN_GEMM_EPILOGUE) { // LayerNorm-2 backward as the epilogue of the k-outer GEMM (the whole row is on chip)
             p.out = G1; p.ldo = dp; p.res = G0; p.ldr = dp; p.lnx = b.x1; p.gamma = P.n2w; p.accumulate = 0;
             p.dgamma = grads + o.n2w; p.dbeta = grads + o.n2b; p.det_base = grads; p.det_acc = det_acc;
             if (!rs_a) { p.u_out = w.g1b; p.ldu = dp; g1b_done = true; }      // bf16 copy of dx1 from the epilogue (no DropPath factor to fold in)
@@ -368,7 +280,7 @@ int block_bwd(const BlkP& P, uint32_t sc, const BlkOff& o, float* grads, const f
         task(1, w.dqkv + dp, 3 * dp, b.u, dp, d, d, o.kw, o.kb);
         task(2, w.dqkv + 2 * dp, 3 * dp, b.u, dp, d, d, o.vw, o.vb);
         task(3, w.g1b, dp, b.o, dp, d, d, o.pw, o.pb);              // all-bf16 operands: wgrad takes its LDS-DMA path
-        if (planar) {
+        if (pl.planar) {
             task(4, w.dh13, hp64, b.u2, dp, h, d, o.w1w, o.w1b); g.t[g.ntasks - 1].dO_plane_rows = prow;
             task(5, w.dh13 + (int64_t)hp64 * prow, hp64, b.u2, dp, h, d, o.w3w, o.w3b); g.t[g.ntasks - 1].dO_plane_rows = prow;
         } else {
@@ -376,11 +288,11 @@ int block_bwd(const BlkP& P, uint32_t sc, const BlkOff& o, float* grads, const f
             task(5, w.dh13 + hp, 2 * hp, b.u2, dp, h, d, o.w3w, o.w3b);
         }
 #ifdef HS_ABL_DW2           /* timing ablation (variant builds only, see fused_enc.hip): the W2 task leaves the launch on the fused path */
-        if (!fmlp)
+        if (!pl.mlp_fused)
 #endif
-        { task(6, w.g0b, dp, b.g, planar ? hp64 : hp, d, h, o.w2w, o.w2b); g.t[g.ntasks - 1].A_plane_rows = prow; }
+        { task(6, w.g0b, dp, b.g, pl.planar ? hp64 : hp, d, h, o.w2w, o.w2b); g.t[g.ntasks - 1].A_plane_rows = prow; }
         g.M = (int)M; g.det_base = grads; g.det_acc = det_acc;
-        g.slab = (sc & SC_WGRAD_SLAB) ? w.slab : nullptr;        // this stream's slab (clear: float atomics on dW also in the 256 x 256-tile launches)
+        g.slab = pl.wgrad_slab ? w.slab : nullptr;               // this stream's slab (NULL: float atomics on dW also in the 256 x 256-tile launches)
         int tiles = 0;
         for (int i = 0; i < g.ntasks; ++i) tiles += ((g.t[i].N + 127) / 128) * ((g.t[i].K + 127) / 128);
         g.msplit = wgrad_msplit(tiles, M, concurrent);
@@ -389,40 +301,30 @@ int block_bwd(const BlkP& P, uint32_t sc, const BlkOff& o, float* grads, const f
     AttnParams a; std::memset(&a, 0, sizeof(a));
     a.qkv = b.qkv; a.ld = 3 * dp; a.d = d; a.heads = heads; a.hd = d / heads; a.Ts = Ts; a.nsamples = nsamples;
     a.mode = mode; a.len_l = len_l; a.o = b.o; a.ldo = dp; a.lse = b.lse; a.dout = w.dob; a.lddo = dp; a.dqkv = w.dqkv; a.kv_off = dp;
-    const bool fuse_pb = (sc & SC_PROJ_BWD) != 0;   // clear: keep the projection's data gradient a separate GEMM
-    const bool fuse_ln = (sc & SC_LNBWD) != 0;
-    // round 4: dO, the attention backward, du and the LayerNorm-1 backward as ONE persistent launch (attn.hip blk128_bwd_kernel);
-    // with q|k|v recomputed from u when the forward did not save them (attn_bwd_recompute: the same predicate of the same word)
-    const bool rc = attn_bwd_recompute(d, dp, heads, h, Ts, f8u, sc);
-    const bool blk_bwd = rc || (fuse_pb && fuse_ln && fmlp && !f8u && d == 128 && dp == d && hs_attn_proj_fusable(a) &&
-                                (sc & SC_ATTN_BLOCK_BWD) && hs_attn_block_bwd_fusable(d, heads, Ts));
-    // round 5, D = 256 (Large): the same four steps as one launch (attn_wide.hip blk256_bwd_kernel), from the saved q|k|v
-    const bool blk256_bwd = !blk_bwd && !f8 && dp == d && (sc & SC_ATTN_BLOCK256_BWD) && (sc & SC_LNBWD) && (sc & SC_PROJ_BWD) &&
-                            hs_attn_block256_bwd_fusable(d, heads, Ts, nsamples);
-    if (blk256_bwd) {
+    // round 5, D = 256 (Large): dO, the attention backward, du and the LayerNorm-1 backward as ONE persistent launch
+    // (attn_wide.hip blk256_bwd_kernel), from the saved q|k|v
+    if (pl.attn_bwd == ATTN_BWD_BLK256) {
         CK(hs_attn_block256_bwd(b.qkv, b.lse, w.g1b, G1, x_in, P.n1w, P.pT, P.qkvT, w.dqkv, dx_out, grads + o.n1w, grads + o.n1b, grads,
                                 reinterpret_cast<long long*>(det_acc), Ts, nsamples, mode, len_l, accumulate, s));
-        CK(run_wgrad());
-        return HSIMAE_OK;
+        return run_wgrad();
     }
-    if (blk_bwd) {
-        CK(hs_attn_block_bwd(rc ? nullptr : b.qkv, b.u, P.qkv, P.bqkv, b.o, b.lse, w.g1b, G1, x_in, P.n1w, P.pT, P.qkvT, w.dqkv, dx_out,
+    // round 4: the same at d = 128 (attn.hip blk128_bwd_kernel); q|k|v recomputed from u when the forward did not save them
+    if (pl.attn_bwd != ATTN_BWD_LAYERED) {
+        CK(hs_attn_block_bwd(pl.save_qkv ? b.qkv : nullptr, b.u, P.qkv, P.bqkv, b.o, b.lse, w.g1b, G1, x_in, P.n1w, P.pT, P.qkvT, w.dqkv, dx_out,
                              grads + o.n1w, grads + o.n1b, grads, reinterpret_cast<long long*>(det_acc), Ts, nsamples, mode, len_l,
                              accumulate, s));
-    } else {
-        p = gp();
-        p.A = w.g1b; p.lda = dp; p.M = (int)M; p.N = dp; p.K = dp; p.n_valid = dp;  // (the bf16 copy carries the DropPath factor)
-        p.W = P.pT; p.out = w.dob; p.ldo = dp;
-        w8(p, P.pT8);
-        CK(hs_gemm(p, A_BF16, E_BF16, s));
+        return run_wgrad();
     }
-    if (!blk_bwd) CK(hs_attn_bwd(a, s));
+    p = gp();
+    p.A = w.g1b; p.lda = dp; p.M = (int)M; p.N = dp; p.K = dp; p.n_valid = dp;  // (the bf16 copy carries the DropPath factor)
+    p.W = P.pT; p.out = w.dob; p.ldo = dp;
+    w8(p, P.pT8);
+    CK(hs_gemm(p, A_BF16, E_BF16, s));
+    CK(hs_attn_bwd(a, s));
     CK(run_wgrad());
-
-    if (blk_bwd) return HSIMAE_OK;
-    // du = dqkv * Wqkv and the LayerNorm-1 backward: one kernel at d = 128 (LN backward as the GEMM's epilogue,
-    // du never goes to HBM), two otherwise.  HSIMAE_FUSED_LNBWD=0 forces the two-kernel form.
-    const bool ln_fused = fuse_ln && ((d == 128 && !f8u) || wide_ln_fused(d, dp, f8, sc));
+    // du = dqkv * Wqkv and the LayerNorm-1 backward: one kernel where the GEMM has the LN backward as its epilogue (du never goes
+    // to HBM), two otherwise
+    const bool ln_fused = pl.ln1_bwd == LN_GEMM_EPILOGUE;
     p = gp();
     p.A = w.dqkv; p.lda = 3 * dp; p.M = (int)M; p.N = dp; p.K = 3 * dp; p.n_valid = d; p.W = P.qkvT;
     if (ln_fused) {
@@ -434,9 +336,6 @@ int block_bwd(const BlkP& P, uint32_t sc, const BlkOff& o, float* grads, const f
         p.out = w.du; p.ldo = dp;
         w8(p, P.qkvT8);
         CK(hs_gemm(p, A_BF16, E_F32, s));
-    }
-
-    if (!ln_fused) {
         l.du = w.du; l.x = x_in; l.gamma = P.n1w; l.dres = G1; l.dx = dx_out; l.accumulate = accumulate;
         l.dgamma = grads + o.n1w; l.dbeta = grads + o.n1b;
         CK(hs_ln_bwd(l, s));
@@ -467,6 +366,44 @@ int make_ctx(const hsimae_config* cfg, const hsimae_io* io, Ctx& c, bool need_ws
         if (c.w.bytes > io->workspace_bytes) return HSIMAE_EDIMS;
     }
     return HSIMAE_OK;
+}
+
+// The plans of a pass (plan.h), each filled once per stack per pass from the pass's schedule word
+BlockPlan enc_plan(const Ctx& c, uint32_t sc) {
+    return plan_block(c.g.D, c.g.H, c.g.h, c.K, c.N, c.Me, enc_linears_fp8(c.g.prec, c.g.D, sc), sc);
+}
+BlockPlan dec_block_plan(const Ctx& c, uint32_t sc) {           // the decoder run layer at a time
+    return plan_block(c.g.Dd, c.g.Hd, c.g.hdec, c.g.TL, c.N, c.Md, false, sc);
+}
+
+// The decoder after decoder_embed (Models.py:582-600), shared by hsimae_forward and hsimae_decode: sequence assembly from w.y,
+// the blocks, decoder_norm + decoder_pred into pred [Md][72]
+int decoder_stack_fwd(const Ctx& c, const hsimae_io* io, uint32_t sc, float* pred, hipStream_t s) {
+    const Geo& g = c.g; const Ws& w = c.w; const float* P = io->params;
+    AssembleParams as; std::memset(&as, 0, sizeof(as));
+    as.y = w.y; as.N = c.N; as.K = c.K; as.TL = g.TL; as.Dd = g.Dd; as.ld = g.Ddp; as.ids_restore = io->ids_restore; as.pos = P + c.L.dpos;
+    as.yfull = w.yfull;
+    CK(hs_assemble_fwd(as, s));
+    const DecPlan dec = plan_dec(c.g.Dd, c.g.Hd, c.g.hdec, c.g.TL, sc);
+    const BlockPlan lay = dec_block_plan(c, sc);
+    const float* z = w.yfull;
+    for (int i = 0; i < g.ddepth; ++i) {
+        const BlkP bp = resolve(c.L.bd[i], c.W.bd[i], P, io->wpk, c.W);
+        const BlkBuf& b = w.bd[i];
+        if (!dec.fused) {
+            CK(block_fwd(bp, lay, z, b, 0, 9, nullptr, s));
+        } else if (dec.split) {
+            CK(hs_dec_attn_fwd(z, b.x1, b.o, b.lse, c.N, g.TL, dec_ptrs(bp, g.hdec), s));
+            CK(hs_enc_mlp_fwd(b.x1, nullptr, b.x2, (int)c.Md, g.Dd, mlp_ptrs(bp, g.hdec), s));
+        } else {
+            CK(hs_dec_block_fwd(z, b.x1, b.x2, b.o, b.lse, c.N, g.TL, dec_ptrs(bp, g.hdec), s));
+        }
+        z = b.x2;
+    }
+    GemmParams p = gp();
+    p.A = z; p.lda = g.Ddp; p.M = (int)c.Md; p.N = 80; p.K = g.Ddp; p.n_valid = 72; p.W = io->wpk + c.W.dp; p.bias = P + c.L.dpb;
+    p.gamma = P + c.L.dnw; p.beta = P + c.L.dnb; p.u_out = w.zn; p.ldu = g.Ddp; p.out = pred; p.ldo = 72; p.ln_width = g.Dd;
+    return hs_gemm(p, A_F32_LN, E_F32, s);
 }
 
 }  // namespace
@@ -520,7 +457,7 @@ int hsimae_two_streams_active(void) { return side().ok ? 1 : 0; }
 int hsimae_effective_precision(const hsimae_config* cfg) {
     if (!cfg) return HSIMAE_ENULL;
     Geo g; CK(make_geo(cfg, g));
-    return (g.prec == HSIMAE_PREC_FP8 && (g.D >= 512 || (sched_from_env() & SC_FP8_UNFUSED))) ? HSIMAE_PREC_FP8 : HSIMAE_PREC_BF16;
+    return enc_linears_fp8(g.prec, g.D, sched_from_env()) ? HSIMAE_PREC_FP8 : HSIMAE_PREC_BF16;
 }
 
 const char* hsimae_strerror(int code) {
@@ -574,8 +511,9 @@ static int forward_impl(const hsimae_config* cfg, const hsimae_io* io, void* str
     if (!encoder_only && io->want_recons && (!io->pred_img || !io->mask_img)) return HSIMAE_ENULL;
     hipStream_t s = S(stream);
     const Geo& g = c.g; const float* P = io->params; const Ws& w = c.w;
-    const uint32_t sc = sched_from_env();             // the pass's schedule: read here, recorded for the backward (see SC_*)
+    const uint32_t sc = sched_from_env();             // the pass's schedule: read here, recorded for the backward (plan.h SC_*)
     record_sched(io->workspace, true, !encoder_only, sc);
+    const BlockPlan enc = enc_plan(c, sc);
 
     MaskParams m; m.noise1 = io->noise1; m.noise2 = io->noise2; m.N = c.N; m.T = g.T; m.L = 9; m.len_t = c.len_t;
     m.len_l = c.len_l; m.ids_keep = io->ids_keep; m.ids_restore = io->ids_restore; m.mask = io->mask;
@@ -600,28 +538,27 @@ static int forward_impl(const hsimae_config* cfg, const hsimae_io* io, void* str
         const float* xb = w.x0;
         for (int i = 0; i < g.sdepth; ++i) {
             // spatial stack: attend within one kept band group (Models.py:553,556)
-            BlkP b1 = resolve_enc(g, sc, c.L.b1[i], c.W.b1[i], P, io->wpk, c.W);
+            BlkP b1 = resolve(c.L.b1[i], c.W.b1[i], P, io->wpk, c.W);
             const DropRs r1 = drop_rs(io, i, c.Me), r2d = drop_rs(io, g.sdepth + i, c.Me);
-            CK(block_fwd(b1, sc, xa, w.b1[i], c.Me, g.D, g.H, g.h, g.hp, c.K, c.N, 1, c.len_l, nullptr, s, r1.a, r1.m));
+            CK(block_fwd(b1, enc, xa, w.b1[i], 1, c.len_l, nullptr, s, r1.a, r1.m));
             xa = w.b1[i].x2;
             // spectral stack: attend within one kept position (Models.py:554,559)
-            BlkP b2 = resolve_enc(g, sc, c.L.b2[i], c.W.b2[i], P, io->wpk, c.W);
+            BlkP b2 = resolve(c.L.b2[i], c.W.b2[i], P, io->wpk, c.W);
             const bool last = (i == g.sdepth - 1);
             const float* r2 = last ? xa : nullptr;                      // x1 + x2 fused into the last epilogue (Models.py:564)
             if (last && forked) {                                       // needs the spatial stack's result: rejoin first
                 CK((int)hipEventRecord(sd.join, sd.s));
                 CK((int)hipStreamWaitEvent(s, sd.join, 0));
             }
-            CK(block_fwd(b2, sc, xb, w.b2[i], c.Me, g.D, g.H, g.h, g.hp, c.K, c.N, 2, c.len_l, r2, (forked && !last) ? sd.s : s,
-                         r2d.a, r2d.m));
+            CK(block_fwd(b2, enc, xb, w.b2[i], 2, c.len_l, r2, (forked && !last) ? sd.s : s, r2d.a, r2d.m));
             xb = w.b2[i].x2;
         }
         x = xb;
     }
     for (int i = 0; i < g.nfus; ++i) {
-        BlkP bp = resolve_enc(g, sc, c.L.bf[i], c.W.bf[i], P, io->wpk, c.W);
+        BlkP bp = resolve(c.L.bf[i], c.W.bf[i], P, io->wpk, c.W);
         const DropRs rf = drop_rs(io, (g.has_axis ? 2 * g.sdepth : 0) + i, c.Me);
-        CK(block_fwd(bp, sc, x, w.bf[i], c.Me, g.D, g.H, g.h, g.hp, c.K, c.N, 0, c.len_l, nullptr, s, rf.a, rf.m));
+        CK(block_fwd(bp, enc, x, w.bf[i], 0, c.len_l, nullptr, s, rf.a, rf.m));
         x = w.bf[i].x2;
     }
     if (encoder_only) {                       // `norm` only (Models.py:570 / 892): the latent the fine-tuning head reads
@@ -633,23 +570,7 @@ static int forward_impl(const hsimae_config* cfg, const hsimae_io* io, void* str
     p.A = x; p.lda = g.Dp; p.M = (int)c.Me; p.N = g.Ddp; p.K = g.Dp; p.n_valid = g.Dd; p.W = io->wpk + c.W.de; p.bias = P + c.L.deb;
     p.gamma = P + c.L.nw; p.beta = P + c.L.nb; p.u_out = w.lat; p.ldu = g.Dp; p.out = w.y; p.ldo = g.Ddp; p.ln_width = g.D;
     CK(hs_gemm(p, A_F32_LN, E_F32, s));
-    AssembleParams as; std::memset(&as, 0, sizeof(as));
-    as.y = w.y; as.N = c.N; as.K = c.K; as.TL = g.TL; as.Dd = g.Dd; as.ld = g.Ddp; as.ids_restore = io->ids_restore; as.pos = P + c.L.dpos;
-    as.yfull = w.yfull;
-    CK(hs_assemble_fwd(as, s));
-    const float* z = w.yfull;
-    const bool fdec = fused_dec_enabled(g, sc);
-    for (int i = 0; i < g.ddepth; ++i) {
-        BlkP bp = resolve(c.L.bd[i], c.W.bd[i], P, io->wpk, c.W);
-        if (fdec) CK(dec_block_fwd_fused(bp, z, w.bd[i], c.N, c.Md, g.TL, g.Dd, g.hdec, sc, s));
-        else CK(block_fwd(bp, sc, z, w.bd[i], c.Md, g.Dd, g.Hd, g.hdec, g.hpd, g.TL, c.N, 0, 9, nullptr, s));
-        z = w.bd[i].x2;
-    }
-    // decoder_norm + decoder_pred (Models.py:597-600)
-    p = gp();
-    p.A = z; p.lda = g.Ddp; p.M = (int)c.Md; p.N = 80; p.K = g.Ddp; p.n_valid = 72; p.W = io->wpk + c.W.dp; p.bias = P + c.L.dpb;
-    p.gamma = P + c.L.dnw; p.beta = P + c.L.dnb; p.u_out = w.zn; p.ldu = g.Ddp; p.out = w.pred; p.ldo = 72; p.ln_width = g.Dd;
-    CK(hs_gemm(p, A_F32_LN, E_F32, s));
+    CK(decoder_stack_fwd(c, io, sc, w.pred, s));
     LossParams lp; std::memset(&lp, 0, sizeof(lp));
     const float sum_mask = (float)((int64_t)c.N * (g.TL - c.K));
     lp.x = io->x; lp.sn = io->sn; lp.sb = io->sb; lp.sh = io->sh; lp.sw = io->sw; lp.N = c.N; lp.T = g.T; lp.pred = w.pred;
@@ -682,34 +603,19 @@ int hsimae_decode(const hsimae_config* cfg, const hsimae_io* io, const float* la
     p.out = w.y; p.ldo = g.Ddp;
     CK(hs_gemm(p, A_F32, E_F32, s));
     CK(hs_rows_to_bf16(lat_in, w.lat, c.Me, g.Dp, nullptr, s));     // decoder_embed's wgrad operand (hsimae_decode_backward)
-    AssembleParams as; std::memset(&as, 0, sizeof(as));
-    as.y = w.y; as.N = c.N; as.K = c.K; as.TL = g.TL; as.Dd = g.Dd; as.ld = g.Ddp; as.ids_restore = io->ids_restore; as.pos = P + c.L.dpos;
-    as.yfull = w.yfull;
-    CK(hs_assemble_fwd(as, s));
-    const float* z = w.yfull;
-    const bool fdec = fused_dec_enabled(g, sc);
-    for (int i = 0; i < g.ddepth; ++i) {
-        BlkP bp = resolve(c.L.bd[i], c.W.bd[i], P, io->wpk, c.W);
-        if (fdec) CK(dec_block_fwd_fused(bp, z, w.bd[i], c.N, c.Md, g.TL, g.Dd, g.hdec, sc, s));
-        else CK(block_fwd(bp, sc, z, w.bd[i], c.Md, g.Dd, g.Hd, g.hdec, g.hpd, g.TL, c.N, 0, 9, nullptr, s));
-        z = w.bd[i].x2;
-    }
-    p = gp();                                 // decoder_norm + decoder_pred (Models.py:597-600)
-    p.A = z; p.lda = g.Ddp; p.M = (int)c.Md; p.N = 80; p.K = g.Ddp; p.n_valid = 72; p.W = io->wpk + c.W.dp; p.bias = P + c.L.dpb;
-    p.gamma = P + c.L.dnw; p.beta = P + c.L.dnb; p.u_out = w.zn; p.ldu = g.Ddp; p.out = pred; p.ldo = 72; p.ln_width = g.Dd;
-    return hs_gemm(p, A_F32_LN, E_F32, s);
+    return decoder_stack_fwd(c, io, sc, pred, s);
 }
 
 // Backward of the encoder stacks + patch embedding, from d(x of the last encoder block) in w.G0.  Shared by
 // hsimae_backward (after the decoder) and hsimae_encode_backward (after `norm`).
 static int encoder_backward(const Ctx& c, const hsimae_io* io, float* grads, hipStream_t s, Emitter& emit, uint32_t sc) {
     const Geo& g = c.g; const float* P = io->params; const Ws& w = c.w; const PLayout& L = c.L;
+    const BlockPlan enc = enc_plan(c, sc);
     for (int i = g.nfus - 1; i >= 0; --i) {
-        BlkP bp = resolve_enc(g, sc, L.bf[i], c.W.bf[i], P, io->wpk, c.W);
+        BlkP bp = resolve(L.bf[i], c.W.bf[i], P, io->wpk, c.W);
         const float* xin = (i > 0) ? w.bf[i - 1].x2 : (g.has_axis ? w.b2[g.sdepth - 1].x2 : w.x0);
         const DropRs rf = drop_rs(io, (g.has_axis ? 2 * g.sdepth : 0) + i, c.Me);
-        CK(block_bwd(bp, sc, L.bf[i], grads, xin, w.bf[i], c.Me, g.D, g.H, g.h, g.hp, c.K, c.N, 0, c.len_l, w.G0, w.sc, w.G0, 0, s, 1,
-                     rf.a, rf.m, io->det_acc));
+        CK(block_bwd(bp, enc, L.bf[i], grads, xin, w.bf[i], 0, c.len_l, w.G0, w.sc, w.G0, 0, s, 1, rf.a, rf.m, io->det_acc));
         CK(emit(L.bf[i].n1w, L.bf[i].end, s));
     }
     if (g.has_axis) {
@@ -727,21 +633,19 @@ static int encoder_backward(const Ctx& c, const hsimae_io* io, float* grads, hip
         // for the right stream through an event); without one the side stream's ranges wait for the join
         const bool per_block = emit.bucket != nullptr || !forked;
         for (int i = g.sdepth - 1; i >= 0; --i) {
-            BlkP b2 = resolve_enc(g, sc, L.b2[i], c.W.b2[i], P, io->wpk, c.W);
+            BlkP b2 = resolve(L.b2[i], c.W.b2[i], P, io->wpk, c.W);
             const DropRs r1 = drop_rs(io, i, c.Me), r2d = drop_rs(io, g.sdepth + i, c.Me);
             const float* xin2 = (i > 0) ? w.b2[i - 1].x2 : w.x0;
-            CK(block_bwd(b2, sc, L.b2[i], grads, xin2, w.b2[i], c.Me, g.D, g.H, g.h, g.hp, c.K, c.N, 2, c.len_l, w.G0, scr2, w.G0, 0, s2, forked ? 2 : 1,
-                         r2d.a, r2d.m, io->det_acc));
+            CK(block_bwd(b2, enc, L.b2[i], grads, xin2, w.b2[i], 2, c.len_l, w.G0, scr2, w.G0, 0, s2, forked ? 2 : 1, r2d.a, r2d.m, io->det_acc));
             if (per_block) CK(emit(L.b2[i].n1w, L.b2[i].end, s2));
             if (i == 0 && forked) {                 // the spatial stack's last step accumulates onto the spectral dX
                 CK((int)hipEventRecord(sd.join, sd.s));
                 CK((int)hipStreamWaitEvent(s, sd.join, 0));
             }
-            BlkP b1 = resolve_enc(g, sc, L.b1[i], c.W.b1[i], P, io->wpk, c.W);
+            BlkP b1 = resolve(L.b1[i], c.W.b1[i], P, io->wpk, c.W);
             const float* xin1 = (i > 0) ? w.b1[i - 1].x2 : w.x0;
             float* out = (i == 0) ? w.G0 : w.G2;
-            CK(block_bwd(b1, sc, L.b1[i], grads, xin1, w.b1[i], c.Me, g.D, g.H, g.h, g.hp, c.K, c.N, 1, c.len_l, w.G2, w.sc, out, i == 0, s, forked ? 2 : 1,
-                         r1.a, r1.m, io->det_acc));
+            CK(block_bwd(b1, enc, L.b1[i], grads, xin1, w.b1[i], 1, c.len_l, w.G2, w.sc, out, i == 0, s, forked ? 2 : 1, r1.a, r1.m, io->det_acc));
             if (per_block) CK(emit(L.b1[i].n1w, L.b1[i].end, s));
         }
         if (!per_block) {     // back-to-front, all complete on the caller's stream by now
@@ -784,11 +688,12 @@ static int decoder_backward(const Ctx& c, const hsimae_io* io, float* grads, hip
     CK(hs_ln_bwd(l, s));
     CK(emit(L.dnw, L.total, s));
 
-    const bool fdec = fused_dec_enabled(g, sc);
+    const DecPlan dec = plan_dec(c.g.Dd, c.g.Hd, c.g.hdec, c.g.TL, sc);
+    const BlockPlan lay = dec_block_plan(c, sc);
     for (int i = g.ddepth - 1; i >= 0; --i) {
         BlkP bp = resolve(L.bd[i], c.W.bd[i], P, io->wpk, c.W);
         const float* xin = (i == 0) ? w.yfull : w.bd[i - 1].x2;
-        if (fdec) {
+        if (dec.fused) {
             const BlkOff& o = L.bd[i];
             DecBlockGrads dg;
             dg.n1w = grads + o.n1w; dg.n1b = grads + o.n1b; dg.qw = grads + o.qw; dg.qb = grads + o.qb;
@@ -799,12 +704,11 @@ static int decoder_backward(const Ctx& c, const hsimae_io* io, float* grads, hip
             dg.det = HsDet{grads, reinterpret_cast<long long*>(io->det_acc)};
             // MLP half then attention half, both persistent with the block's weight gradients held in registers
             // (measured equal to "row-tile kernel + wgrad operands through HBM" at d = 64, with 0.7 GB less traffic)
-            // SC_DEC_SLAB clear: commit the in-register weight gradients with float atomics (rounds 1-2) instead of slab + reduce
+            // slab NULL: commit the in-register weight gradients with float atomics (rounds 1-2) instead of slab + reduce
             CK(hs_dec_block_bwd(xin, w.bd[i].x1, w.G0, w.G1, w.G0, w.bd[i].o, w.bd[i].lse, c.N, g.TL, dec_ptrs(bp, g.hdec), dg, s,
-                                (sc & SC_DEC_SLAB) ? w.slab : nullptr));
+                                dec.slab ? w.slab : nullptr));
         } else {
-            CK(block_bwd(bp, sc, L.bd[i], grads, xin, w.bd[i], c.Md, g.Dd, g.Hd, g.hdec, g.hpd, g.TL, c.N, 0, 9, w.G0, w.sc, w.G0, 0, s, 1, nullptr, nullptr,
-                         io->det_acc));
+            CK(block_bwd(bp, lay, L.bd[i], grads, xin, w.bd[i], 0, 9, w.G0, w.sc, w.G0, 0, s, 1, nullptr, nullptr, io->det_acc));
         }
         CK(emit(L.bd[i].n1w, L.bd[i].end, s));
     }
@@ -826,6 +730,16 @@ static int decoder_backward(const Ctx& c, const hsimae_io* io, float* grads, hip
     return HSIMAE_OK;
 }
 
+// Backward of `norm` (Models.py:570 / 892): du [Me][Dp] -> d(x of the last encoder block) in w.G0
+static int norm_backward(const Ctx& c, const hsimae_io* io, const float* du, float* grads, hipStream_t s) {
+    const Geo& g = c.g; const Ws& w = c.w; const PLayout& L = c.L;
+    LnBwdParams l; std::memset(&l, 0, sizeof(l));
+    l.du = du; l.x = g.nfus ? w.bf[g.nfus - 1].x2 : (g.has_axis ? w.b2[g.sdepth - 1].x2 : w.x0);
+    l.gamma = io->params + L.nw; l.dres = nullptr; l.dx = w.G0; l.dgamma = grads + L.nw; l.dbeta = grads + L.nb;
+    l.M = (int)c.Me; l.d = g.D; l.ld = g.Dp; l.det_base = grads; l.det_acc = io->det_acc;
+    return hs_ln_bwd(l, s);
+}
+
 int hsimae_backward(const hsimae_config* cfg, const hsimae_io* io, float* grads, hsimae_bucket_cb cb, void* user,
                     void* stream) {
     Ctx c; CK(make_ctx(cfg, io, c, true));
@@ -834,15 +748,10 @@ int hsimae_backward(const hsimae_config* cfg, const hsimae_io* io, float* grads,
     CK(lookup_sched(io->workspace, true, true, sc_enc, sc_dec));
     hipStream_t s = S(stream);
     if (io->det_acc) CK((int)hipMemsetAsync(io->det_acc, 0, (size_t)c.L.total * 8, s));     // deterministic mode: fixed-point shadow sums
-    const Geo& g = c.g; const float* P = io->params; const Ws& w = c.w; const PLayout& L = c.L;
+    const Geo& g = c.g; const Ws& w = c.w; const PLayout& L = c.L;
     Emitter emit{cb, user, cb ? S(io->bucket_stream) : nullptr, 0, grads, io->det_acc};
     CK(decoder_backward(c, io, grads, s, emit, sc_dec));
-    // norm (Models.py:570)
-    const float* xf = g.nfus ? w.bf[g.nfus - 1].x2 : (g.has_axis ? w.b2[g.sdepth - 1].x2 : w.x0);
-    LnBwdParams l; std::memset(&l, 0, sizeof(l));
-    l.du = w.du; l.x = xf; l.gamma = P + L.nw; l.dres = nullptr; l.dx = w.G0; l.dgamma = grads + L.nw; l.dbeta = grads + L.nb;
-    l.M = (int)c.Me; l.d = g.D; l.ld = g.Dp; l.det_base = grads; l.det_acc = io->det_acc;
-    CK(hs_ln_bwd(l, s));
+    CK(norm_backward(c, io, w.du, grads, s));
     CK(emit(L.nw, L.deb + g.Dd, s));
     return encoder_backward(c, io, grads, s, emit, sc_enc);
 }
@@ -871,18 +780,13 @@ int hsimae_encode_backward(const hsimae_config* cfg, const hsimae_io* io, const 
     CK(lookup_sched(io->workspace, true, false, sc_enc, sc_dec));
     hipStream_t s = S(stream);
     if (io->det_acc) CK((int)hipMemsetAsync(io->det_acc, 0, (size_t)c.L.total * 8, s));     // deterministic mode: fixed-point shadow sums
-    const Geo& g = c.g; const float* P = io->params; const Ws& w = c.w; const PLayout& L = c.L;
-    // `norm` (Models.py:892): dlatent -> d(x of the last encoder block) in G0
-    const float* xf = g.nfus ? w.bf[g.nfus - 1].x2 : (g.has_axis ? w.b2[g.sdepth - 1].x2 : w.x0);
-    LnBwdParams l; std::memset(&l, 0, sizeof(l));
+    const Geo& g = c.g; const Ws& w = c.w; const PLayout& L = c.L;
     const float* dlat = dlatent;
     if (g.Dp != g.D) {          // rows stored wider than the model: the caller's [Me][D] gradient into a padded buffer
         CK((int)hipMemcpy2DAsync(w.du, (size_t)g.Dp * 4, dlatent, (size_t)g.D * 4, (size_t)g.D * 4, (size_t)c.Me, hipMemcpyDeviceToDevice, s));
         dlat = w.du;
     }
-    l.du = dlat; l.x = xf; l.gamma = P + L.nw; l.dres = nullptr; l.dx = w.G0; l.dgamma = grads + L.nw; l.dbeta = grads + L.nb;
-    l.M = (int)c.Me; l.d = g.D; l.ld = g.Dp; l.det_base = grads; l.det_acc = io->det_acc;
-    CK(hs_ln_bwd(l, s));
+    CK(norm_backward(c, io, dlat, grads, s));
     Emitter emit{cb, user, cb ? S(io->bucket_stream) : nullptr, 0, grads, io->det_acc};
     CK(emit(L.nw, L.nb + g.D, s));
     return encoder_backward(c, io, grads, s, emit, sc_enc);
@@ -900,18 +804,12 @@ int hsimae_gemm_tiled(const hsimae_gemm_params* p, int32_t a_kind, int32_t epilo
 int hsimae_pack_matrix(const hsimae_pack_desc* d, int32_t n, int32_t max_elems, void* stream) {
     return d ? hs_pack(d, n, max_elems, S(stream)) : HSIMAE_ENULL;
 }
-static EncMlpPtrs mlp_from_abi(const hsimae_mlp_weights* w) {
-    EncMlpPtrs m;
-    m.n2w = w->n2w; m.n2b = w->n2b; m.w1b = w->w1b; m.w3b = w->w3b; m.w2b = w->w2b;
-    m.w1 = w->w1; m.w3 = w->w3; m.w2 = w->w2; m.w2T = w->w2T; m.w13T = w->w13T; m.h = w->hidden;
-    return m;
-}
 int hsimae_enc_mlp_fwd(const float* x1, const float* res2, float* x2, int32_t M, int32_t d, const hsimae_mlp_weights* w,
                        const float* rowscale, void* stream) {
     if (M <= 0) return HSIMAE_OK;
     if (!x1 || !x2 || !w) return HSIMAE_ENULL;
-    if (!hs_enc_mlp_fused_supported(d, w->hidden)) return HSIMAE_EUNSUPPORTED;
-    return hs_enc_mlp_fwd(x1, res2, x2, M, d, mlp_from_abi(w), S(stream), rowscale);
+    if (!mlp_fusable(d, w->hidden)) return HSIMAE_EUNSUPPORTED;
+    return hs_enc_mlp_fwd(x1, res2, x2, M, d, mlp_ptrs(*w, w->hidden), S(stream), rowscale);
 }
 int hsimae_enc_mlp_bwd(const float* x1, const float* dy, float* dx1, hs_bf16* u2, hs_bf16* dh13, hs_bf16* g, hs_bf16* dyb,
                        hs_bf16* dx1b, int32_t M, int32_t d, const hsimae_mlp_weights* w, float* g_n2w, float* g_n2b,
@@ -921,8 +819,8 @@ int hsimae_enc_mlp_bwd(const float* x1, const float* dy, float* dx1, hs_bf16* u2
     if (!x1 || !dy || !dx1 || !w || !g_n2w || !g_n2b) return HSIMAE_ENULL;
     // operand outputs are optional as groups: {u2, dyb} and {dh13, g} (NULL = not written: the data path alone), dx1b on its own
     if ((!u2) != (!dyb) || (!dh13) != (!g)) return HSIMAE_ENULL;
-    if (!hs_enc_mlp_fused_supported(d, w->hidden)) return HSIMAE_EUNSUPPORTED;
-    return hs_enc_mlp_bwd(x1, dy, dx1, u2, dh13, g, dyb, dx1b, M, d, mlp_from_abi(w), g_n2w, g_n2b, S(stream), rs_mlp, rs_attn,
+    if (!mlp_fusable(d, w->hidden)) return HSIMAE_EUNSUPPORTED;
+    return hs_enc_mlp_bwd(x1, dy, dx1, u2, dh13, g, dyb, dx1b, M, d, mlp_ptrs(*w, w->hidden), g_n2w, g_n2b, S(stream), rs_mlp, rs_attn,
                           HsDet{nullptr, nullptr}, plane_rows);
 }
 static DecBlockPtrs dec_from_abi(const hsimae_dec_block_weights* w) {
@@ -937,14 +835,11 @@ int hsimae_dec_block_fwd(const hsimae_dec_block_weights* w, const float* x, floa
                          int32_t nsamples, int32_t Ts, int32_t split, void* stream) {
     if (nsamples <= 0) return HSIMAE_OK;
     if (!w || !x || !x1 || !x2 || !o || !lse) return HSIMAE_ENULL;
-    if (!hs_dec_fused_supported(64, 8, w->hidden, Ts)) return HSIMAE_EUNSUPPORTED;
+    if (!dec_fusable(kDecD, kDecHeads, w->hidden, Ts)) return HSIMAE_EUNSUPPORTED;
     const DecBlockPtrs d = dec_from_abi(w);
     if (split) {
         CK(hs_dec_attn_fwd(x, x1, o, lse, nsamples, Ts, d, S(stream)));
-        EncMlpPtrs m;
-        m.n2w = d.n2w; m.n2b = d.n2b; m.w1b = d.w1b; m.w3b = d.w3b; m.w2b = d.w2b;
-        m.w1 = d.w1; m.w3 = d.w3; m.w2 = d.w2; m.w2T = d.w2T; m.w13T = nullptr; m.h = d.h;
-        return hs_enc_mlp_fwd(x1, nullptr, x2, nsamples * Ts, 64, m, S(stream));
+        return hs_enc_mlp_fwd(x1, nullptr, x2, nsamples * Ts, kDecD, mlp_ptrs(d, d.h), S(stream));      // (d.w13T is NULL: forward only)
     }
     return hs_dec_block_fwd(x, x1, x2, o, lse, nsamples, Ts, d, S(stream));
 }
@@ -955,7 +850,7 @@ int hsimae_dec_block_bwd(const hsimae_dec_block_weights* w, const hsimae_dec_blo
                          int32_t Ts, float* slab, void* stream) {
     if (nsamples <= 0) return HSIMAE_OK;
     if (!w || !g || !x || !x1 || !dy || !dx1_tmp || !dx || !o || !lse) return HSIMAE_ENULL;
-    if (!hs_dec_fused_supported(64, 8, w->hidden, Ts)) return HSIMAE_EUNSUPPORTED;
+    if (!dec_fusable(kDecD, kDecHeads, w->hidden, Ts)) return HSIMAE_EUNSUPPORTED;
     DecBlockGrads dg;
     dg.n1w = g->n1w; dg.n1b = g->n1b; dg.qw = g->qw; dg.qb = g->qb; dg.kw = g->kw; dg.kb = g->kb; dg.vw = g->vw; dg.vb = g->vb;
     dg.pw = g->pw; dg.pb = g->pb; dg.n2w = g->n2w; dg.n2b = g->n2b; dg.w1w = g->w1w; dg.w1b = g->w1b; dg.w2w = g->w2w;
@@ -968,11 +863,11 @@ int hsimae_attn_bwd(const hsimae_attn_params* p, void* stream) { return p ? hs_a
 static int attn_block_check(const hsimae_attn_block_weights* w, int d, int heads, int Ts, int nsamples, int mode, int len_l,
                             std::initializer_list<const void*> rows) {
     if (!w || !w->n1w || !w->n1b || !w->bqkv || !w->pb || !w->qkv || !w->p || !w->qkvT || !w->pT) return HSIMAE_ENULL;
-    if (!((d == 128 && heads == 8) || (d == 256 && heads == 16))) return HSIMAE_EUNSUPPORTED;
+    if (!((d == kAttn128D && heads == kAttn128Heads) || (d == kAttn256D && heads == kAttn256Heads))) return HSIMAE_EUNSUPPORTED;
     if (mode < 0 || mode > 2) return HSIMAE_EUNSUPPORTED;
     if (Ts < 1 || (mode != 0 && len_l < 1)) return HSIMAE_EDIMS;
-    if (Ts > 32) return HSIMAE_EUNSUPPORTED;
-    if (d == 256 && !hs_attn_block256_fusable(d, heads, Ts, nsamples)) return HSIMAE_EUNSUPPORTED;     // 32-bit offsets
+    if (Ts > kAttnMaxTs) return HSIMAE_EUNSUPPORTED;
+    if (d == kAttn256D && !attn256_fusable(d, heads, Ts, nsamples)) return HSIMAE_EUNSUPPORTED;     // 32-bit offsets
     for (const void* r : rows) {
         if (!r) return HSIMAE_ENULL;
         if (reinterpret_cast<uintptr_t>(r) & 15) return HSIMAE_EALIGN;

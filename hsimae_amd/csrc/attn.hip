@@ -13,6 +13,7 @@
 // recomputes the scores in both orientations instead of transposing dS through LDS.
 #include "common.h"
 #include "kernels.h"
+#include "plan.h"
 #ifndef HS_BLK_PRIO
 #define HS_BLK_PRIO 0      /* s_setprio level of waves 4-7 in blk128_fwd / blk128_bwd (round 6) */
 #endif
@@ -1264,48 +1265,39 @@ int dispatch(const AttnParams& p, hipStream_t s) {
 }  // namespace
 
 int hs_attn_fwd(const AttnParams& p, hipStream_t s) { return dispatch<false>(p, s); }
-// shape predicate of the fused attention half at d = 128 (blk128_fwd / blk128_bwd): 8 heads of 16, <= 32 tokens, unpadded rows
-bool hs_attn_proj_fusable(const AttnParams& p) {
-    return p.lse && p.d == 128 && p.heads == 8 && p.hd == 16 && p.Ts <= 32 && p.ld == 384 && p.ldo == 128;
-}
 int hs_attn_bwd(const AttnParams& p, hipStream_t s) { return dispatch<true>(p, s); }
 
-// LN1 + q|k|v + attention + projection + residual in one launch (see blk128_fwd_kernel).  Shape predicate only: whether a pass
-// uses it is part of the schedule word its forward records (api.hip SC_ATTN_BLOCK, HSIMAE_FUSED_ATTN_BLOCK=0 clears it).
-bool hs_attn_block_fusable(int d, int heads, int Ts) {
-    AttnParams q = AttnParams();
-    q.d = d; q.heads = heads; q.hd = heads ? d / heads : 0; q.Ts = Ts; q.ld = 384; q.ldo = 128; q.lse = reinterpret_cast<float*>(1);
-    return hs_attn_proj_fusable(q);
-}
+// LN1 + q|k|v + attention + projection + residual in one launch (see blk128_fwd_kernel).  Which passes use it: plan.h plan_block();
+// the shape it selects the kernel for is the one instantiated here (NT <= 2 tiles of 16 tokens, 8 waves = 8 heads of 16).
+static_assert(hsplan::kAttn128D == BIR && hsplan::kAttn128D == 16 * hsplan::kAttn128Heads,
+              "plan.h attn128_fusable must select exactly the shape blk128_fwd / blk128_bwd are instantiated for");
 int hs_attn_block_fwd(const float* x, const float* n1w, const float* n1b, const hs_bf16* wqkv, const float* bqkv, const hs_bf16* wp,
                       const float* pb, hs_bf16* u, hs_bf16* qkv, hs_bf16* o, float* lse, float* x1, const float* rowscale, int Ts,
                       int nsamples, int mode, int len_l, hipStream_t s) {
     if (nsamples <= 0) return HS_OK;
-    if (Ts < 1 || Ts > 32) return HS_EUNSUPPORTED;
+    if (Ts < 1 || Ts > hsplan::kAttnMaxTs) return HS_EUNSUPPORTED;
     Blk128Args a;
     a.x = x; a.n1w = n1w; a.n1b = n1b; a.wqkv = wqkv; a.bqkv = bqkv; a.wp = wp; a.pb = pb; a.u = u; a.qkv = qkv; a.o = o;
     a.lse = lse; a.x1 = x1; a.rowscale = rowscale; a.Ts = Ts; a.nsamples = nsamples; a.mode = mode; a.len_l = len_l;
     // two samples in hand per iteration (one: 84 instead of 74 us in round 3; three measured 0.5 % slower than two)
-    return Ts <= 16 ? launch_blk128<1, 2>(a, s) : launch_blk128<2, 2>(a, s);
+    return Ts <= hsplan::kAttnTile ? launch_blk128<1, 2>(a, s) : launch_blk128<2, 2>(a, s);
 }
 
-// dO + attention backward + du + LayerNorm-1 backward in one launch (see blk128_bwd_kernel).  Shape predicate only (api.hip
-// SC_ATTN_BLOCK_BWD, HSIMAE_FUSED_ATTN_BLOCK_BWD=0 clears it in the forward's schedule word).
-bool hs_attn_block_bwd_fusable(int d, int heads, int Ts) { return hs_attn_block_fusable(d, heads, Ts); }
+// dO + attention backward + du + LayerNorm-1 backward in one launch (see blk128_bwd_kernel)
 int hs_attn_block_bwd(const hs_bf16* qkv, const hs_bf16* u, const hs_bf16* wqkv, const float* bqkv, const hs_bf16* o, const float* lse,
                       const hs_bf16* dx1b, const float* dx1, const float* x, const float* gamma, const hs_bf16* wpT, const hs_bf16* wqkvT,
                       hs_bf16* dqkv, float* dx, float* dgamma, float* dbeta, const float* det_base, long long* det_acc, int Ts,
                       int nsamples, int mode, int len_l, int accumulate, hipStream_t s) {
     if (nsamples <= 0) return HS_OK;
-    if (Ts < 1 || Ts > 32) return HS_EUNSUPPORTED;
+    if (Ts < 1 || Ts > hsplan::kAttnMaxTs) return HS_EUNSUPPORTED;
     const bool rc = qkv == nullptr;                  // no saved q|k|v: recompute them from u
     if (rc && !(u && wqkv && bqkv)) return HS_EUNSUPPORTED;
     Blk128BwdArgs a;
     a.qkv = qkv; a.u = u; a.wqkv = wqkv; a.bqkv = bqkv; a.o = o; a.lse = lse; a.dx1b = dx1b; a.dx1 = dx1; a.x = x; a.gamma = gamma;
     a.wpT = wpT; a.wqkvT = wqkvT; a.dqkv = dqkv; a.dx = dx; a.dgamma = dgamma; a.dbeta = dbeta; a.det_base = det_base; a.det_acc = det_acc;
     a.Ts = Ts; a.nsamples = nsamples; a.mode = mode; a.len_l = len_l; a.accumulate = accumulate;
-    if (rc) return Ts <= 16 ? launch_blk128_bwd<1, 2, true>(a, s) : launch_blk128_bwd<2, 2, true>(a, s);
-    return Ts <= 16 ? launch_blk128_bwd<1, 2, false>(a, s) : launch_blk128_bwd<2, 2, false>(a, s);
+    if (rc) return Ts <= hsplan::kAttnTile ? launch_blk128_bwd<1, 2, true>(a, s) : launch_blk128_bwd<2, 2, true>(a, s);
+    return Ts <= hsplan::kAttnTile ? launch_blk128_bwd<1, 2, false>(a, s) : launch_blk128_bwd<2, 2, false>(a, s);
 }
 
 HS_UNIT_VARIANT_BITS(attn)

@@ -20,6 +20,7 @@
 // LDS: cls 0.25 + U/O image 34.8 + staging 99.3 + lse 4 + vectors 6 = 144.4 KB => one workgroup per CU, 4 waves per SIMD.
 #include "common.h"
 #include "kernels.h"
+#include "plan.h"
 #include <cstdlib>
 
 #ifndef HS_NT_C
@@ -745,40 +746,36 @@ int launch_blk256(const Blk256Args& a, hipStream_t s) {
 
 }  // namespace
 
-// Shape predicate (api.hip SC_ATTN_BLOCK256 is the A/B switch).  The kernel's 32-bit element offsets bound the launch size: a
-// larger launch answers false here and takes the layer-at-a-time kernels instead of failing in hs_attn_block256_fwd.
-bool hs_attn_block256_fusable(int d, int heads, int Ts, int nsamples) {
-    return d == DW && heads == HW && Ts >= 1 && Ts <= 32 && (int64_t)nsamples * Ts * 3 * DW < (1ll << 31);
-}
+// Which passes use these kernels: plan.h plan_block().  Its shape predicate also answers false for a launch beyond the kernels'
+// 32-bit element offsets, which then takes the layer-at-a-time kernels instead of being refused below.
+static_assert(hsplan::kAttn256D == DW && hsplan::kAttn256Heads == HW,
+              "plan.h attn256_fusable must select exactly the shape blk256_fwd / blk256_bwd are instantiated for");
 
-// dO + attention backward + du + LayerNorm-1 backward at D = 256 in one launch (blk256_bwd_kernel).  Shape predicate (api.hip
-// SC_ATTN_BLOCK256_BWD is the A/B switch); the same 32-bit offset bound as the forward.
-bool hs_attn_block256_bwd_fusable(int d, int heads, int Ts, int nsamples) { return hs_attn_block256_fusable(d, heads, Ts, nsamples); }
-
+// dO + attention backward + du + LayerNorm-1 backward at D = 256 in one launch (blk256_bwd_kernel)
 int hs_attn_block256_bwd(const hs_bf16* qkv, const float* lse, const hs_bf16* dx1b, const float* dx1, const float* x, const float* gamma,
                          const hs_bf16* wpT, const hs_bf16* wqkvT, hs_bf16* dqkv, float* dx, float* dgamma, float* dbeta,
                          const float* det_base, long long* det_acc, int Ts, int nsamples, int mode, int len_l, int accumulate,
                          hipStream_t s) {
     if (nsamples <= 0) return HS_OK;
-    if (Ts < 1 || Ts > 32) return HS_EUNSUPPORTED;
+    if (Ts < 1 || Ts > hsplan::kAttnMaxTs) return HS_EUNSUPPORTED;
     if ((int64_t)nsamples * Ts * 3 * DW >= (1ll << 31)) return HS_EUNSUPPORTED;      // 32-bit element offsets inside the kernel
     Blk256BwdArgs a;
     a.qkv = qkv; a.lse = lse; a.dx1b = dx1b; a.dx1 = dx1; a.x = x; a.gamma = gamma; a.wpT = wpT; a.wqkvT = wqkvT; a.dqkv = dqkv; a.dx = dx;
     a.dgamma = dgamma; a.dbeta = dbeta; a.det_base = det_base; a.det_acc = det_acc;
     a.Ts = Ts; a.nsamples = nsamples; a.mode = mode; a.len_l = len_l; a.accumulate = accumulate;
-    return Ts <= 16 ? launch_blk256_bwd<1, 2>(a, s) : launch_blk256_bwd<2, 2>(a, s);
+    return Ts <= hsplan::kAttnTile ? launch_blk256_bwd<1, 2>(a, s) : launch_blk256_bwd<2, 2>(a, s);
 }
 
 int hs_attn_block256_fwd(const float* x, const float* n1w, const float* n1b, const hs_bf16* wqkv, const float* bqkv, const hs_bf16* wp,
                          const float* pb, hs_bf16* u, hs_bf16* qkv, hs_bf16* o, float* lse, float* x1, const float* rowscale, int Ts,
                          int nsamples, int mode, int len_l, hipStream_t s) {
     if (nsamples <= 0) return HS_OK;
-    if (Ts < 1 || Ts > 32) return HS_EUNSUPPORTED;
+    if (Ts < 1 || Ts > hsplan::kAttnMaxTs) return HS_EUNSUPPORTED;
     if ((int64_t)nsamples * Ts * 3 * DW >= (1ll << 31)) return HS_EUNSUPPORTED;      // 32-bit element offsets inside the kernel
     Blk256Args a;
     a.x = x; a.n1w = n1w; a.n1b = n1b; a.wqkv = wqkv; a.bqkv = bqkv; a.wp = wp; a.pb = pb; a.u = u; a.qkv = qkv; a.o = o;
     a.lse = lse; a.x1 = x1; a.rowscale = rowscale; a.Ts = Ts; a.nsamples = nsamples; a.mode = mode; a.len_l = len_l;
-    return Ts <= 16 ? launch_blk256<1, 2>(a, s) : launch_blk256<2, 2>(a, s);
+    return Ts <= hsplan::kAttnTile ? launch_blk256<1, 2>(a, s) : launch_blk256<2, 2>(a, s);
 }
 
 HS_UNIT_VARIANT_BITS(attn_wide)

@@ -12,6 +12,7 @@
 // LDS staging tile, which is also how x / x1 / x2 move to and from HBM with 16-B accesses.
 #include "common.h"
 #include "kernels.h"
+#include "plan.h"
 #include <type_traits>
 #include <cstdlib>
 
@@ -2028,7 +2029,7 @@ int launch_fwd(const DecFwdArgs& a, hipStream_t s) {
                                   hipFuncAttributeMaxDynamicSharedMemorySize, L::FWD_TOTAL);
         attr_set = true;
     }
-    static int wgs = 0;                       // workgroups: 2 per CU walking the samples (HSIMAE_DEC_FWD_WGS overrides)
+    static int wgs = 0;                       // workgroups: 2 per CU walking the samples
     if (!wgs) wgs = 512;
     hipLaunchKernelGGL((dec_block_fwd_kernel<MT>), dim3(a.nsamples < wgs ? a.nsamples : wgs), dim3(256), L::FWD_TOTAL, s, a);
     return (int)hipGetLastError();
@@ -2078,13 +2079,12 @@ int launch_bwd(const DecBwdMlpArgs& a, const DecBwdAttnArgs& b, hipStream_t s) {
     return (int)hipGetLastError();
 }
 
-bool hs_dec_fused_supported(int d, int heads, int hidden, int Ts) {
-    // the backward kernels keep 5-6 bf16 images + an fp32 tile of the sample in LDS: up to 7 m-tiles (112 tokens).
-    // Every kernel of this file is compiled for HPD = 192-row hidden images (w1 / w3 / w2 / w2T packed to rup(hidden, 32) = 192
-    // rows, 6 k-steps): a narrower hidden width would be read with the wrong k-step layout and past the caller's images
-    // (ADVICE r03), so it is refused here — the layer-at-a-time schedule covers it.
-    return d == D && heads == 8 && (hidden + 31) / 32 * 32 == HPD && hidden % 4 == 0 && Ts <= 112 && Ts >= 16;
-}
+// The backward kernels keep 5-6 bf16 images + an fp32 tile of the sample in LDS: up to 7 m-tiles (112 tokens).  Every kernel of
+// this file is compiled for HPD = 192-row hidden images (w1 / w3 / w2 / w2T packed to rup(hidden, 32) = 192 rows, 6 k-steps): a
+// narrower hidden width would be read with the wrong k-step layout and past the caller's images, so plan.h
+// dec_fusable refuses it — the layer-at-a-time schedule covers it.
+static_assert(hsplan::kDecD == D && hsplan::kDecHeads * HD == D && hsplan::kDecHeads * 64 == NT_ && hsplan::kDecHp == HPD &&
+              hsplan::kDecMaxTs == 7 * 16, "plan.h dec_fusable must select exactly the shape these kernels are compiled for");
 
 int hs_dec_block_bwd(const float* x, const float* x1, const float* dy, float* dx1_tmp, float* dx, const hs_bf16* o,
                      const float* lse, int nsamples, int Ts, const DecBlockPtrs& bp, const DecBlockGrads& g, hipStream_t s,

@@ -9,6 +9,7 @@
 // 64-column chunk.  Weight fragments are prefetched one chunk ahead.
 #include "common.h"
 #include "kernels.h"
+#include "plan.h"
 #include <cstdlib>
 
 // Per-phase cycle accounting for scripts/phase_timing.py (compiled only with -DHS_PHASE_TIMING; never in the shipped library)
@@ -798,13 +799,8 @@ __global__ __launch_bounds__(NTH, (MG<D, HPE>::WPC)) void enc_mlp_bwd_kernel(Enc
 
 }  // namespace
 
-static int hp_of(int hidden) { return (hidden + 31) / 32 * 32; }
-
-bool hs_enc_mlp_fused_supported(int d, int hidden) {
-    // the kernels are templates on <D, HP>: Base (128, 344 -> 352), Large (256, 684 -> 704) and the decoder width
-    // (64, 172 -> 192) are instantiated
-    return (d == 128 && hp_of(hidden) == 352) || (d == 256 && hp_of(hidden) == 704) || (d == 64 && hp_of(hidden) == 192);
-}
+// the kernels are templates on <D, HP>: Base (128, 344 -> 352), Large (256, 684 -> 704) and the decoder width (64, 172 -> 192)
+// are instantiated by launch_fwd / launch_bwd below; every launch goes through set_attrs<D, HP>
 
 static EncMlpW mkw(const EncMlpPtrs& b) {
     EncMlpW w;
@@ -815,6 +811,7 @@ static EncMlpW mkw(const EncMlpPtrs& b) {
 
 template <int D, int HP>
 static void set_attrs() {
+    static_assert(hsplan::mlp_shape(D, HP), "plan.h mlp_fusable must select every <D, HP> launched here");
     static bool done = false;
     if (done) return;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(enc_mlp_fwd_kernel<D, HP>), hipFuncAttributeMaxDynamicSharedMemorySize, MG<D, HP>::LDS_FWD);
@@ -827,7 +824,7 @@ template <int D, int HP>
 static int fwd_grid(int M) {
     const int panels = (M + MG<D, HP>::R - 1) / MG<D, HP>::R;
     if (!MG<D, HP>::PERSIST) return panels;
-    static int slots = 0;                     // resident workgroups: WPCF per CU (HSIMAE_MLP_FWD_WGS overrides)
+    static int slots = 0;                     // resident workgroups: WPCF per CU
     if (!slots) slots = 256 * MG<D, HP>::WPCF;
     return panels < slots ? panels : slots;
 }

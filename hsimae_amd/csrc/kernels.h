@@ -27,7 +27,6 @@ int hs_gemm_tiled(const GemmParams& p, int akind, int epi, int bm, int kc, hipSt
 int hs_pack(const PackDesc* descs_dev, int ndesc, int max_elems, hipStream_t s);
 int hs_attn_fwd(const AttnParams& p, hipStream_t s);
 int hs_attn_bwd(const AttnParams& p, hipStream_t s);
-bool hs_attn_proj_fusable(const AttnParams& p);      // shape predicate of the fused attention half (d = 128, 8 heads of 16, Ts <= 32, unpadded rows)
 int hs_wgrad(const WgradParams& p, hipStream_t s);
 int hs_ln_bwd(const LnBwdParams& p, hipStream_t s);
 int hs_ln_fwd(const float* x, const float* gamma, const float* beta, float* out, int M, int d, hipStream_t s, int ldx = 0, int ldo = 0);
@@ -62,7 +61,6 @@ struct DecBlockGrads {
     float *n1w, *n1b, *qw, *qb, *kw, *kb, *vw, *vb, *pw, *pb, *n2w, *n2b, *w1w, *w1b, *w2w, *w2b, *w3w, *w3b;
     HsDet det;                    // deterministic commits (common.h); {nullptr, nullptr} = fp32 atomics
 };
-bool hs_dec_fused_supported(int d, int heads, int hidden, int Ts);
 int hs_dec_block_fwd(const float* x, float* x1, float* x2, hs_bf16* o, float* lse, int nsamples, int Ts,
                      const DecBlockPtrs& bp, hipStream_t s);
 int hs_dec_attn_fwd(const float* x, float* x1, hs_bf16* o, float* lse, int nsamples, int Ts, const DecBlockPtrs& bp, hipStream_t s);
@@ -80,8 +78,6 @@ struct EncMlpPtrs {
     const bf16_t *w1, *w3, *w2, *w2T, *w13T;
     int h;
 };
-bool hs_attn_block_fusable(int d, int heads, int Ts);
-bool hs_attn_block_bwd_fusable(int d, int heads, int Ts);
 int hs_attn_block_bwd(const hs_bf16* qkv, const hs_bf16* u, const hs_bf16* wqkv, const float* bqkv, const hs_bf16* o, const float* lse,
                       const hs_bf16* dx1b, const float* dx1, const float* x, const float* gamma, const hs_bf16* wpT, const hs_bf16* wqkvT,
                       hs_bf16* dqkv, float* dx, float* dgamma, float* dbeta, const float* det_base, long long* det_acc, int Ts,
@@ -89,18 +85,15 @@ int hs_attn_block_bwd(const hs_bf16* qkv, const hs_bf16* u, const hs_bf16* wqkv,
 int hs_attn_block_fwd(const float* x, const float* n1w, const float* n1b, const hs_bf16* wqkv, const float* bqkv, const hs_bf16* wp,
                       const float* pb, hs_bf16* u, hs_bf16* qkv, hs_bf16* o, float* lse, float* x1, const float* rowscale, int Ts,
                       int nsamples, int mode, int len_l, hipStream_t s);
-// the same half at D = 256 (16 heads of 16, <= 32 tokens): attn_wide.hip.  HSIMAE_FUSED_ATTN_BLOCK256=0 disables (api.hip SC_*).
-bool hs_attn_block256_fusable(int d, int heads, int Ts, int nsamples);
+// the same half at D = 256 (16 heads of 16, <= 32 tokens): attn_wide.hip
 int hs_attn_block256_fwd(const float* x, const float* n1w, const float* n1b, const hs_bf16* wqkv, const float* bqkv, const hs_bf16* wp,
                          const float* pb, hs_bf16* u, hs_bf16* qkv, hs_bf16* o, float* lse, float* x1, const float* rowscale, int Ts,
                          int nsamples, int mode, int len_l, hipStream_t s);
-// ... and its backward (dO + attention backward + du + LayerNorm-1 backward, round 5).  HSIMAE_FUSED_ATTN_BLOCK256_BWD=0 disables.
-bool hs_attn_block256_bwd_fusable(int d, int heads, int Ts, int nsamples);
+// ... and its backward (dO + attention backward + du + LayerNorm-1 backward, round 5)
 int hs_attn_block256_bwd(const hs_bf16* qkv, const float* lse, const hs_bf16* dx1b, const float* dx1, const float* x, const float* gamma,
                          const hs_bf16* wpT, const hs_bf16* wqkvT, hs_bf16* dqkv, float* dx, float* dgamma, float* dbeta,
                          const float* det_base, long long* det_acc, int Ts, int nsamples, int mode, int len_l, int accumulate,
                          hipStream_t s);
-bool hs_enc_mlp_fused_supported(int d, int hidden);
 int hs_enc_mlp_fwd(const float* x1, const float* res2, float* x2, int M, int d, const EncMlpPtrs& b, hipStream_t s,
                    const float* rowscale = nullptr);
 int hs_enc_mlp_bwd(const float* x1, const float* dy, float* dx1, hs_bf16* u2, hs_bf16* dh13, hs_bf16* g, hs_bf16* dyb,

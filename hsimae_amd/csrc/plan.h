@@ -298,6 +298,118 @@ inline int wgrad_msplit(int tiles, int64_t M, int concurrent = 1) {
     return std::max(1, std::min(ms, chunks));
 }
 
+// ------------------------------------------------------------------ the schedule of a pass, decided ONCE, by its forward
+// Every choice between two kernel generations that changes what the forward leaves in the workspace for the backward — fused
+// or layer-at-a-time halves (which intermediates exist), q|k|v saved or recomputed, fp8 GEMMs or fused bf16 kernels — is read from
+// the environment exactly once per pass: by the forward entry point (api.hip sched_from_env), which records the word for its
+// workspace arena.  The backward entry points look the record up and follow it (HSIMAE_ENOFORWARD if there is none); they never
+// read the environment, so a switch flipped between a forward and its backward has no effect on that pass.  What a word means
+// for a stack of blocks is worked out in ONE place, plan_block() below, and both directions switch on its result (rounds 1-4
+// re-derived each decision where it was needed: a forward that skipped the q|k|v store followed by a backward that decided not to
+// recompute read an unwritten buffer and returned HSIMAE_OK — VERDICT r04 item 5).  Only this list names the switches.
+enum : uint32_t {
+    SC_FUSED_DEC = 1u << 0,        // HSIMAE_FUSED_DEC=0 clears: layer-at-a-time decoder
+    SC_DEC_SPLIT = 1u << 1,        // HSIMAE_DEC_SPLIT=0 clears: one-kernel decoder block forward
+    SC_FP8_UNFUSED = 1u << 2,      // HSIMAE_FP8_UNFUSED=1 sets: every linear of an fp8 encoder block on the MX GEMMs, no fused kernel
+    SC_FUSED_MLP = 1u << 3,        // HSIMAE_FUSED_MLP=0 clears: layer-at-a-time MLP half of the encoder blocks
+    SC_ATTN_BLOCK = 1u << 4,       // HSIMAE_FUSED_ATTN_BLOCK=0 clears: blk128_fwd
+    SC_ATTN_BLOCK256 = 1u << 5,    // HSIMAE_FUSED_ATTN_BLOCK256=0 clears: blk256_fwd
+    SC_ATTN_BLOCK_BWD = 1u << 6,   // HSIMAE_FUSED_ATTN_BLOCK_BWD=0 clears: blk128_bwd
+    SC_PROJ_BWD = 1u << 7,         // HSIMAE_FUSED_PROJ_BWD=0 clears: the projection's data gradient as its own GEMM
+    SC_LNBWD = 1u << 8,            // HSIMAE_FUSED_LNBWD=0 clears: du store + separate ln_bwd pass
+    SC_LNBWD_512 = 1u << 9,        // HSIMAE_FUSED_LNBWD_512=0 clears it at d = 512 only
+    SC_RECOMPUTE = 1u << 10,       // HSIMAE_ATTN_BWD_RECOMPUTE=0 clears: the forward saves q|k|v
+    SC_WGRAD_SLAB = 1u << 11,      // HSIMAE_WGRAD_SLAB=0 clears: float atomics in the 256 x 256-tile weight-gradient launches
+    SC_DEC_SLAB = 1u << 12,        // HSIMAE_DEC_SLAB=0 clears: float atomics in the fused decoder backward
+    SC_PLANAR = 1u << 13,          // HSIMAE_WGRAD_PLANAR=0 clears: g / dh1|dh3 of the fused MLP backward row-major instead of 64-column planes
+    SC_ATTN_BLOCK256_BWD = 1u << 14,   // HSIMAE_FUSED_ATTN_BLOCK256_BWD=0 clears: blk256_bwd (three launches instead)
+};
+
+// Shapes the fused kernels are instantiated for.  Each kernel unit ties its template constants to these with static_assert and
+// keeps its own refusals at launch; whether a pass USES a kernel is plan_block()'s / plan_dec()'s answer.
+constexpr int kAttnTile = 16, kAttnMaxTs = 2 * kAttnTile;   // blk128_* / blk256_*: one or two 16-token tiles per sample
+constexpr int kAttn128D = 128, kAttn128Heads = 8;           // attn.hip blk128_fwd / blk128_bwd: 8 heads of 16, unpadded rows
+constexpr int kAttn256D = 256, kAttn256Heads = 16;          // attn_wide.hip blk256_fwd / blk256_bwd: 16 waves = 16 heads of 16
+constexpr bool mlp_shape(int d, int hp) {                   // fused_enc.hip enc_mlp_*_kernel<D, HP>: (d, rup(hidden, 32))
+    return (d == 128 && hp == 352) || (d == 256 && hp == 704) || (d == 64 && hp == 192);
+}
+constexpr int kDecD = 64, kDecHeads = 8, kDecHp = 192, kDecMinTs = 16, kDecMaxTs = 112;    // fused_dec.hip: up to 7 m-tiles of a sample in LDS
+inline bool attn128_fusable(int d, int heads, int Ts) { return d == kAttn128D && heads == kAttn128Heads && Ts <= kAttnMaxTs; }
+// (the kernels index q|k|v with 32-bit element offsets: a larger launch takes the layer-at-a-time kernels)
+inline bool attn256_fusable(int d, int heads, int Ts, int nsamples) {
+    return d == kAttn256D && heads == kAttn256Heads && Ts >= 1 && Ts <= kAttnMaxTs && (int64_t)nsamples * Ts * 3 * kAttn256D < (1ll << 31);
+}
+inline bool mlp_fusable(int d, int hidden) { return mlp_shape(d, rup(hidden, 32)); }
+inline bool dec_fusable(int d, int heads, int hidden, int Ts) {
+    return d == kDecD && heads == kDecHeads && rup(hidden, 32) == kDecHp && hidden % 4 == 0 && Ts <= kDecMaxTs && Ts >= kDecMinTs;
+}
+
+// precision = FP8 puts the MX e4m3 images on the encoder linears that run as stand-alone GEMMs, where it pays: K >= 512.  At
+// d = 256 the MX GEMMs are no faster than the bf16 ones (Large: 37.8 vs 37.2 ms per step, r03_k) and at d = 128 every linear sits
+// inside a fused bf16 kernel; SC_FP8_UNFUSED forces them at every width (tests of the generic path).  The decoder's blocks never are.
+inline bool enc_linears_fp8(int model_prec, int D, uint32_t sc) {
+    return model_prec == HSIMAE_PREC_FP8 && (D >= 512 || (sc & SC_FP8_UNFUSED));
+}
+
+enum AttnFwd { ATTN_FWD_LAYERED, ATTN_FWD_BLK128, ATTN_FWD_BLK256 };
+enum AttnBwd { ATTN_BWD_LAYERED, ATTN_BWD_BLK128, ATTN_BWD_BLK128_RECOMPUTE, ATTN_BWD_BLK256 };
+enum LnBwd { LN_SEPARATE, LN_GEMM_EPILOGUE, LN_IN_KERNEL };     // du store + ln_bwd pass / epilogue of the du GEMM / inside a fused kernel
+struct BlockPlan {
+    int d, dp, heads, h, hp, Ts, nsamples; int64_t M;      // d: true width, dp / hp: storage widths (Geo::Dp), M rows of Ts-token samples
+    AttnFwd attn_fwd;
+    bool save_qkv;           // the forward stores q|k|v (false: attn_bwd recomputes them from u)
+    bool mlp_fused;          // MLP half as enc_mlp_fwd / enc_mlp_bwd (both directions)
+    bool gemm_fp8;           // the stand-alone linears on MX e4m3 images
+    AttnBwd attn_bwd;
+    bool proj_bwd_fused;     // the projection's data gradient inside the attention backward kernel: derived, attn_bwd != LAYERED
+    LnBwd ln1_bwd, ln2_bwd;
+    bool planar; int plane_rows;     // g / dh1|dh3 as 64-column planes of plane_rows rows (hsimae_wgrad_task), 0 = row-major
+    bool wgrad_slab;         // the 256 x 256-tile weight-gradient launches commit through the stream's slab
+};
+
+// fp8: enc_linears_fp8 for encoder stacks, false for the decoder.  Where a fused bf16 kernel covers the shape it is kept: it beats
+// the layer-at-a-time fp8 form (round 2: Base 26.9 vs 19.4 ms, Large 44.1 vs 39.5 ms); SC_FP8_UNFUSED restores that all-fp8 schedule.
+inline BlockPlan plan_block(int d, int heads, int hidden, int Ts, int nsamples, int64_t M, bool fp8, uint32_t sc) {
+    BlockPlan p;
+    p.d = d; p.dp = rup(d, 32); p.heads = heads; p.h = hidden; p.hp = rup(hidden, 32); p.Ts = Ts; p.nsamples = nsamples; p.M = M;
+    auto on = [sc](uint32_t bits) { return (sc & bits) == bits; };
+    const bool unpadded = p.dp == d;                     // the fused kernels have no pad columns
+    const bool all_fp8 = fp8 && on(SC_FP8_UNFUSED);
+    const bool a128 = !all_fp8 && attn128_fusable(d, heads, Ts), a256 = !fp8 && unpadded && attn256_fusable(d, heads, Ts, nsamples);
+    p.gemm_fp8 = fp8;
+    p.mlp_fused = !all_fp8 && on(SC_FUSED_MLP) && mlp_fusable(d, hidden);
+    p.attn_fwd = (a128 && on(SC_ATTN_BLOCK)) ? ATTN_FWD_BLK128 : (a256 && on(SC_ATTN_BLOCK256)) ? ATTN_FWD_BLK256 : ATTN_FWD_LAYERED;
+    // dO, the attention backward, du and the LayerNorm-1 backward as ONE persistent launch; its dx1 operand is the fused MLP
+    // backward's bf16 copy.  With q|k|v recomputed from u when the forward ran blk128_fwd, which then does not store them.
+    const bool b128 = a128 && p.mlp_fused && on(SC_ATTN_BLOCK_BWD | SC_PROJ_BWD | SC_LNBWD);
+    const bool b256 = a256 && on(SC_ATTN_BLOCK256_BWD | SC_PROJ_BWD | SC_LNBWD);          // from the saved q|k|v
+    p.attn_bwd = !b128 ? (b256 ? ATTN_BWD_BLK256 : ATTN_BWD_LAYERED)
+                       : (p.attn_fwd == ATTN_FWD_BLK128 && on(SC_RECOMPUTE)) ? ATTN_BWD_BLK128_RECOMPUTE : ATTN_BWD_BLK128;
+    p.save_qkv = p.attn_bwd != ATTN_BWD_BLK128_RECOMPUTE;
+    p.proj_bwd_fused = p.attn_bwd != ATTN_BWD_LAYERED;
+    // d = 256 / 512 (rows of exactly two / four 128-column chunks): LayerNorm backward as the epilogue of the k-outer GEMM
+    // (gemm.hip epilogue_ln_ko; d = 512 on 32-row panels, fp8 only: Huge fp8 49.9 -> 48.9 ms per step, but bf16 60.2 -> 61.5);
+    // at d = 128 LayerNorm-1's is the epilogue of the row-panel GEMM (du never goes to HBM)
+    const bool wide_ln = on(SC_LNBWD) && unpadded && (d == 256 || (d == 512 && fp8 && on(SC_LNBWD_512)));
+    p.ln1_bwd = p.proj_bwd_fused ? LN_IN_KERNEL : ((on(SC_LNBWD) && d == 128 && !all_fp8) || wide_ln) ? LN_GEMM_EPILOGUE : LN_SEPARATE;
+    p.ln2_bwd = p.mlp_fused ? LN_IN_KERNEL : wide_ln ? LN_GEMM_EPILOGUE : LN_SEPARATE;
+    // planes need whole 32-row DMA chunks and 32-bit byte offsets
+    p.planar = p.mlp_fused && on(SC_PLANAR) && M % 32 == 0 && (M + kPlanePadRows) * 2 * (int64_t)(rup(p.hp, 64) + 256) * 2 < (1ll << 32);
+    p.plane_rows = p.planar ? (int)M + HS_PLANE_PAD_ROWS : 0;
+    p.wgrad_slab = on(SC_WGRAD_SLAB);
+    return p;
+}
+
+// The decoder stack: fused Block kernels (fused_dec.hip), else layer at a time (plan_block of its own shape).  split: the fused
+// forward as the attention half (q / k / v in registers, 16 waves per CU) + the row-panel MLP half enc_mlp_fwd_kernel<64, 192>
+// (default since round 3) instead of the one-kernel form; slab: the fused backward commits its in-register weight gradients
+// through the slab + one reduce launch instead of float atomics.
+struct DecPlan { bool fused, split, slab; };
+inline DecPlan plan_dec(int Dd, int heads, int hidden, int TL, uint32_t sc) {
+    return DecPlan{(sc & SC_FUSED_DEC) && dec_fusable(Dd, heads, hidden, TL), (sc & SC_DEC_SPLIT) && mlp_fusable(Dd, hidden),
+                   (sc & SC_DEC_SLAB) != 0};
+}
+
 // ------------------------------------------------------------------ bodies of the host-only C entry points
 inline int param_layout(const hsimae_config* cfg, int64_t* offsets, int64_t* sizes, int max_entries) {
     Geo g; int e = make_geo(cfg, g); if (e) return e;

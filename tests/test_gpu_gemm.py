@@ -589,8 +589,8 @@ def test_ln_bwd_deterministic_commits(prec, N, K):
 
 
 def test_ln_bwd_bf16_n512():
-    """The bf16 N = 512 form gemm_kernel<0, 6, 256, 32, 0, 4>: no caller in the library reaches it (wide_ln_fused uses d = 512
-    only in fp8), run on its own so that a fault in it is attributed to it."""
+    """The bf16 N = 512 form gemm_kernel<0, 6, 256, 32, 0, 4>: no caller in the library reaches it (plan_block chooses the
+    LayerNorm-backward epilogue at d = 512 only in fp8), run on its own so that a fault in it is attributed to it."""
     kw, W, ldo = ln_bwd_inputs(BF16, 512, 1056, 97, seed=3)
     dx64, bnd, dg64, bg, db64, bb = ln_bwd_ref(kw, W, BF16)
     out, canary, dg, db, u, _ = run_ln_bwd(kw, ldo, u_out=True)
