@@ -21,5 +21,6 @@ from .pretrain import mask_pretraining  # noqa: F401
 from .finetune import DualViT, HSIViT  # noqa: F401
 from .finetune_train import dual_branch_finetuning, test_model, test_model_scene  # noqa: F401
 from .gwpca import GWPCA, apply_gwpca  # noqa: F401
+from .classify import ClassLoss, ScoreMeter  # noqa: F401
 
 __version__ = "0.1.0"

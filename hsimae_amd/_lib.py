@@ -128,6 +128,11 @@ class GwpcaParams(C.Structure):
                 ("minmax", vp), ("mean", vp), ("lambda_", vp), ("proj", vp), ("group_off", vp)]
 
 
+class ClsParams(C.Structure):
+    _fields_ = [("logits", vp), ("ld", i32), ("targets", vp), ("N", i32), ("C", i32), ("ignore_index", i64), ("first", i32),
+                ("loss", vp), ("n_valid", vp), ("dlogits", vp), ("ldd", i32), ("pred", vp), ("bad", vp), ("workspace", vp)]
+
+
 class BuildInfo(C.Structure):
     _fields_ = [("abi_version", i32), ("variant_bits", C.c_uint32), ("kernel_source_hash", C.c_uint64), ("flags_hash", C.c_uint64),
                 ("default_flags", i32), ("reserved", i32)]
@@ -182,6 +187,12 @@ SYMBOLS = {
     "hsimae_gwpca_workspace_bytes": (i64, [C.POINTER(GwpcaParams)]),
     "hsimae_gwpca_fit": (C.c_int, [C.POINTER(GwpcaParams), vp, vp]),
     "hsimae_gwpca_apply": (C.c_int, [C.POINTER(GwpcaParams), vp, i32, vp]),
+    "hsimae_cls_workspace_bytes": (i64, [i32]),
+    "hsimae_cls_loss": (C.c_int, [C.POINTER(ClsParams), vp]),
+    "hsimae_cls_grad_scale": (C.c_int, [vp, vp, vp, i64, vp]),
+    "hsimae_confusion": (C.c_int, [vp, vp, i64, i32, vp, vp, vp]),
+    "hsimae_confusion_map": (C.c_int, [vp, vp, vp, vp, i64, i32, vp, vp, vp]),
+    "hsimae_scores": (C.c_int, [vp, i32, vp, vp]),
     "hsimae_encode": (C.c_int, [C.POINTER(Config), C.POINTER(IO), vp]),
     "hsimae_encode_backward": (C.c_int, [C.POINTER(Config), C.POINTER(IO), vp, vp, BUCKET_CB, vp, vp]),
     "hsimae_agg_pool": (C.c_int, [vp, vp, i32, i32, i32, i32, vp]),

@@ -420,6 +420,7 @@ extern "C" unsigned hs_variant_bits_fused_enc();
 extern "C" unsigned hs_variant_bits_loader();
 extern "C" unsigned hs_variant_bits_scene();
 extern "C" unsigned hs_variant_bits_gwpca();
+extern "C" unsigned hs_variant_bits_cls();
 #ifndef HS_KERNEL_SOURCE_HASH
 #define HS_KERNEL_SOURCE_HASH 0ULL
 #endif
@@ -437,7 +438,7 @@ int hsimae_version(void) { return HSIMAE_VERSION; }
 int hsimae_build_info(hsimae_build_info_t* out) {
     if (!out) return HSIMAE_ENULL;
     out->abi_version = HSIMAE_VERSION;
-    out->variant_bits = hs_variant_bits() | hs_variant_bits_gemm() | hs_variant_bits_attn() | hs_variant_bits_attn_wide() | hs_variant_bits_wgrad() | hs_variant_bits_elem() | hs_variant_bits_pack() | hs_variant_bits_fused_dec() | hs_variant_bits_fused_enc() | hs_variant_bits_loader() | hs_variant_bits_scene() | hs_variant_bits_gwpca();
+    out->variant_bits = hs_variant_bits() | hs_variant_bits_gemm() | hs_variant_bits_attn() | hs_variant_bits_attn_wide() | hs_variant_bits_wgrad() | hs_variant_bits_elem() | hs_variant_bits_pack() | hs_variant_bits_fused_dec() | hs_variant_bits_fused_enc() | hs_variant_bits_loader() | hs_variant_bits_scene() | hs_variant_bits_gwpca() | hs_variant_bits_cls();
     out->kernel_source_hash = HS_KERNEL_SOURCE_HASH;
     out->flags_hash = HS_BUILD_FLAGS_HASH;
     out->default_flags = HS_BUILD_DEFAULT_FLAGS;
@@ -954,6 +955,19 @@ int hsimae_gwpca_fit(const hsimae_gwpca_params* p, void* workspace, void* stream
 int hsimae_gwpca_apply(const hsimae_gwpca_params* p, void* out, int32_t out_f64, void* stream) {
     return p ? hs_gwpca_apply(*p, out, out_f64, S(stream)) : HSIMAE_ENULL;
 }
+int64_t hsimae_cls_workspace_bytes(int32_t N) { return hs_cls_workspace_bytes(N); }
+int hsimae_cls_loss(const hsimae_cls_params* p, void* stream) { return p ? hs_cls_loss(*p, S(stream)) : HSIMAE_ENULL; }
+int hsimae_cls_grad_scale(const float* src, const float* scale, float* dst, int64_t n, void* stream) {
+    return hs_cls_grad_scale(src, scale, dst, n, S(stream));
+}
+int hsimae_confusion(const int64_t* gt, const int64_t* pred, int64_t n, int32_t C, int64_t* cm, int32_t* bad, void* stream) {
+    return hs_confusion(gt, pred, n, C, cm, bad, S(stream));
+}
+int hsimae_confusion_map(const int64_t* gt_map, const int64_t* mask_map, const int64_t* pred_map, int64_t* masked, int64_t n, int32_t C,
+                         int64_t* cm, int32_t* bad, void* stream) {
+    return hs_confusion_map(gt_map, mask_map, pred_map, masked, n, C, cm, bad, S(stream));
+}
+int hsimae_scores(const int64_t* cm, int32_t C, double* out, void* stream) { return hs_scores(cm, C, out, S(stream)); }
 int hsimae_ln_bwd(const hsimae_lnbwd_params* p, void* stream) { return p ? hs_ln_bwd(*p, S(stream)) : HSIMAE_ENULL; }
 int hsimae_ln_fwd(const float* x, const float* gamma, const float* beta, float* out, int32_t M, int32_t d, void* stream) {
     return (x && gamma && beta && out) ? hs_ln_fwd(x, gamma, beta, out, M, d, S(stream)) : HSIMAE_ENULL;

@@ -42,6 +42,13 @@ int hs_class_argmax(const SceneParams& p, const float* logits, int ld, int num_c
 int64_t hs_gwpca_workspace_bytes(const hsimae_gwpca_params& p);
 int hs_gwpca_fit(const hsimae_gwpca_params& p, void* workspace, hipStream_t s);
 int hs_gwpca_apply(const hsimae_gwpca_params& p, void* out, int out_f64, hipStream_t s);
+int64_t hs_cls_workspace_bytes(int N);
+int hs_cls_loss(const hsimae_cls_params& p, hipStream_t s);
+int hs_cls_grad_scale(const float* src, const float* scale, float* dst, int64_t n, hipStream_t s);
+int hs_confusion(const int64_t* gt, const int64_t* pred, int64_t n, int C, int64_t* cm, int32_t* bad, hipStream_t s);
+int hs_confusion_map(const int64_t* gt_map, const int64_t* mask_map, const int64_t* pred_map, int64_t* masked, int64_t n, int C,
+                     int64_t* cm, int32_t* bad, hipStream_t s);
+int hs_scores(const int64_t* cm, int C, double* out, hipStream_t s);
 int hs_agg_pool(const float* latent, float* pooled, int N, int T, int L, int D, hipStream_t s);
 int hs_head_bwd(const float* g, const float* pooled, const float* w, float* gw, float* gb, float* dlat, int N, int C, int T, int L,
                 int D, hipStream_t s);

@@ -136,7 +136,7 @@ class DualViT(HSIMAE):
                 hi = mid - 1
         return lo
 
-    def predict_scene(self, scene, pixels=None, batch_size=8192, return_logits=False):
+    def predict_scene(self, scene, pixels=None, batch_size=8192, return_logits=False, on_device=False):
         """Per-pixel classification map of a whole scene (what `test_model` computes from `data_cubes`, :268-283), from the
         scene itself: `scene` [H, W, C] fp32 / fp64 (numpy or tensor; the `HSI_data` of get_data_set_dual after GWPCA / norm)
         is uploaded once; per chunk of pixels, on the current stream: the symmetric-padded 9 x 9 windows (hsimae_scene_windows),
@@ -145,7 +145,8 @@ class DualViT(HSIMAE):
         Evaluates as in eval mode (no DropPath), without autograd.  `pixels`: row-major pixel indices r * W + c to classify
         (default: all); the map is 0 elsewhere.  `batch_size` caps the pixels per chunk; the chunk is also kept small enough
         for the encoder's workspace to fit SCENE_WORKSPACE_BUDGET bytes.
-        -> int64 [H, W] map (CPU), and with return_logits=True also fp32 [n, num_class] logits (CPU) in pixel order."""
+        -> int64 [H, W] map (CPU), and with return_logits=True also fp32 [n, num_class] logits (CPU) in pixel order.
+        on_device=True: both stay on the model's device and nothing waits for the host."""
         if isinstance(scene, torch.Tensor):
             s = scene
         else:
@@ -202,9 +203,9 @@ class DualViT(HSIMAE):
                                                    labels.data_ptr(), stream), "hsimae_class_argmax")
                 if logits_all is not None:
                     logits_all[k0:k0 + n].copy_(logits)
-            out = labels.view(H, W).cpu()
+            out = labels.view(H, W) if on_device else labels.view(H, W).cpu()
         if return_logits:
-            return out, logits_all.cpu()
+            return out, (logits_all if on_device else logits_all.cpu())
         return out
 
     # ------------------------------------------------------------------ stochastic depth (Models.py:235-263, 687-731)

@@ -5,20 +5,26 @@ parts: same signature, same order of operations, hyper-parameters and RNG consum
   data       : labeled / unlabeled / validation cubes resident in HBM (`HSIdataset` below, the reference's :26-63 with the
                same two python-`random` flip draws per training sample), batched by hsimae_amd.data.DeviceLoader
   step       : loss = lamda * loss_rec + CrossEntropy(ignore_index=0)(class_pred, y)             (:150-160)
+               the cross-entropy, its gradient and the predictions are one launch pair (hsimae_amd.ClassLoss); the losses of
+               an epoch are summed on the device and read once, at its end
   optimizer  : hsimae_amd.FusedAdamW (default betas), CosineLRScheduler stepped per EPOCH with
                t_initial=epochs, lr_min=lr/100, warmup_t=ceil(0.1 epochs), warmup_lr_init=lr/100  (:103-106, 236)
   metrics    : OA / AA / kappa on the labeled pixels (gt != 0, classes shifted by one)             (:171-178, 206-215)
+               counted and computed on the device (hsimae_amd.ScoreMeter); `scores` below is the same arithmetic on the host
 Not carried over: the matplotlib figure (:131-137, 222-233, 240-241).  The reference's defaults dim=144 / dec_dim=72 (widths that
 are not multiples of the kernels' 32-deep k-step) run zero-padded to 160 / 96 inside the library.
 """
 from __future__ import annotations
 
+import ctypes as C
 import os
 import random
 
 import numpy as np
 import torch
 
+from . import _lib
+from .classify import ClassLoss, ScoreMeter
 from .data import DeviceLoader
 from .finetune import DualViT, HSIViT
 from .optim import FusedAdamW
@@ -116,7 +122,8 @@ def dual_branch_finetuning(data_list, labeled_index, unlabeled_data, gt, save_di
     optimizer = FusedAdamW(model, lr=lr, weight_decay=wd)
     scheduler = CosineLRScheduler(optimizer, t_initial=epochs, lr_min=lr * 0.01, warmup_t=int(np.ceil(0.1 * epochs)),
                                   warmup_lr_init=lr * 0.01)
-    criterion = torch.nn.CrossEntropyLoss(reduction="mean", ignore_index=0)
+    criterion = ClassLoss(ignore_index=0)
+    meter = ScoreMeter(n_class, device)
 
     data_arr = [data_list[i] for i in labeled_index]
     tr_x, tr_y, va_x, va_y = spilt_dataset(data_arr, gt, training_ratio=0.5)
@@ -134,29 +141,31 @@ def dual_branch_finetuning(data_list, labeled_index, unlabeled_data, gt, save_di
         model.train()
         seed_everything(42 + epoch); labeled_iter = iter(train_dl)              # `stable(loader, 42 + epoch)` twice
         seed_everything(42 + epoch); unlabeled_iter = iter(unl_dl)
-        train_loss, preds, gts = 0.0, [], []
+        train_loss = torch.zeros((), dtype=torch.float64, device=device)         # summed on the device, read once per epoch
         for _ in range(len(train_dl)):
             x, y = next(labeled_iter)
             x_u = next(unlabeled_iter)
             loss_rec, _, _, outputs = model(x, x_u, mask_ratio=mask_ratio)
             loss = lamda * loss_rec + criterion(outputs, y)
-            preds.append(outputs.detach().argmax(1)); gts.append(y)
             optimizer.zero_grad()
             loss.backward()
             optimizer.step()
-            train_loss += loss.item()
-        epoch_loss_list.append(train_loss / len(train_dl))
+            train_loss += loss.detach()
 
         model.eval()
         with torch.no_grad():
             seed_everything(42 + epoch)
-            val_loss, preds, gts = 0.0, [], []
+            val_loss = torch.zeros((), dtype=torch.float64, device=device)
+            meter.reset()
             for x, y in val_dl:
                 outputs = model(x, mask_ratio=mask_ratio)
-                val_loss += criterion(outputs, y).item()
-                preds.append(outputs.argmax(1)); gts.append(y)
-        val_value = list(scores(torch.cat(gts).cpu().numpy(), torch.cat(preds).cpu().numpy()))
-        val_loss_list.append(val_loss / len(val_dl))
+                val_loss += criterion(outputs, y)
+                meter.update(y, criterion.last_pred)
+        val_value = list(meter.compute())
+        tr, va = torch.stack([train_loss, val_loss]).tolist()                   # the epoch's one wait for its losses
+        criterion.check()
+        epoch_loss_list.append(tr / len(train_dl))
+        val_loss_list.append(va / len(val_dl))
         scheduler.step(epoch)
 
     torch.save(model.state_dict(), os.path.join(save_dir, model_name))
@@ -178,15 +187,28 @@ def test_model(data_cubes, test_gt, gt, save_dir, model_name, depth=12, dim=96, 
     model.load_state_dict(model_dict)
     model.eval()
     dataset = HSIdataset(data_cubes, device=device)
-    preds = []
-    with torch.no_grad():
+    lib = _lib.load()
+    n_total = len(dataset)
+    pred = torch.zeros(n_total, dtype=torch.int64, device=device)
+    with torch.no_grad(), torch.cuda.device(device):
+        stream = torch.cuda.current_stream(device).cuda_stream
+        k0 = 0
         for x in DeviceLoader(dataset, batch_size=256, shuffle=False):
-            preds.append(model(x)[:, 1:].argmax(1))
-    pred = (torch.cat(preds).cpu().numpy() + 1).reshape(np.asarray(gt).shape)
-    pred_all = pred.copy()
-    pred[np.asarray(gt) == 0] = 0
-    oa, aa, kappa, ca = scores(np.asarray(test_gt).reshape(-1), pred.reshape(-1))
-    return oa, aa, kappa, ca, pred_all
+            logits = model(x)
+            # label = 1 + argmax(logits[:, 1:]) written in place into the device-resident map, as predict_scene does
+            sp = _lib.SceneParams(H=1, W=n_total, C=c, p0=k0, N=int(logits.shape[0]))
+            _lib.check(lib.hsimae_class_argmax(C.byref(sp), logits.data_ptr(), logits.stride(0), n_class, 1, pred.data_ptr(), stream),
+                       "hsimae_class_argmax")
+            k0 += int(logits.shape[0])
+    oa, aa, kappa, ca = _scene_scores(pred.view(np.asarray(gt).shape), test_gt, gt, n_class, device)
+    return oa, aa, kappa, ca, pred.cpu().numpy().reshape(np.asarray(gt).shape)
+
+
+def _scene_scores(pred, test_gt, gt, n_class, device):
+    """Model_Finetuning.py:285-290 on the device: the prediction map zeroed where `gt` is 0, counted against `test_gt`."""
+    meter = ScoreMeter(n_class, device)
+    meter.update_map(np.asarray(test_gt).reshape(-1), pred.reshape(-1), mask_map=np.asarray(gt).reshape(-1))
+    return meter.compute()
 
 
 def test_model_scene(scene, test_gt, gt, save_dir, model_name, depth=12, dim=96, s_depth=6, device="cuda:0", batch_size=8192):
@@ -206,8 +228,6 @@ def test_model_scene(scene, test_gt, gt, save_dir, model_name, depth=12, dim=96,
     model_dict.update({k: v for k, v in loaded.items() if k in model_dict})
     model.load_state_dict(model_dict)
     model.eval()
-    pred = model.predict_scene(scene, batch_size=batch_size).numpy().reshape(np.asarray(gt).shape)
-    pred_all = pred.copy()
-    pred[np.asarray(gt) == 0] = 0
-    oa, aa, kappa, ca = scores(np.asarray(test_gt).reshape(-1), pred.reshape(-1))
-    return oa, aa, kappa, ca, pred_all
+    pred = model.predict_scene(scene, batch_size=batch_size, on_device=True)
+    oa, aa, kappa, ca = _scene_scores(pred, test_gt, gt, n_class, device)
+    return oa, aa, kappa, ca, pred.cpu().numpy().reshape(np.asarray(gt).shape)

@@ -549,6 +549,61 @@ int64_t hsimae_gwpca_workspace_bytes(const hsimae_gwpca_params* p);
 int hsimae_gwpca_fit(const hsimae_gwpca_params* p, void* workspace, void* stream);
 int hsimae_gwpca_apply(const hsimae_gwpca_params* p, void* out, int32_t out_f64, void* stream);
 
+/* ------------------------------------------------------------------ classification loss, predictions and scores
+ * (Model_Finetuning.py:150-178, 206-215, 268-290).  These entry points were ADDED under HSIMAE_VERSION 108: no struct or
+ * function that 108 already had changes, so a caller written against 108 is unaffected, and a binder that wants them looks
+ * the symbols up.
+ *
+ * hsimae_cls_loss: torch.nn.functional.cross_entropy(logits, targets, reduction="mean", ignore_index=ignore_index).
+ *   logits fp32 [N][ld], of which only columns [0, C) are classes (the head's output is padded to 16 columns: the pad is never
+ *   read); targets int64 [N].  A row is valid when its target is not ignore_index and lies in [0, C); a target that is neither
+ *   sets *bad = 1 (never cleared here) and the row counts as ignored.  Written, each optional except `loss`:
+ *     loss     fp32 scalar: sum over valid rows of (log sum_c exp(z_c - max z) - (z_y - max z)) / n_valid; NaN when n_valid = 0
+ *              (also for N = 0), as torch;
+ *     n_valid  int64 scalar;
+ *     dlogits  fp32 [N][ldd]: (softmax(z_i) - onehot(y_i)) / n_valid in a valid row; exact zeros in an ignored row and in the
+ *              columns [C, ldd);
+ *     pred     int64 [N]: first + argmax(z_i[first:C]), for every row; ties go to the lowest index and NaN counts as the
+ *              maximum (torch.argmax, hsimae_class_argmax);
+ *     bad      int32 flag, see above.
+ *   The row maximum is subtracted before the exponentials.  Two launches on `stream`, no host wait; the losses of the rows are
+ *   summed in fp64 in a fixed order (no floating-point atomics): two runs are bit-identical.  `logits` is only read.
+ *   workspace: hsimae_cls_workspace_bytes(N) bytes of scratch, 8-byte aligned.
+ *   Refusals: params NULL -> HSIMAE_ENULL; N < 0, C < 2, ld < C, first outside [0, C), dlogits given with ldd < C -> HSIMAE_EDIMS;
+ *   C > 1024 -> HSIMAE_EUNSUPPORTED; loss or workspace NULL, logits or targets NULL with N > 0 -> HSIMAE_ENULL; a pointer not
+ *   aligned to its element (workspace: 8 bytes) -> HSIMAE_EALIGN.  hsimae_cls_workspace_bytes: N < 0 -> HSIMAE_EDIMS.
+ * hsimae_cls_grad_scale: dst[i] = src[i] * *scale for i < n, `scale` an fp32 scalar in DEVICE memory (the gradient that
+ *   arrives at the loss): the chain rule without a host read.  n < 0 -> HSIMAE_EDIMS, a NULL pointer with n > 0 -> HSIMAE_ENULL.
+ * hsimae_confusion: cm[gt_i * C + pred_i] += 1 for every i < n with gt_i != 0; gt, pred int64 [n], cm int64 [C][C] that the
+ *   caller zeroes once: counts accumulate over calls.  A gt_i or pred_i outside [0, C) (with gt_i != 0) sets *bad = 1 and is
+ *   skipped.  Integer atomics: the result does not depend on their order.
+ * hsimae_confusion_map: the same over a label map and a prediction map (hsimae_class_argmax's) of n pixels, with
+ *   masked[i] = mask_map[i] != 0 ? pred_map[i] : 0 written first and counted in place of pred_map[i] (Model_Finetuning.py:285);
+ *   mask_map NULL = gt_map.  `masked` may be pred_map itself.
+ *   Refusals of both: n < 0, C < 2 -> HSIMAE_EDIMS; C > 1024 -> HSIMAE_EUNSUPPORTED; cm or bad NULL, and with n > 0 gt, pred or
+ *   masked NULL -> HSIMAE_ENULL; a misaligned pointer -> HSIMAE_EALIGN.  n = 0 -> HSIMAE_OK, nothing written.
+ * hsimae_scores: out fp64 [3 + 2 (C - 1)] = OA, AA, kappa, recall of label 1 .. C - 1, then 1.0 / 0.0 for "label k occurs in
+ *   gt"; from cm as (Model_Finetuning.py:171-178) computes them from gt and pred: over the rows 1 .. C - 1 (gt != 0), n their
+ *   total, OA = trace / n, recall_k = cm[k][k] / rowsum_k (0 when the label does not occur), AA the mean recall of the labels
+ *   that occur, pe = sum_k rowsum_k colsum_k / n^2 over k >= 1 (a prediction of 0 is a miss with a column of its own),
+ *   kappa = (OA - pe) / (1 - pe), 0 when pe = 1.  n = 0 gives NaN, as the host arithmetic does.  One workgroup, fp64; the
+ *   count sums are integer and exact below 2^53.
+ *   Refusals: C < 2 -> HSIMAE_EDIMS; C > 1024 -> HSIMAE_EUNSUPPORTED; cm or out NULL -> HSIMAE_ENULL; misaligned -> HSIMAE_EALIGN. */
+typedef struct {
+    const float* logits; int32_t ld;
+    const int64_t* targets; int32_t N, C;
+    int64_t ignore_index; int32_t first;
+    float* loss; int64_t* n_valid; float* dlogits; int32_t ldd; int64_t* pred; int32_t* bad;
+    void* workspace;
+} hsimae_cls_params;
+int64_t hsimae_cls_workspace_bytes(int32_t N);
+int hsimae_cls_loss(const hsimae_cls_params* p, void* stream);
+int hsimae_cls_grad_scale(const float* src, const float* scale, float* dst, int64_t n, void* stream);
+int hsimae_confusion(const int64_t* gt, const int64_t* pred, int64_t n, int32_t C, int64_t* cm, int32_t* bad, void* stream);
+int hsimae_confusion_map(const int64_t* gt_map, const int64_t* mask_map, const int64_t* pred_map, int64_t* masked, int64_t n, int32_t C,
+                         int64_t* cm, int32_t* bad, void* stream);
+int hsimae_scores(const int64_t* cm, int32_t C, double* out, void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
