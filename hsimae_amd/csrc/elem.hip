@@ -591,7 +591,8 @@ int hs_assemble_bwd(const AssembleParams& p, hipStream_t s) {
 int hs_loss(const LossParams& p, hipStream_t s) {
     const int64_t M = (int64_t)p.N * p.T * 9;
     if (M <= 0) return HS_OK;
-    // per-sample form while two cube images + the mask row fit in LDS (T <= 24 with images, T <= 48 without)
+    // per-sample form while two cube images + the mask row fit in 150 KiB of LDS: T * (648 * k + 9) * 4 <= 153600 (k = 2 with images, else 1), which is
+    // T <= 29 with images, T <= 58 without; loss_kernel takes over at T = 30 / 59
     const size_t lds = ((size_t)p.T * 8 * 81 * (p.pred_img ? 2 : 1) + (size_t)p.T * 9) * 4;
     int grid;
     if (lds <= 150 * 1024) {
