@@ -19,7 +19,8 @@ from .data import HSIdataset4PT, DeviceLoader  # noqa: F401
 from .sched import CosineLRScheduler  # noqa: F401
 from .pretrain import mask_pretraining  # noqa: F401
 from .finetune import DualViT, HSIViT  # noqa: F401
-from .finetune_train import dual_branch_finetuning, test_model, test_model_scene  # noqa: F401
+from .finetune_train import dual_branch_finetuning, dual_branch_finetuning_scene, test_model, test_model_scene  # noqa: F401
+from .scene_data import SceneCubes, get_scene_set_dual, split_labeled, tile_origins, unlabeled_pixels  # noqa: F401
 from .gwpca import GWPCA, apply_gwpca  # noqa: F401
 from .classify import ClassLoss, ScoreMeter  # noqa: F401
 

@@ -123,6 +123,12 @@ class SceneParams(C.Structure):
                 ("out", vp), ("sn", i64), ("sb", i64), ("sh", i64), ("sw", i64)]
 
 
+class SceneBatchParams(C.Structure):
+    _fields_ = [("scene", vp), ("scene_f64", i32), ("H", i32), ("W", i32), ("C", i32),
+                ("items", vp), ("N", i32), ("n_items", i64), ("pixels", vp), ("labels", vp), ("flips", vp),
+                ("out", vp), ("sn", i64), ("sb", i64), ("sh", i64), ("sw", i64), ("y", vp), ("bad", vp)]
+
+
 class GwpcaParams(C.Structure):
     _fields_ = [("scene", vp), ("scene_f64", i32), ("H", i32), ("W", i32), ("C", i32), ("nc", i32), ("group", i32), ("whiten", i32),
                 ("minmax", vp), ("mean", vp), ("lambda_", vp), ("proj", vp), ("group_off", vp)]
@@ -184,6 +190,7 @@ SYMBOLS = {
     "hsimae_cube_gather": (C.c_int, [C.POINTER(CubeParams), vp]),
     "hsimae_scene_windows": (C.c_int, [C.POINTER(SceneParams), vp]),
     "hsimae_class_argmax": (C.c_int, [C.POINTER(SceneParams), vp, i32, i32, i32, vp, vp]),
+    "hsimae_scene_batch": (C.c_int, [C.POINTER(SceneBatchParams), vp]),
     "hsimae_gwpca_workspace_bytes": (i64, [C.POINTER(GwpcaParams)]),
     "hsimae_gwpca_fit": (C.c_int, [C.POINTER(GwpcaParams), vp, vp]),
     "hsimae_gwpca_apply": (C.c_int, [C.POINTER(GwpcaParams), vp, i32, vp]),

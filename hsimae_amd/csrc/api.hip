@@ -948,6 +948,18 @@ int hsimae_class_argmax(const hsimae_scene_params* p, const float* logits, int32
     if (!p->pixels && (p->p0 < 0 || p->p0 + p->N > (int64_t)p->H * p->W)) return HSIMAE_EDIMS;
     return hs_class_argmax(*p, logits, ld, num_class, first, map, S(stream));
 }
+int hsimae_scene_batch(const hsimae_scene_batch_params* p, void* stream) {
+    if (!p || !p->bad) return HSIMAE_ENULL;
+    if (p->N < 0 || p->n_items < 0 || p->H <= 0 || p->W <= 0 || p->C <= 0) return HSIMAE_EDIMS;
+    if (!p->labels != !p->y) return HSIMAE_ENULL;
+    const auto misaligned = [](const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) != 0; };
+    if (misaligned(p->scene, p->scene_f64 ? 8 : 4) || misaligned(p->items, 8) || misaligned(p->pixels, 8) || misaligned(p->labels, 8) ||
+        misaligned(p->out, 4) || misaligned(p->y, 8) || misaligned(p->bad, 4))
+        return HSIMAE_EALIGN;
+    if (p->N == 0) return HSIMAE_OK;
+    if (!p->scene || !p->items || !p->out) return HSIMAE_ENULL;
+    return hs_scene_batch(*p, S(stream));
+}
 int64_t hsimae_gwpca_workspace_bytes(const hsimae_gwpca_params* p) { return p ? hs_gwpca_workspace_bytes(*p) : (int64_t)HSIMAE_ENULL; }
 int hsimae_gwpca_fit(const hsimae_gwpca_params* p, void* workspace, void* stream) {
     return p ? hs_gwpca_fit(*p, workspace, S(stream)) : HSIMAE_ENULL;

@@ -39,6 +39,7 @@ int hs_loss_partials(int N, int T);
 int hs_cube_gather(const CubeParams& p, hipStream_t s);
 int hs_scene_windows(const SceneParams& p, hipStream_t s);
 int hs_class_argmax(const SceneParams& p, const float* logits, int ld, int num_class, int first, int64_t* map, hipStream_t s);
+int hs_scene_batch(const hsimae_scene_batch_params& p, hipStream_t s);
 int64_t hs_gwpca_workspace_bytes(const hsimae_gwpca_params& p);
 int hs_gwpca_fit(const hsimae_gwpca_params& p, void* workspace, hipStream_t s);
 int hs_gwpca_apply(const hsimae_gwpca_params& p, void* out, int out_f64, hipStream_t s);

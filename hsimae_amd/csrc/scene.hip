@@ -88,6 +88,65 @@ void launch_windows(const SceneParams& p, bool vec, hipStream_t s) {
     else hipLaunchKernelGGL((scene_window_kernel<T, false>), dim3(p.N), dim3(256), 0, s, p);
 }
 
+// ------------------------------------------------------------------ fine-tuning batches (Model_Finetuning.py:28-63 `HSIdataset`)
+// Sample k of a batch is entry items[k] of a dataset's tables: its pixel (pixels[item], or the item itself), its label, and the
+// batch's own flip bits.  The same gather as above; a flip only reverses the 9-entry offset table of its axis, so the copy loop
+// is the unflipped one.  An item or a pixel out of range reads nothing: zero window, y = -1, *bad = 1.
+template <typename T, bool VEC>
+__global__ __launch_bounds__(256) void scene_batch_kernel(hsimae_scene_batch_params p) {
+    __shared__ int64_t row_off[9], col_off[9];
+    const int k = blockIdx.x;
+    const int64_t item = p.items[k];                      // every thread the same address: block-uniform
+    int64_t pix = -1;
+    if (item >= 0 && item < p.n_items) pix = p.pixels ? p.pixels[item] : item;
+    const bool ok = pix >= 0 && pix < (int64_t)p.H * p.W;
+    const int C = p.C;
+    if (ok && threadIdx.x < 18) {
+        const int r = (int)(pix / p.W), c = (int)(pix - (int64_t)r * p.W), t = threadIdx.x;
+        const int f = p.flips ? p.flips[k] : 0;
+        if (t < 9) row_off[t] = (int64_t)sym_index(r - 4 + ((f & 2) ? 8 - t : t), p.H) * p.W * C;
+        else col_off[t - 9] = (int64_t)sym_index(c - 4 + ((f & 1) ? 17 - t : t - 9), p.W) * C;
+    }
+    if (threadIdx.x == 32) {
+        if (p.y) p.y[k] = ok ? p.labels[item] : -1;
+        if (!ok) *p.bad = 1;                              // every writer stores the same value
+    }
+    __syncthreads();
+    const T* src = reinterpret_cast<const T*>(p.scene);
+    float* dst = p.out + (int64_t)k * p.sn;
+    if (VEC) {                                            // C % 4 == 0, sb == 1, the other strides and `out` 16-byte aligned
+        const int C4 = C >> 2;
+        for (int e = threadIdx.x; e < 81 * C4; e += 256) {
+            const int px = e / C4, b4 = e - px * C4;
+            const int i = px / 9, j = px - i * 9;
+            float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (ok) {
+                const T* s = src + row_off[i] + col_off[j] + 4 * b4;
+                if (sizeof(T) == 4) {
+                    o = *reinterpret_cast<const float4*>(s);
+                } else {
+                    const double2 a = reinterpret_cast<const double2*>(s)[0], b = reinterpret_cast<const double2*>(s)[1];
+                    o = make_float4((float)a.x, (float)a.y, (float)b.x, (float)b.y);
+                }
+            }
+            *reinterpret_cast<float4*>(dst + (int64_t)i * p.sh + (int64_t)j * p.sw + 4 * b4) = o;
+        }
+    } else {
+        for (int e = threadIdx.x; e < 81 * C; e += 256) {
+            const int px = e / C, b = e - px * C;
+            const int i = px / 9, j = px - i * 9;
+            const float v = ok ? (float)src[row_off[i] + col_off[j] + b] : 0.f;
+            dst[(int64_t)b * p.sb + (int64_t)i * p.sh + (int64_t)j * p.sw] = v;
+        }
+    }
+}
+
+template <typename T>
+void launch_batch(const hsimae_scene_batch_params& p, bool vec, hipStream_t s) {
+    if (vec) hipLaunchKernelGGL((scene_batch_kernel<T, true>), dim3(p.N), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((scene_batch_kernel<T, false>), dim3(p.N), dim3(256), 0, s, p);
+}
+
 }  // namespace
 
 int hs_scene_windows(const SceneParams& p, hipStream_t s) {
@@ -104,6 +163,17 @@ int hs_scene_windows(const SceneParams& p, hipStream_t s) {
 int hs_class_argmax(const SceneParams& p, const float* logits, int ld, int num_class, int first, int64_t* map, hipStream_t s) {
     if (p.N <= 0) return HS_OK;
     hipLaunchKernelGGL(class_argmax_kernel, dim3((p.N + 255) / 256), dim3(256), 0, s, p, logits, ld, num_class, first, map);
+    return (int)hipGetLastError();
+}
+
+int hs_scene_batch(const hsimae_scene_batch_params& p, hipStream_t s) {
+    if (p.N <= 0) return HS_OK;
+    if (p.H <= 0 || p.W <= 0 || p.C <= 0) return HS_EDIMS;
+    const bool vec = (p.C & 3) == 0 && p.sb == 1 && (p.sw & 3) == 0 && (p.sh & 3) == 0 && (p.sn & 3) == 0 &&
+                     (reinterpret_cast<uintptr_t>(p.out) & 15) == 0 &&
+                     (reinterpret_cast<uintptr_t>(p.scene) & (p.scene_f64 ? 31 : 15)) == 0;
+    if (p.scene_f64) launch_batch<double>(p, vec, s);
+    else launch_batch<float>(p, vec, s);
     return (int)hipGetLastError();
 }
 

@@ -29,6 +29,7 @@ from .data import DeviceLoader
 from .finetune import DualViT, HSIViT
 from .optim import FusedAdamW
 from .pretrain import seed_everything
+from .scene_data import SceneCubes, device_scene, unlabeled_pixels
 from .sched import CosineLRScheduler
 
 
@@ -106,6 +107,49 @@ def dual_branch_finetuning(data_list, labeled_index, unlabeled_data, gt, save_di
                            epochs=100, mask_ratio=0.5, lamda=5, batch_size=32, device="cuda:0", log=print):
     device = torch.device(device)
     h, w, c = data_list[0].shape
+
+    def datasets():
+        data_arr = [data_list[i] for i in labeled_index]
+        tr_x, tr_y, va_x, va_y = spilt_dataset(data_arr, gt, training_ratio=0.5)
+        return (HSIdataset(tr_x, tr_y, train=True, device=device), HSIdataset(unlabeled_data, train=True, device=device),
+                HSIdataset(va_x, va_y, device=device))
+
+    return _finetune(datasets, h, c, gt, save_dir, model_name, pretrained, lr, wd, depth, dim, dec_depth, dec_dim, s_depth, epochs,
+                     mask_ratio, lamda, batch_size, device, log)
+
+
+def dual_branch_finetuning_scene(scene, labeled_index, gt, save_dir, model_name, pretrained=None,
+                                 lr=1e-3, wd=5e-3, depth=12, dim=144, dec_depth=2, dec_dim=72, s_depth=6,
+                                 epochs=100, mask_ratio=0.5, lamda=5, batch_size=32, device="cuda:0", log=print):
+    """`dual_branch_finetuning` from the scene itself: `scene` is the processed [H, W, C] `HSI_data` (get_scene_set_dual's third
+    result; a device tensor is used in place), `labeled_index` the labeled pixels r * W + c and `gt` their labels.  The same
+    loop, with `data_list[i]` = the padded window of pixel i and `unlabeled_data` = the scene's non-overlapping 9 x 9 tiles,
+    both cut per batch on the device (scene_data.SceneCubes): no `data_cubes` is ever built.  Same np.random / torch /
+    python-random consumption, same return value."""
+    device = torch.device(device)
+    scene = device_scene(scene, device)                                         # uploaded once, shared by the three sets
+    H, W, c = (int(v) for v in scene.shape)
+    device = scene.device
+    sets = []
+
+    def datasets():
+        tr_i, tr_y, va_i, va_y = spilt_dataset(list(labeled_index), gt, training_ratio=0.5)
+        sets.extend([SceneCubes(scene, tr_i, tr_y, train=True), SceneCubes(scene, unlabeled_pixels(H, W), train=True),
+                     SceneCubes(scene, va_i, va_y)])
+        return tuple(sets)
+
+    def check():
+        for ds in sets:
+            ds.check()
+
+    return _finetune(datasets, 9, c, gt, save_dir, model_name, pretrained, lr, wd, depth, dim, dec_depth, dec_dim, s_depth, epochs,
+                     mask_ratio, lamda, batch_size, device, log, check)
+
+
+def _finetune(datasets, h, c, gt, save_dir, model_name, pretrained, lr, wd, depth, dim, dec_depth, dec_dim, s_depth, epochs, mask_ratio,
+              lamda, batch_size, device, log, check_data=None):
+    """The loop of Model_Finetuning.py:66-240.  `datasets()` -> (labeled, unlabeled, validation), called where the reference
+    splits the labeled set (after the model's initialisation draws); `check_data()` once per epoch, with the loss's check."""
     n_class = int(np.max(gt) + 1)
     model = DualViT(img_size=h, patch_size=3, in_chans=1, bands=c, b_patch_size=8, num_class=n_class,
                     embed_dim=dim, depth=depth, num_heads=dim // 16, s_depth=s_depth,
@@ -125,11 +169,7 @@ def dual_branch_finetuning(data_list, labeled_index, unlabeled_data, gt, save_di
     criterion = ClassLoss(ignore_index=0)
     meter = ScoreMeter(n_class, device)
 
-    data_arr = [data_list[i] for i in labeled_index]
-    tr_x, tr_y, va_x, va_y = spilt_dataset(data_arr, gt, training_ratio=0.5)
-    train_ds = HSIdataset(tr_x, tr_y, train=True, device=device)
-    unl_ds = HSIdataset(unlabeled_data, train=True, device=device)
-    val_ds = HSIdataset(va_x, va_y, device=device)
+    train_ds, unl_ds, val_ds = datasets()
     train_dl = DeviceLoader(train_ds, batch_size=batch_size, shuffle=True)
     unl_bs = int(np.ceil(len(unl_ds) / len(train_dl)) / 2)
     unl_dl = DeviceLoader(unl_ds, batch_size=unl_bs, shuffle=True)
@@ -164,6 +204,8 @@ def dual_branch_finetuning(data_list, labeled_index, unlabeled_data, gt, save_di
         val_value = list(meter.compute())
         tr, va = torch.stack([train_loss, val_loss]).tolist()                   # the epoch's one wait for its losses
         criterion.check()
+        if check_data is not None:
+            check_data()
         epoch_loss_list.append(tr / len(train_dl))
         val_loss_list.append(va / len(val_dl))
         scheduler.step(epoch)

@@ -514,6 +514,35 @@ int hsimae_scene_windows(const hsimae_scene_params* p, void* stream);
 int hsimae_class_argmax(const hsimae_scene_params* p, const float* logits, int32_t ld, int32_t num_class, int32_t first, int64_t* map,
                         void* stream);
 
+/* ------------------------------------------------------------------ fine-tuning batches from the scene (Model_Finetuning.py:28-63)
+ * ADDED under HSIMAE_VERSION 108 like the classification entry points below: nothing that 108 already had changes.
+ * One launch assembles a batch of the fine-tuning `HSIdataset` from the HBM-resident scene [H][W][C] (fp32 or fp64, as in
+ * hsimae_scene_params) instead of from host-built `data_cubes`: windows, flips and labels.
+ *   items   int64 [N], device: sample k is entry items[k] of the dataset's tables (a batch may repeat an entry);
+ *   n_items the tables' length;
+ *   pixels  int64 [n_items] or NULL: the entry's pixel r * W + c.  NULL: entry i is pixel i, and n_items = H * W;
+ *   labels  int64 [n_items] or NULL;
+ *   flips   uint8 [N] or NULL (no flips): bit 0 = np.flip(data, 1), along w; bit 1 = np.flip(data, 0), along h;
+ *   out     out[k, 0, b, i, j] = (float) scene[sym(r - 4 + i', H)][sym(c - 4 + j', W)][b] through the element strides sn, sb, sh,
+ *           sw, with i' = bit 1 ? 8 - i : i, j' = bit 0 ? 8 - j : j, and sym and the fp64 -> fp32 rounding of
+ *           hsimae_scene_windows: bit-exact with the reference's items.  An unpadded 9 x 9 tile with origin (r0, c0)
+ *           (`data_cubes_2`, the unlabeled set) is the window of pixel (r0 + 4, c0 + 4);
+ *   y       int64 [N] = labels[items[k]]; required exactly when `labels` is given;
+ *   bad     int32 flag, required: an item outside [0, n_items) or a pixel outside [0, H * W) reads nothing, gets a window of
+ *           zeros and y = -1, and sets *bad = 1.  The call never clears the flag.
+ * One workgroup per sample, no host wait; two runs are bit-identical.
+ * Refusals: params or bad NULL, `labels` without `y` or `y` without `labels`, and with N > 0 scene, items or out NULL ->
+ * HSIMAE_ENULL; H, W or C <= 0, N < 0, n_items < 0 -> HSIMAE_EDIMS; a pointer not aligned to its element -> HSIMAE_EALIGN.
+ * N = 0 -> HSIMAE_OK, nothing written. */
+typedef struct {
+    const void* scene; int32_t scene_f64; int32_t H, W, C;
+    const int64_t* items; int32_t N;
+    int64_t n_items; const int64_t* pixels; const int64_t* labels; const uint8_t* flips;
+    float* out; int64_t sn, sb, sh, sw;
+    int64_t* y; int32_t* bad;
+} hsimae_scene_batch_params;
+int hsimae_scene_batch(const hsimae_scene_batch_params* p, void* stream);
+
 /* ------------------------------------------------------------------ group-wise PCA of a raw scene (Utils/GroupWisePCA.py) */
 /* `applyGWPCA` on the device: x = (X - min X) / (max X - min X) over the whole scene [H][W][C] (row-major, fp32 or fp64; an
  * fp32 scene is widened to fp64 exactly, where the reference would stay in fp32), the band axis halved `group / 2` times

@@ -1,5 +1,8 @@
 """Fine-tuning iteration at the reference's defaults: the parent's loop body (torch CrossEntropyLoss, argmax, loss.item())
-against this tree's (ClassLoss, device sums), alternating, on the same model; epoch-end metric; test_model_scene tail."""
+against this tree's (ClassLoss, device sums), alternating, on the same model; epoch-end metric; test_model_scene tail.
+--prep: the data side instead, on a synthetic 610 x 340 x 32 fp64 scene: host time and peak host bytes of building data_cubes +
+data_cubes_2 + the three HSIdataset uploads against get_scene_set_dual(GWPCA=False) + three SceneCubes, and the batch assembly
+time per iteration of both at the reference's batch sizes (-> profiles/finetune_prep.json)."""
 import contextlib, io, json, os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.getcwd())
@@ -8,6 +11,75 @@ from hsimae_amd.finetune_train import scores
 
 PROFILE = "--profile" in sys.argv
 dev = torch.device("cuda:0")
+
+
+def prep():
+    import random
+    import tracemalloc
+    from hsimae_amd import DeviceLoader, SceneCubes, get_scene_set_dual, unlabeled_pixels
+    from hsimae_amd.finetune_train import HSIdataset, spilt_dataset
+    from hsimae_amd.scene_data import split_labeled, tile_origins
+    H, W, Cb, n_class = 610, 340, 32, 10
+    rng = np.random.default_rng(0)
+    raw = rng.standard_normal((H, W, Cb))
+    gt = rng.integers(0, n_class, (H, W)); gt.reshape(-1)[:n_class] = np.arange(n_class)
+    res = {"scene": [H, W, Cb], "scene_bytes": raw.nbytes}
+    torch.zeros(1, device=dev); torch.cuda.synchronize()
+
+    def measured(fn):
+        tracemalloc.start(); torch.cuda.synchronize(); t = time.perf_counter()
+        out = fn(); torch.cuda.synchronize(); dt = time.perf_counter() - t
+        peak = tracemalloc.get_traced_memory()[1]; tracemalloc.stop()
+        return out, dt, peak
+
+    def old_prep():                                                 # Utils/Preprocessing.py:205-213 + Model_Finetuning.py:111-115
+        cubes2 = np.array([raw[r:r + 9, c:c + 9] for r in tile_origins(H) for c in tile_origins(W)])
+        pad = np.pad(raw, ((4, 4), (4, 4), (0, 0)), "symmetric")
+        cubes = np.array([pad[r:r + 9, c:c + 9] for r in range(H) for c in range(W)])
+        np.random.seed(1); idx, lab, _ = split_labeled(gt, num=40)
+        np.random.seed(2); tr_x, tr_y, va_x, va_y = spilt_dataset([cubes[i] for i in idx], lab, training_ratio=0.5)
+        return HSIdataset(tr_x, tr_y, train=True, device=dev), HSIdataset(cubes2, train=True, device=dev), HSIdataset(va_x, va_y, device=dev)
+
+    def new_prep():
+        np.random.seed(1); idx, lab, scene, _, _ = get_scene_set_dual(raw, gt, num=40, GWPCA=False, device=dev)
+        np.random.seed(2); tr_i, tr_y, va_i, va_y = spilt_dataset(list(idx), lab, training_ratio=0.5)
+        return SceneCubes(scene, tr_i, tr_y, train=True), SceneCubes(scene, unlabeled_pixels(H, W), train=True), SceneCubes(scene, va_i, va_y)
+
+    sets = {}
+    for name, fn in (("new", new_prep), ("old", old_prep)):
+        sets[name], res[f"prep_{name}_s"], res[f"prep_{name}_peak_host_bytes"] = measured(fn)
+        print(f"prep {name}: {res[f'prep_{name}_s']:.3f} s, peak host {res[f'prep_{name}_peak_host_bytes'] / 1e6:.1f} MB, "
+              f"{len(sets[name][0])} / {len(sets[name][1])} / {len(sets[name][2])} items")
+
+    def epoch(ds3):                                                 # the loop's data path, Model_Finetuning.py:119-122, 144-149
+        train_dl = DeviceLoader(ds3[0], batch_size=32, shuffle=True)
+        unl_dl = DeviceLoader(ds3[1], batch_size=int(np.ceil(len(ds3[1]) / len(train_dl)) / 2), shuffle=True)
+        a, b = iter(train_dl), iter(unl_dl)
+        for _ in range(len(train_dl)):
+            next(a); next(b)
+        return len(train_dl)
+
+    for name in ("old", "new"):
+        torch.manual_seed(0); epoch(sets[name]); torch.cuda.synchronize()
+        times = []
+        for rep in range(5):
+            t = time.perf_counter(); n = epoch(sets[name]); torch.cuda.synchronize()
+            times.append((time.perf_counter() - t) / n * 1e3)
+        res[f"batch_{name}_ms"] = times
+        print(f"batch assembly, ms / iteration (labeled 32 + unlabeled), {name}:", ["%.3f" % v for v in times])
+    random.seed(3)
+    xo = sets["old"][0].batch(list(range(32)))
+    random.seed(3)
+    xn = sets["new"][0].batch(list(range(32)))
+    res["first_batch_equal"] = bool(torch.equal(xo[0], xn[0]) and torch.equal(xo[1], xn[1]))
+    print("first labeled batch equal:", res["first_batch_equal"])
+    os.makedirs("profiles", exist_ok=True)
+    json.dump(res, open("profiles/finetune_prep.json", "w"), indent=1)
+
+
+if "--prep" in sys.argv:
+    prep(); sys.exit(0)
+
 torch.manual_seed(0); np.random.seed(0)
 n_class, bands, B = 10, 32, 32
 with contextlib.redirect_stdout(io.StringIO()):
