@@ -139,6 +139,20 @@ class ClsParams(C.Structure):
                 ("loss", vp), ("n_valid", vp), ("dlogits", vp), ("ldd", i32), ("pred", vp), ("bad", vp), ("workspace", vp)]
 
 
+class GradSeg(C.Structure):
+    _fields_ = [("g", vp), ("group", vp), ("n", i64)]
+
+
+class ClipCtl(C.Structure):
+    """hsimae_clip_ctl: lives in DEVICE memory; this mirror gives its size and the byte offsets of its fields."""
+    _fields_ = [("sumsq", C.c_double), ("norm", f32), ("coef", f32), ("finite", i32), ("apply", i32), ("skipped", i64),
+                ("inv_bc1", f32), ("inv_sqrt_bc2", f32), ("norm_max", f32)]
+
+
+CLIP_GRID = 1024        # HSIMAE_CLIP_GRID: doubles of scratch hsimae_grad_norm needs in `partials`
+CLIP_MAX_SEGS = 8       # HSIMAE_CLIP_MAX_SEGS
+
+
 class BuildInfo(C.Structure):
     _fields_ = [("abi_version", i32), ("variant_bits", C.c_uint32), ("kernel_source_hash", C.c_uint64), ("flags_hash", C.c_uint64),
                 ("default_flags", i32), ("reserved", i32)]
@@ -187,6 +201,8 @@ SYMBOLS = {
     "hsimae_loss_partials": (C.c_int, [i32, i32]),
     "hsimae_loss": (C.c_int, [C.POINTER(LossParams), vp]),
     "hsimae_adamw_step": (C.c_int, [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, vp]),
+    "hsimae_grad_norm": (C.c_int, [C.POINTER(GradSeg), i32, f32, i32, i32, f32, f32, vp, vp, vp]),
+    "hsimae_adamw_step_ctl": (C.c_int, [vp, vp, vp, vp, vp, i32, i64, f32, f32, f32, f32, f32, vp, vp]),
     "hsimae_cube_gather": (C.c_int, [C.POINTER(CubeParams), vp]),
     "hsimae_scene_windows": (C.c_int, [C.POINTER(SceneParams), vp]),
     "hsimae_class_argmax": (C.c_int, [C.POINTER(SceneParams), vp, i32, i32, i32, vp, vp]),

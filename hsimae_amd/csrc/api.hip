@@ -421,6 +421,7 @@ extern "C" unsigned hs_variant_bits_loader();
 extern "C" unsigned hs_variant_bits_scene();
 extern "C" unsigned hs_variant_bits_gwpca();
 extern "C" unsigned hs_variant_bits_cls();
+extern "C" unsigned hs_variant_bits_clip();
 #ifndef HS_KERNEL_SOURCE_HASH
 #define HS_KERNEL_SOURCE_HASH 0ULL
 #endif
@@ -438,7 +439,7 @@ int hsimae_version(void) { return HSIMAE_VERSION; }
 int hsimae_build_info(hsimae_build_info_t* out) {
     if (!out) return HSIMAE_ENULL;
     out->abi_version = HSIMAE_VERSION;
-    out->variant_bits = hs_variant_bits() | hs_variant_bits_gemm() | hs_variant_bits_attn() | hs_variant_bits_attn_wide() | hs_variant_bits_wgrad() | hs_variant_bits_elem() | hs_variant_bits_pack() | hs_variant_bits_fused_dec() | hs_variant_bits_fused_enc() | hs_variant_bits_loader() | hs_variant_bits_scene() | hs_variant_bits_gwpca() | hs_variant_bits_cls();
+    out->variant_bits = hs_variant_bits() | hs_variant_bits_gemm() | hs_variant_bits_attn() | hs_variant_bits_attn_wide() | hs_variant_bits_wgrad() | hs_variant_bits_elem() | hs_variant_bits_pack() | hs_variant_bits_fused_dec() | hs_variant_bits_fused_enc() | hs_variant_bits_loader() | hs_variant_bits_scene() | hs_variant_bits_gwpca() | hs_variant_bits_cls() | hs_variant_bits_clip();
     out->kernel_source_hash = HS_KERNEL_SOURCE_HASH;
     out->flags_hash = HS_BUILD_FLAGS_HASH;
     out->default_flags = HS_BUILD_DEFAULT_FLAGS;
@@ -990,6 +991,15 @@ int hsimae_adamw_step(float* params, const float* grads, float* exp_avg, float* 
                       float lr, float beta1, float beta2, float eps, float weight_decay, int32_t step, void* stream) {
     if (!params || !grads || !exp_avg || !exp_avg_sq || !group) return HSIMAE_ENULL;
     return hs_adamw(params, grads, exp_avg, exp_avg_sq, group, n, lr, beta1, beta2, eps, weight_decay, step, S(stream));
+}
+int hsimae_grad_norm(const hsimae_grad_seg* segs, int32_t nseg, float max_norm, int32_t skip_nonfinite, int32_t step, float beta1,
+                     float beta2, double* partials, hsimae_clip_ctl* ctl, void* stream) {
+    return hs_grad_norm(segs, nseg, max_norm, skip_nonfinite, step, beta1, beta2, partials, ctl, S(stream));
+}
+int hsimae_adamw_step_ctl(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* group,
+                          int32_t group_uniform, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
+                          const hsimae_clip_ctl* ctl, void* stream) {
+    return hs_adamw_ctl(params, grads, exp_avg, exp_avg_sq, group, group_uniform, n, lr, beta1, beta2, eps, weight_decay, ctl, S(stream));
 }
 int hsimae_loss_partials(int32_t N, int32_t T) { return hs_loss_partials(N, T); }
 int hsimae_loss(const hsimae_loss_params* p, void* stream) { return p ? hs_loss(*p, S(stream)) : HSIMAE_ENULL; }

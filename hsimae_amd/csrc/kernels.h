@@ -110,3 +110,8 @@ int hs_enc_mlp_bwd(const float* x1, const float* dy, float* dx1, hs_bf16* u2, hs
 
 int hs_adamw(float* p, const float* g, float* m, float* v, const unsigned char* group, int64_t n, float lr, float b1, float b2,
              float eps, float wd, int step, hipStream_t s);
+// clip.hip: the gradient norm / clip coefficient / skip decision in device memory, and the AdamW step that reads them
+int hs_grad_norm(const hsimae_grad_seg* segs, int nseg, float max_norm, int skip_nonfinite, int step, float beta1, float beta2,
+                 double* partials, hsimae_clip_ctl* ctl, hipStream_t s);
+int hs_adamw_ctl(float* p, const float* g, float* m, float* v, const unsigned char* group, int group_uniform, int64_t n, float lr,
+                 float b1, float b2, float eps, float wd, const hsimae_clip_ctl* ctl, hipStream_t s);

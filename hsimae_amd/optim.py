@@ -4,7 +4,11 @@ The reference builds `torch.optim.AdamW` over two name-filtered parameter groups
 steps it once per iteration (:102).  With fwd+bwd at ~30 ms, 535 per-tensor updates are pure launch overhead; here
 the whole flat parameter buffer is updated by ONE kernel (`hsimae_adamw_step`) with torch's AdamW arithmetic, and
 the model is told to refresh its packed bf16 weight images.  `param_groups` is kept (one dict per reference group,
-sharing `lr`) so LR schedulers that write `group['lr']` keep working."""
+sharing `lr`) so LR schedulers that write `group['lr']` keep working.
+
+`max_grad_norm` / `skip_nonfinite` (both off by default, and then nothing below changes) put the size of the update under control
+without a host wait: `hsimae_grad_norm` forms the global 2-norm of every gradient that takes part in the step, the clip
+coefficient and the decision to skip a non-finite step in device memory, and `hsimae_adamw_step_ctl` reads them there."""
 from __future__ import annotations
 
 import torch
@@ -13,15 +17,34 @@ from . import _lib
 
 
 class FusedAdamW:
-    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, no_decay=("bias", "norm"), strict=True):
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, no_decay=("bias", "norm"), strict=True,
+                 max_grad_norm=None, skip_nonfinite=False):
+        """max_grad_norm: clip the global gradient 2-norm to it, with torch.nn.utils.clip_grad_norm_'s coefficient
+        min(1, max_norm / (norm + 1e-6)); `float("inf")` only measures.  skip_nonfinite: a step whose norm is Inf or NaN
+        changes nothing (no parameter, no moment, no weight decay, no advance of the bias-correction count).
+
+        The clip is applied INSIDE the step: `.grad` is not modified, the update is computed from g * coef.  A parameter
+        that is masked out of the step (no `.grad`) is left out of the norm, as torch leaves out a `.grad` that is None.
+        `step()` waits for nothing and copies nothing to the host; `grad_norm`, `clip_coef` and `skipped_steps` are 0-d device
+        tensors (views of the control block), and reading them from the host is the caller's wait.
+
+        Data parallel: the reducer's all-reduce has completed on the stream before `step()` reads the gradients; the norm kernel
+        is launched on the same stream, sees the reduced gradients, and so every rank takes the same decision."""
         self.model = model
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        if self.max_grad_norm is not None and not self.max_grad_norm > 0:
+            raise ValueError(f"max_grad_norm must be greater than 0 (or None), got {max_grad_norm}")
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._clip = self.max_grad_norm is not None or self.skip_nonfinite
+        self._ctl = self._partials = None
+        self._skipped_loaded = None
         self.strict = bool(strict)                   # see _sync_grads
         self._mask_cache = {}
         self.defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay)
         decay, nodecay = [], []
         self._groups_of = []
         # Parameters that do not live in the model's flat buffer (DualViT's cls_head) are stepped by a stock
-        # torch.optim.AdamW with the same hyper-parameters; their lr follows param_groups[0] / [1].
+        # torch.optim.AdamW with the same hyper-parameters; their lr follows param_groups[0] / [1].  (Not in the clipped mode.)
         in_flat = {id(p) for p in model._plist()} if hasattr(model, "_plist") else None
         extra_decay, extra_nodecay = [], []
         for n, p in model.named_parameters():
@@ -40,7 +63,15 @@ class FusedAdamW:
         self.param_groups = [dict(params=decay, lr=lr, weight_decay=weight_decay, betas=tuple(betas), eps=eps),
                              dict(params=nodecay, lr=lr, weight_decay=0.0, betas=tuple(betas), eps=eps)]
         self._extra = None
-        if extra_decay or extra_nodecay:
+        # In the clipped mode the optimizer steps the outside parameters itself (its own moments, hsimae_adamw_step_ctl with
+        # their reference group for every element): a host-side optimizer could not honour a skip decided on the device.
+        self._outside = [(p, 0) for p in extra_decay] + [(p, 1) for p in extra_nodecay] if self._clip else []
+        self._out_m = [None] * len(self._outside)
+        self._out_v = [None] * len(self._outside)
+        if len(self._outside) > _lib.CLIP_MAX_SEGS - 1:
+            raise NotImplementedError(f"FusedAdamW(max_grad_norm / skip_nonfinite): {len(self._outside)} parameters outside the flat "
+                                      f"buffer, one hsimae_grad_norm call takes {_lib.CLIP_MAX_SEGS - 1}")
+        if (extra_decay or extra_nodecay) and not self._clip:
             groups = [(0, dict(params=extra_decay, weight_decay=weight_decay)), (1, dict(params=extra_nodecay, weight_decay=0.0))]
             groups = [(i, g) for i, g in groups if g["params"]]
             self._extra_of = [i for i, _ in groups]          # which reference group each extra group follows
@@ -139,6 +170,10 @@ class FusedAdamW:
         b1, b2 = g0["betas"]
         stream = torch.cuda.current_stream(m._flat.device).cuda_stream
         group = self._sync_grads()
+        if self._clip:
+            self._step_clipped(group, float(b1), float(b2), stream)
+            m._packed_version = -1
+            return
         _lib.check(_lib.load().hsimae_adamw_step(
             m._flat.data_ptr(), m._flat_grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
             group.data_ptr(), m._flat.numel(), float(g0["lr"]), float(b1), float(b2), float(g0["eps"]),
@@ -149,10 +184,94 @@ class FusedAdamW:
                 ge["lr"] = self.param_groups[gi]["lr"]
             self._extra.step()
 
+    # ------------------------------------------------------------------ gradient norm / clipping / skip (off by default)
+    def _ensure_ctl(self, device=None):
+        if self._ctl is None:
+            if not self._clip:
+                raise AttributeError("FusedAdamW was built without max_grad_norm / skip_nonfinite: there is no gradient norm")
+            device = device if device is not None else next(self.model.parameters()).device
+            if torch.device(device).type != "cuda":
+                raise RuntimeError("FusedAdamW: the model is not on the GPU (hsimae_amd has no CPU fallback)")
+            f = _lib.ClipCtl
+            self._ctl = torch.zeros(_lib.C.sizeof(f), dtype=torch.uint8, device=device)     # skipped = 0, norm_max = 0
+            self._partials = torch.empty(_lib.CLIP_GRID, dtype=torch.float64, device=device)
+
+            def field(fd, dtype):
+                return self._ctl[fd.offset: fd.offset + fd.size].view(dtype)[0]
+            self._views = dict(norm=field(f.norm, torch.float32), coef=field(f.coef, torch.float32),
+                               skipped=field(f.skipped, torch.int64), norm_max=field(f.norm_max, torch.float32))
+            if self._skipped_loaded is not None:
+                self._views["skipped"].copy_(torch.as_tensor(self._skipped_loaded, dtype=torch.int64))
+                self._skipped_loaded = None
+        return self._views
+
+    @property
+    def grad_norm(self):
+        """Global 2-norm of the last step's gradients, before clipping (0-d fp32 device tensor)."""
+        return self._ensure_ctl()["norm"]
+
+    @property
+    def clip_coef(self):
+        """What the last step multiplied the gradients by (0-d fp32 device tensor)."""
+        return self._ensure_ctl()["coef"]
+
+    @property
+    def skipped_steps(self):
+        """Number of steps skipped for a non-finite norm so far (0-d int64 device tensor)."""
+        return self._ensure_ctl()["skipped"]
+
+    @property
+    def grad_norm_max(self):
+        """Largest finite `grad_norm` since `reset_grad_norm_max()` (0-d fp32 device tensor; the loops log it per epoch)."""
+        return self._ensure_ctl()["norm_max"]
+
+    def reset_grad_norm_max(self):
+        self._ensure_ctl()["norm_max"].zero_()
+
+    def _step_clipped(self, group, b1, b2, stream):
+        m, lib = self.model, _lib.load()
+        flat = m._flat
+        self._ensure_ctl(flat.device)
+        segs = (_lib.GradSeg * _lib.CLIP_MAX_SEGS)()
+        segs[0] = _lib.GradSeg(m._flat_grad.data_ptr(), group.data_ptr(), flat.numel())
+        live = []
+        for k, (p, gid) in enumerate(self._outside):
+            g = p.grad
+            if g is None:                              # as torch: not in the norm, not stepped
+                continue
+            if g.dtype != torch.float32 or not g.is_contiguous():
+                g = g.float().contiguous()
+            if not p.is_contiguous() or p.dtype != torch.float32:
+                raise RuntimeError("FusedAdamW: a parameter outside the flat buffer must be a contiguous fp32 tensor")
+            if self._out_m[k] is None or self._out_m[k].device != p.device:
+                z = torch.zeros(p.numel(), dtype=torch.float32, device=p.device)
+                self._out_m[k] = z if self._out_m[k] is None else self._out_m[k].to(p.device)
+                self._out_v[k] = z.clone() if self._out_v[k] is None else self._out_v[k].to(p.device)
+            live.append((k, p, g, gid))
+            segs[len(live)] = _lib.GradSeg(g.data_ptr(), None, g.numel())
+        g0 = self.param_groups[0]
+        max_norm = float("inf") if self.max_grad_norm is None else self.max_grad_norm
+        ctl = self._ctl.data_ptr()
+        _lib.check(lib.hsimae_grad_norm(segs, 1 + len(live), max_norm, int(self.skip_nonfinite), self.step_count, b1, b2,
+                                        self._partials.data_ptr(), ctl, stream), "hsimae_grad_norm")
+        _lib.check(lib.hsimae_adamw_step_ctl(
+            flat.data_ptr(), m._flat_grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), group.data_ptr(), 0,
+            flat.numel(), float(g0["lr"]), b1, b2, float(g0["eps"]), float(g0["weight_decay"]), ctl, stream), "hsimae_adamw_step_ctl")
+        for k, p, g, gid in live:
+            _lib.check(lib.hsimae_adamw_step_ctl(
+                p.data_ptr(), g.data_ptr(), self._out_m[k].data_ptr(), self._out_v[k].data_ptr(), None, gid, p.numel(),
+                float(self.param_groups[gid]["lr"]), b1, b2, float(g0["eps"]), float(g0["weight_decay"]), ctl, stream),
+                "hsimae_adamw_step_ctl")
+
     def state_dict(self):
-        return {"step": self.step_count, "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq,
-                "param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups],
-                "extra": self._extra.state_dict() if self._extra is not None else None}
+        sd = {"step": self.step_count, "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq,
+              "param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups],
+              "extra": self._extra.state_dict() if self._extra is not None else None}
+        if self._clip:
+            sd["skipped"] = (self._views["skipped"].clone() if self._ctl is not None
+                             else torch.as_tensor(self._skipped_loaded or 0, dtype=torch.int64))
+            sd["outside_exp_avg"], sd["outside_exp_avg_sq"] = list(self._out_m), list(self._out_v)
+        return sd
 
     def load_state_dict(self, sd):
         self.step_count = int(sd["step"])
@@ -161,4 +280,29 @@ class FusedAdamW:
             g.update(s)
         if self._extra is not None and sd.get("extra") is not None:
             self._extra.load_state_dict(sd["extra"])
+        if self._clip:
+            self._load_clip_state(sd)
         self._flat_id = None
+
+    def _load_clip_state(self, sd):
+        """`skipped` and the outside parameters' moments.  A checkpoint written without the feature has neither: skipped = 0, and
+        the moments are taken from the stock optimizer's state it carries for those parameters (same order: decayed, then not)."""
+        sk = sd.get("skipped", 0)
+        if self._ctl is not None:
+            self._views["skipped"].copy_(torch.as_tensor(sk, dtype=torch.int64))
+        else:
+            self._skipped_loaded = sk.clone() if torch.is_tensor(sk) else int(sk)
+        n = len(self._outside)
+        if sd.get("outside_exp_avg") is not None:
+            om, ov = list(sd["outside_exp_avg"]), list(sd["outside_exp_avg_sq"])
+            if len(om) != n or len(ov) != n:
+                raise ValueError(f"checkpoint carries moments for {len(om)} outside parameters, the model has {n}")
+            self._out_m = [None if t is None else t.reshape(-1) for t in om]
+            self._out_v = [None if t is None else t.reshape(-1) for t in ov]
+        elif sd.get("extra") is not None:
+            state = sd["extra"].get("state", {})
+            for k in range(n):
+                st = state.get(k)
+                if st is not None and "exp_avg" in st:
+                    self._out_m[k] = st["exp_avg"].detach().float().reshape(-1).clone()
+                    self._out_v[k] = st["exp_avg_sq"].detach().float().reshape(-1).clone()

@@ -633,6 +633,49 @@ int hsimae_confusion_map(const int64_t* gt_map, const int64_t* mask_map, const i
                          int64_t* cm, int32_t* bad, void* stream);
 int hsimae_scores(const int64_t* cm, int32_t C, double* out, void* stream);
 
+/* ------------------------------------------------------------------ gradient norm, clipping and the non-finite step skip
+ * (what torch.nn.utils.clip_grad_norm_ and an `isfinite(...).item()` test do on the host, kept in device memory: no host wait).
+ * ADDED under HSIMAE_VERSION 108 like the entry points above: nothing that 108 already had changes; hsimae_adamw_step is as it was.
+ *
+ * hsimae_grad_norm: the 2-norm over up to HSIMAE_CLIP_MAX_SEGS segments of fp32 gradients.  A segment without `group` counts
+ *   every element; with it (one id per element, hsimae_adamw_step's) an element whose id is 2 is left out of the sum, whatever
+ *   it holds.  `n` need not be a multiple of 4 and `g` need only be 4-byte aligned.  Two launches on `stream`: a fixed grid of
+ *   HSIMAE_CLIP_GRID workgroups forms squares and sums in fp64 and writes one fp64 partial per workgroup (`partials`:
+ *   HSIMAE_CLIP_GRID doubles, 8-byte aligned, scratch); one workgroup then adds them in a fixed order and fills `ctl`.  No
+ *   atomics: two runs on the same input agree bit for bit.  Written to ctl:
+ *     sumsq, norm = (float)sqrt(sumsq), finite = sumsq is finite;
+ *     coef    = (float)min(1, max_norm / (norm + 1e-6)) evaluated in fp64 (clip_grad_norm_'s formula; 1.0f for max_norm = +inf
+ *               and a finite norm; with a norm that is not finite, what IEEE arithmetic gives: 0 for +inf, NaN for NaN);
+ *     apply   = !(skip_nonfinite && !finite);   skipped += !apply (the caller zeroes it once);
+ *     inv_bc1, inv_sqrt_bc2 = 1 / (1 - beta1^t), 1 / sqrt(1 - beta2^t) for t = step - skipped, fp64 rounded to fp32;
+ *     norm_max = max(norm_max, norm) when finite (the caller zeroes it when it has read it).
+ *   Refusals, before any launch: nseg outside 1 .. 8, a segment with n < 0, step < 1, ctl or partials NULL, max_norm not > 0
+ *   (NaN included; +inf is allowed and means report only) -> HSIMAE_EDIMS; segs NULL, g NULL with n > 0 -> HSIMAE_ENULL; g not
+ *   4-byte, partials or ctl not 8-byte aligned -> HSIMAE_EALIGN.
+ * hsimae_adamw_step_ctl: hsimae_adamw_step's update, element for element, on g * ctl->coef (one fp32 multiply; `g` itself is
+ *   not modified) with the bias corrections read from ctl; when ctl->apply is 0 nothing is written.  group NULL: every element
+ *   has the id `group_uniform`.  Any n >= 0.  One launch, no host wait.
+ *   Refusals: n < 0, group NULL with group_uniform outside 0 .. 2 -> HSIMAE_EDIMS; a NULL array or ctl with n > 0 -> HSIMAE_ENULL;
+ *   an array not 4-byte or ctl not 8-byte aligned -> HSIMAE_EALIGN. */
+#define HSIMAE_CLIP_GRID 1024        /* workgroups of the norm's first launch = doubles the caller provides in `partials` */
+#define HSIMAE_CLIP_MAX_SEGS 8
+typedef struct { const float* g; const uint8_t* group; int64_t n; } hsimae_grad_seg;
+typedef struct hsimae_clip_ctl {     /* written by hsimae_grad_norm, read by hsimae_adamw_step_ctl; 48 bytes */
+    double sumsq;
+    float norm;
+    float coef;
+    int32_t finite;
+    int32_t apply;
+    int64_t skipped;
+    float inv_bc1, inv_sqrt_bc2;
+    float norm_max;
+} hsimae_clip_ctl;
+int hsimae_grad_norm(const hsimae_grad_seg* segs, int32_t nseg, float max_norm, int32_t skip_nonfinite, int32_t step, float beta1,
+                     float beta2, double* partials, hsimae_clip_ctl* ctl, void* stream);
+int hsimae_adamw_step_ctl(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* group,
+                          int32_t group_uniform, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
+                          const hsimae_clip_ctl* ctl, void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
