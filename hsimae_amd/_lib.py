@@ -149,6 +149,12 @@ class ClipCtl(C.Structure):
                 ("inv_bc1", f32), ("inv_sqrt_bc2", f32), ("norm_max", f32)]
 
 
+class AdamWGroup(C.Structure):
+    """hsimae_adamw_group: one entry of hsimae_adamw_step_groups' table (host memory, copied into the launch)."""
+    _fields_ = [("lr", f32), ("weight_decay", f32)]
+
+
+ADAMW_MAX_GROUPS = 64   # HSIMAE_ADAMW_MAX_GROUPS
 CLIP_GRID = 1024        # HSIMAE_CLIP_GRID: doubles of scratch hsimae_grad_norm needs in `partials`
 CLIP_MAX_SEGS = 8       # HSIMAE_CLIP_MAX_SEGS
 
@@ -203,6 +209,7 @@ SYMBOLS = {
     "hsimae_adamw_step": (C.c_int, [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, vp]),
     "hsimae_grad_norm": (C.c_int, [C.POINTER(GradSeg), i32, f32, i32, i32, f32, f32, vp, vp, vp]),
     "hsimae_adamw_step_ctl": (C.c_int, [vp, vp, vp, vp, vp, i32, i64, f32, f32, f32, f32, f32, vp, vp]),
+    "hsimae_adamw_step_groups": (C.c_int, [vp, vp, vp, vp, vp, i32, i64, C.POINTER(AdamWGroup), i32, f32, f32, f32, i32, vp, vp]),
     "hsimae_cube_gather": (C.c_int, [C.POINTER(CubeParams), vp]),
     "hsimae_scene_windows": (C.c_int, [C.POINTER(SceneParams), vp]),
     "hsimae_class_argmax": (C.c_int, [C.POINTER(SceneParams), vp, i32, i32, i32, vp, vp]),

@@ -1001,6 +1001,12 @@ int hsimae_adamw_step_ctl(float* params, const float* grads, float* exp_avg, flo
                           const hsimae_clip_ctl* ctl, void* stream) {
     return hs_adamw_ctl(params, grads, exp_avg, exp_avg_sq, group, group_uniform, n, lr, beta1, beta2, eps, weight_decay, ctl, S(stream));
 }
+int hsimae_adamw_step_groups(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* group,
+                             int32_t group_uniform, int64_t n, const hsimae_adamw_group* table, int32_t ngroups, float beta1,
+                             float beta2, float eps, int32_t step, const hsimae_clip_ctl* ctl, void* stream) {
+    return hs_adamw_groups(params, grads, exp_avg, exp_avg_sq, group, group_uniform, n, table, ngroups, beta1, beta2, eps, step, ctl,
+                           S(stream));
+}
 int hsimae_loss_partials(int32_t N, int32_t T) { return hs_loss_partials(N, T); }
 int hsimae_loss(const hsimae_loss_params* p, void* stream) { return p ? hs_loss(*p, S(stream)) : HSIMAE_ENULL; }
 

@@ -9,9 +9,11 @@
 //                       No atomics: the order of every addition is fixed by the grid, so two runs are bit-identical.
 //   clip_finish_kernel  one workgroup: thread t adds partials t, t + 256, ... in order, then the LDS tree of loss_final_kernel;
 //                       thread 0 fills the control block.
-//   adamw_ctl_kernel    adamw_kernel's arithmetic on g * coef (one fp32 multiply), the bias corrections read from the control
-//                       block, nothing written when ctl->apply is 0; any n (float4 body where the four arrays are 16-byte
-//                       aligned, one element per thread behind it), group ids per element or one id for all.
+//   adamw_groups_kernel adamw_kernel's arithmetic on g * coef (one fp32 multiply) with a learning rate and a weight decay PER GROUP
+//                       ID: up to 64 {lr, weight_decay} pairs travel in the launch and are staged into LDS.  With a control block
+//                       the bias corrections are read from it and nothing is written when ctl->apply is 0; without one coef = 1.
+//                       Any n (float4 body where the four arrays are 16-byte aligned, one element per thread behind it), group
+//                       ids per element or one id for all.  hsimae_adamw_step_ctl is this kernel with a two-entry table.
 #include "common.h"
 #include "kernels.h"
 
@@ -105,12 +107,13 @@ __global__ __launch_bounds__(256) void clip_finish_kernel(const double* partials
     if (finite) ctl->norm_max = fmaxf(ctl->norm_max, (float)norm);
 }
 
-// one element of adamw_kernel (elem.hip), its gradient scaled by coef first
-__device__ __forceinline__ void adamw_one(float& p, float g, float& m, float& v, int grp, float lr, float b1, float b2, float eps,
-                                          float wd, float inv_bc1, float inv_sqrt_bc2, float coef) {
+// one element of adamw_kernel (elem.hip), its gradient scaled by coef first, with that element's own lr and weight decay
+// (wd == 0 is "no decay": the multiply is left out, as adamw_kernel leaves it out for id 1)
+__device__ __forceinline__ void adamw_one(float& p, float g, float& m, float& v, float lr, float wd, float b1, float b2, float eps,
+                                          float inv_bc1, float inv_sqrt_bc2, float coef) {
     const float gc = g * coef;
     float x = p;
-    if (grp == 0) x *= 1.f - lr * wd;
+    if (wd != 0.f) x *= 1.f - lr * wd;
     const float mn = m + (gc - m) * (1.f - b1);                                  // lerp, as torch does it
     const float vn = v * b2 + gc * gc * (1.f - b2);
     const float denom = sqrtf(vn) * inv_sqrt_bc2 + eps;
@@ -118,32 +121,54 @@ __device__ __forceinline__ void adamw_one(float& p, float g, float& m, float& v,
     m = mn; v = vn;
 }
 
-__global__ __launch_bounds__(256) void adamw_ctl_kernel(float* p, const float* g, float* m, float* v, const uint8_t* group,
-                                                        int group_uniform, int64_t n, int64_t n4, float lr, float b1, float b2,
-                                                        float eps, float wd, const hsimae_clip_ctl* ctl) {
-    if (ctl->apply == 0) return;                                                // a skipped step writes nothing
-    const float coef = ctl->coef, inv_bc1 = ctl->inv_bc1, inv_sqrt_bc2 = ctl->inv_sqrt_bc2;
+struct GroupTable { hsimae_adamw_group e[HSIMAE_ADAMW_MAX_GROUPS]; };            // by value in the launch: 512 bytes of kernarg
+static_assert(sizeof(GroupTable) == 512, "the table travels as a kernel argument");
+
+// The grouped step.  The table is staged into LDS once per workgroup (64 lanes, one entry each); an element's id indexes it.
+// Id 2 and every id >= ngroups are frozen: never read, never written, so the table is never indexed past ngroups.
+// ctl != NULL: coef, apply and the bias corrections come from the control block; NULL: coef = 1 and the launcher's corrections.
+__global__ __launch_bounds__(256) void adamw_groups_kernel(float* p, const float* g, float* m, float* v, const uint8_t* group,
+                                                           int group_uniform, int64_t n, int64_t n4, int ngroups, GroupTable table,
+                                                           float b1, float b2, float eps, float inv_bc1, float inv_sqrt_bc2,
+                                                           const hsimae_clip_ctl* ctl) {
+    __shared__ float2 tab[HSIMAE_ADAMW_MAX_GROUPS];
+    float coef = 1.f;
+    if (ctl) {                                                                   // uniform
+        if (ctl->apply == 0) return;                                            // a skipped step writes nothing
+        coef = ctl->coef; inv_bc1 = ctl->inv_bc1; inv_sqrt_bc2 = ctl->inv_sqrt_bc2;
+    }
+    if (threadIdx.x < HSIMAE_ADAMW_MAX_GROUPS) {
+        const int k = threadIdx.x < (unsigned)ngroups ? (int)threadIdx.x : 0;   // entries behind ngroups are never used
+        tab[threadIdx.x] = make_float2(table.e[k].lr, table.e[k].weight_decay);
+    }
+    __syncthreads();
     const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
     const unsigned char gu = (unsigned char)group_uniform;
+    const unsigned ng = (unsigned)ngroups;
     for (int64_t i = tid; i < n4; i += stride) {
         const uchar4 gr = group ? reinterpret_cast<const uchar4*>(group)[i] : make_uchar4(gu, gu, gu, gu);
-        if (gr.x == 2 && gr.y == 2 && gr.z == 2 && gr.w == 2) continue;
+        const unsigned char grp[4] = {gr.x, gr.y, gr.z, gr.w};
+        bool live[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) live[e] = grp[e] != 2 && grp[e] < ng;
+        if (!(live[0] || live[1] || live[2] || live[3])) continue;
         float4 P = reinterpret_cast<float4*>(p)[i], M = reinterpret_cast<float4*>(m)[i], V = reinterpret_cast<float4*>(v)[i];
         const float4 G = reinterpret_cast<const float4*>(g)[i];
         float* pp = &P.x; float* mm = &M.x; float* vv = &V.x;
         const float* gg = &G.x;
-        const unsigned char grp[4] = {gr.x, gr.y, gr.z, gr.w};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            if (grp[e] == 2) continue;
-            adamw_one(pp[e], gg[e], mm[e], vv[e], grp[e], lr, b1, b2, eps, wd, inv_bc1, inv_sqrt_bc2, coef);
+            if (!live[e]) continue;
+            const float2 t = tab[grp[e]];
+            adamw_one(pp[e], gg[e], mm[e], vv[e], t.x, t.y, b1, b2, eps, inv_bc1, inv_sqrt_bc2, coef);
         }
         reinterpret_cast<float4*>(p)[i] = P; reinterpret_cast<float4*>(m)[i] = M; reinterpret_cast<float4*>(v)[i] = V;
     }
     for (int64_t e = 4 * n4 + tid; e < n; e += stride) {                        // behind the float4 body (everything when unaligned)
-        const int grp = group ? group[e] : gu;
-        if (grp == 2) continue;
-        adamw_one(p[e], g[e], m[e], v[e], grp, lr, b1, b2, eps, wd, inv_bc1, inv_sqrt_bc2, coef);
+        const unsigned grp = group ? group[e] : gu;
+        if (grp == 2 || grp >= ng) continue;
+        const float2 t = tab[grp];
+        adamw_one(p[e], g[e], m[e], v[e], t.x, t.y, b1, b2, eps, inv_bc1, inv_sqrt_bc2, coef);
     }
 }
 
@@ -172,18 +197,43 @@ int hs_grad_norm(const hsimae_grad_seg* segs, int nseg, float max_norm, int skip
     return (int)hipGetLastError();
 }
 
+int hs_adamw_groups(float* p, const float* g, float* m, float* v, const unsigned char* group, int group_uniform, int64_t n,
+                    const hsimae_adamw_group* table, int ngroups, float b1, float b2, float eps, int step, const hsimae_clip_ctl* ctl,
+                    hipStream_t s) {
+    if (n < 0 || ngroups < 1 || ngroups > HSIMAE_ADAMW_MAX_GROUPS) return HS_EDIMS;
+    if (!group && group_uniform != 2 && (group_uniform < 0 || group_uniform >= ngroups)) return HS_EDIMS;   // 2 is frozen in any table
+    if (!ctl && step < 1) return HS_EDIMS;
+    if (n == 0) return HS_OK;
+    if (!p || !g || !m || !v || !table) return HS_ENULL;
+    GroupTable t;
+    for (int k = 0; k < HSIMAE_ADAMW_MAX_GROUPS; ++k) {
+        t.e[k] = k < ngroups ? table[k] : hsimae_adamw_group{0.f, 0.f};
+        if (k != 2 && !(t.e[k].lr >= 0.f && t.e[k].weight_decay >= 0.f)) return HS_EDIMS;   // negative or NaN; table[2] is ignored
+    }
+    if (misaligned(p, 3) || misaligned(g, 3) || misaligned(m, 3) || misaligned(v, 3) || misaligned(ctl, 7)) return HS_EALIGN;
+    if (!group && group_uniform == 2) return HS_OK;                              // all frozen: nothing to do
+    float inv_bc1 = 0.f, inv_sqrt_bc2 = 0.f;                                     // read from ctl when there is one
+    if (!ctl) {
+        const double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);   // as hs_adamw forms them
+        inv_bc1 = (float)(1.0 / bc1);
+        inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+    }
+    const bool vec = !(misaligned(p, 15) || misaligned(g, 15) || misaligned(m, 15) || misaligned(v, 15) || misaligned(group, 3));
+    const int64_t n4 = vec ? n / 4 : 0, work = vec ? n4 + 3 : n;
+    const int grid = (int)std::min<int64_t>((work + 255) / 256, 2048);
+    hipLaunchKernelGGL(adamw_groups_kernel, dim3(grid), dim3(256), 0, s, p, g, m, v, group, group_uniform, n, n4, ngroups, t, b1, b2,
+                       eps, inv_bc1, inv_sqrt_bc2, ctl);
+    return (int)hipGetLastError();
+}
+
+// hsimae_adamw_step_ctl: the grouped step with the table {(lr, wd), (lr, 0)}
 int hs_adamw_ctl(float* p, const float* g, float* m, float* v, const unsigned char* group, int group_uniform, int64_t n, float lr,
                  float b1, float b2, float eps, float wd, const hsimae_clip_ctl* ctl, hipStream_t s) {
     if (n < 0 || (!group && (group_uniform < 0 || group_uniform > 2))) return HS_EDIMS;
     if (n == 0) return HS_OK;
-    if (!p || !g || !m || !v || !ctl) return HS_ENULL;
-    if (misaligned(p, 3) || misaligned(g, 3) || misaligned(m, 3) || misaligned(v, 3) || misaligned(ctl, 7)) return HS_EALIGN;
-    if (!group && group_uniform == 2) return HS_OK;                              // all frozen: nothing to do
-    const bool vec = !(misaligned(p, 15) || misaligned(g, 15) || misaligned(m, 15) || misaligned(v, 15) || misaligned(group, 3));
-    const int64_t n4 = vec ? n / 4 : 0, work = vec ? n4 + 3 : n;
-    const int grid = (int)std::min<int64_t>((work + 255) / 256, 2048);
-    hipLaunchKernelGGL(adamw_ctl_kernel, dim3(grid), dim3(256), 0, s, p, g, m, v, group, group_uniform, n, n4, lr, b1, b2, eps, wd, ctl);
-    return (int)hipGetLastError();
+    if (!ctl) return HS_ENULL;
+    const hsimae_adamw_group table[2] = {{lr, wd}, {lr, 0.f}};
+    return hs_adamw_groups(p, g, m, v, group, group_uniform, n, table, 2, b1, b2, eps, 1, ctl, s);
 }
 
 HS_UNIT_VARIANT_BITS(clip)

@@ -115,3 +115,6 @@ int hs_grad_norm(const hsimae_grad_seg* segs, int nseg, float max_norm, int skip
                  double* partials, hsimae_clip_ctl* ctl, hipStream_t s);
 int hs_adamw_ctl(float* p, const float* g, float* m, float* v, const unsigned char* group, int group_uniform, int64_t n, float lr,
                  float b1, float b2, float eps, float wd, const hsimae_clip_ctl* ctl, hipStream_t s);
+int hs_adamw_groups(float* p, const float* g, float* m, float* v, const unsigned char* group, int group_uniform, int64_t n,
+                    const hsimae_adamw_group* table, int ngroups, float b1, float b2, float eps, int step, const hsimae_clip_ctl* ctl,
+                    hipStream_t s);

@@ -105,9 +105,11 @@ def scores(gt, pred):
 def dual_branch_finetuning(data_list, labeled_index, unlabeled_data, gt, save_dir, model_name, pretrained=None,
                            lr=1e-3, wd=5e-3, depth=12, dim=144, dec_depth=2, dec_dim=72, s_depth=6,
                            epochs=100, mask_ratio=0.5, lamda=5, batch_size=32, device="cuda:0", log=print,
-                           max_grad_norm=None, skip_nonfinite=False):
+                           max_grad_norm=None, skip_nonfinite=False, layer_decay=None, freeze=()):
     """`max_grad_norm` / `skip_nonfinite` go to FusedAdamW; when either is set every epoch logs the largest gradient norm it saw and
-    the number of steps skipped so far, both read in the epoch's one wait for its losses."""
+    the number of steps skipped so far, both read in the epoch's one wait for its losses.  `layer_decay` / `freeze` go to FusedAdamW
+    too (layer-wise learning-rate decay, name prefixes left out of the step); with `layer_decay` every epoch also logs the smallest
+    and largest effective learning rate it stepped with, from the host's param_groups."""
     device = torch.device(device)
     h, w, c = data_list[0].shape
 
@@ -118,13 +120,14 @@ def dual_branch_finetuning(data_list, labeled_index, unlabeled_data, gt, save_di
                 HSIdataset(va_x, va_y, device=device))
 
     return _finetune(datasets, h, c, gt, save_dir, model_name, pretrained, lr, wd, depth, dim, dec_depth, dec_dim, s_depth, epochs,
-                     mask_ratio, lamda, batch_size, device, log, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+                     mask_ratio, lamda, batch_size, device, log, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite,
+                     layer_decay=layer_decay, freeze=freeze)
 
 
 def dual_branch_finetuning_scene(scene, labeled_index, gt, save_dir, model_name, pretrained=None,
                                  lr=1e-3, wd=5e-3, depth=12, dim=144, dec_depth=2, dec_dim=72, s_depth=6,
                                  epochs=100, mask_ratio=0.5, lamda=5, batch_size=32, device="cuda:0", log=print,
-                                 max_grad_norm=None, skip_nonfinite=False):
+                                 max_grad_norm=None, skip_nonfinite=False, layer_decay=None, freeze=()):
     """`dual_branch_finetuning` from the scene itself: `scene` is the processed [H, W, C] `HSI_data` (get_scene_set_dual's third
     result; a device tensor is used in place), `labeled_index` the labeled pixels r * W + c and `gt` their labels.  The same
     loop, with `data_list[i]` = the padded window of pixel i and `unlabeled_data` = the scene's non-overlapping 9 x 9 tiles,
@@ -147,11 +150,12 @@ def dual_branch_finetuning_scene(scene, labeled_index, gt, save_dir, model_name,
             ds.check()
 
     return _finetune(datasets, 9, c, gt, save_dir, model_name, pretrained, lr, wd, depth, dim, dec_depth, dec_dim, s_depth, epochs,
-                     mask_ratio, lamda, batch_size, device, log, check, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+                     mask_ratio, lamda, batch_size, device, log, check, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite,
+                     layer_decay=layer_decay, freeze=freeze)
 
 
 def _finetune(datasets, h, c, gt, save_dir, model_name, pretrained, lr, wd, depth, dim, dec_depth, dec_dim, s_depth, epochs, mask_ratio,
-              lamda, batch_size, device, log, check_data=None, max_grad_norm=None, skip_nonfinite=False):
+              lamda, batch_size, device, log, check_data=None, max_grad_norm=None, skip_nonfinite=False, layer_decay=None, freeze=()):
     """The loop of Model_Finetuning.py:66-240.  `datasets()` -> (labeled, unlabeled, validation), called where the reference
     splits the labeled set (after the model's initialisation draws); `check_data()` once per epoch, with the loss's check."""
     n_class = int(np.max(gt) + 1)
@@ -167,7 +171,8 @@ def _finetune(datasets, h, c, gt, save_dir, model_name, pretrained, lr, wd, dept
         model_dict.update({k: v for k, v in loaded.items() if k in model_dict})
         model.load_state_dict(model_dict)
 
-    optimizer = FusedAdamW(model, lr=lr, weight_decay=wd, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+    optimizer = FusedAdamW(model, lr=lr, weight_decay=wd, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite,
+                           layer_decay=layer_decay, freeze=freeze)
     clipped = max_grad_norm is not None or skip_nonfinite
     scheduler = CosineLRScheduler(optimizer, t_initial=epochs, lr_min=lr * 0.01, warmup_t=int(np.ceil(0.1 * epochs)),
                                   warmup_lr_init=lr * 0.01)
@@ -187,6 +192,7 @@ def _finetune(datasets, h, c, gt, save_dir, model_name, pretrained, lr, wd, dept
         seed_everything(42 + epoch); labeled_iter = iter(train_dl)              # `stable(loader, 42 + epoch)` twice
         seed_everything(42 + epoch); unlabeled_iter = iter(unl_dl)
         train_loss = torch.zeros((), dtype=torch.float64, device=device)         # summed on the device, read once per epoch
+        lr_lo, lr_hi = optimizer.lr_range()                                     # the scheduler writes once per epoch
         for _ in range(len(train_dl)):
             x, y = next(labeled_iter)
             x_u = next(unlabeled_iter)
@@ -215,6 +221,8 @@ def _finetune(datasets, h, c, gt, save_dir, model_name, pretrained, lr, wd, dept
                 f"{int(skipped)} steps skipped so far")
         else:
             tr, va = torch.stack([train_loss, val_loss]).tolist()               # the epoch's one wait for its losses
+        if layer_decay is not None:
+            log(f"epoch {epoch}: learning rate {lr_lo:.6g} .. {lr_hi:.6g} over {len(optimizer.param_groups)} groups")
         criterion.check()
         if check_data is not None:
             check_data()

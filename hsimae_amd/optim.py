@@ -8,17 +8,53 @@ sharing `lr`) so LR schedulers that write `group['lr']` keep working.
 
 `max_grad_norm` / `skip_nonfinite` (both off by default, and then nothing below changes) put the size of the update under control
 without a host wait: `hsimae_grad_norm` forms the global 2-norm of every gradient that takes part in the step, the clip
-coefficient and the decision to skip a non-finite step in device memory, and `hsimae_adamw_step_ctl` reads them there."""
+coefficient and the decision to skip a non-finite step in device memory, and the step reads them there.
+
+`layer_decay` / `freeze` (both off by default) and `param_groups` whose values differ are honoured by `hsimae_adamw_step_groups`: the
+id byte the kernel already reads per element indexes a table of {lr, weight_decay} pairs that travels in the launch, so the step
+stays one launch however many groups there are, and composes with the clipping above."""
 from __future__ import annotations
+
+import re
 
 import torch
 
 from . import _lib
 
+_BLOCK = re.compile(r"^(blocks_1|blocks_2|blocks)\.(\d+)\.")
+
+
+def layer_ids(model, depth=None, s_depth=None):
+    """{parameter name: layer id} for layer-wise learning-rate decay, the MAE / BEiT convention on this model's names:
+    `patch_embed.*` and `pos_embed` 0; `blocks_1.i.*` and `blocks_2.i.*` 1 + i (the two axis stacks run side by side and share a
+    depth); `blocks.j.*` 1 + s_depth + j; everything else (`norm`, `cls_head`, the decoder, `mask_token`) depth + 1.
+    `model`: an HSIMAE / DualViT / HSIViT, or an iterable of names with `depth` and `s_depth` given."""
+    if hasattr(model, "named_parameters"):
+        names = [n for n, _ in model.named_parameters()]
+        depth = model.depth if depth is None else depth
+        s_depth = model.s_depth if s_depth is None else s_depth
+    else:
+        names = list(model)
+    if depth is None or s_depth is None:
+        raise ValueError("layer_ids: a list of names needs depth and s_depth")
+    depth, s_depth = int(depth), int(s_depth)
+    out = {}
+    for n in names:
+        blk = _BLOCK.match(n)
+        if n == "pos_embed" or n.startswith("patch_embed."):
+            out[n] = 0
+        elif blk:
+            out[n] = 1 + int(blk.group(2)) + (s_depth if blk.group(1) == "blocks" else 0)
+        else:
+            out[n] = depth + 1
+        if out[n] > depth + 1:
+            raise ValueError(f"layer_ids: {n} lies behind depth {depth} (s_depth {s_depth})")
+    return out
+
 
 class FusedAdamW:
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, no_decay=("bias", "norm"), strict=True,
-                 max_grad_norm=None, skip_nonfinite=False):
+                 max_grad_norm=None, skip_nonfinite=False, layer_decay=None, freeze=()):
         """max_grad_norm: clip the global gradient 2-norm to it, with torch.nn.utils.clip_grad_norm_'s coefficient
         min(1, max_norm / (norm + 1e-6)); `float("inf")` only measures.  skip_nonfinite: a step whose norm is Inf or NaN
         changes nothing (no parameter, no moment, no weight decay, no advance of the bias-correction count).
@@ -29,8 +65,22 @@ class FusedAdamW:
         tensors (views of the control block), and reading them from the host is the caller's wait.
 
         Data parallel: the reducer's all-reduce has completed on the stream before `step()` reads the gradients; the norm kernel
-        is launched on the same stream, sees the reduced gradients, and so every rank takes the same decision."""
+        is launched on the same stream, sees the reduced gradients, and so every rank takes the same decision.
+
+        layer_decay: a float in (0, 1]; a parameter of layer id i (`layer_ids`) is stepped with lr * layer_decay ** (depth + 1 - i):
+        the head and the final norm at the full rate, the embedding at the smallest.  `param_groups` then holds one dict per distinct
+        (lr_scale, decays or not) pair, top layer first, each with its own `lr`, `weight_decay` and `lr_scale`; schedulers keep
+        writing `lr`, and `lr_scale` is applied at the step (as MAE's adjust_learning_rate does).
+        freeze: name prefixes; a matching parameter is left out for good, exactly as one with requires_grad=False is: no update, no
+        weight decay, its moments stay zero, and it is not part of the gradient norm.  `freeze` only selects what the optimizer
+        steps: it does NOT shorten the backward pass, the frozen layers' gradients are still computed.
+        Whatever is written into `param_groups` (by hand or by a scheduler with per-group values) is honoured at the next step."""
         self.model = model
+        self.layer_decay = None if layer_decay is None else float(layer_decay)
+        if self.layer_decay is not None and not 0.0 < self.layer_decay <= 1.0:
+            raise ValueError(f"layer_decay must lie in (0, 1] (or be None), got {layer_decay}")
+        self.freeze = (freeze,) if isinstance(freeze, str) else tuple(freeze)
+        self._grouped = self.layer_decay is not None or bool(self.freeze)
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         if self.max_grad_norm is not None and not self.max_grad_norm > 0:
             raise ValueError(f"max_grad_norm must be greater than 0 (or None), got {max_grad_norm}")
@@ -41,41 +91,60 @@ class FusedAdamW:
         self.strict = bool(strict)                   # see _sync_grads
         self._mask_cache = {}
         self.defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay)
-        decay, nodecay = [], []
-        self._groups_of = []
+        # One entry per distinct (lr_scale, decays or not) pair, the two at scale 1 first: they keep the ids 0 / 1 ("decay / no decay"
+        # as hsimae_adamw_step knows them).  Id 2 stays "frozen or absent", so the third entry takes id 3.
+        if self.layer_decay is not None:
+            lids, top = layer_ids(model), int(model.depth) + 1
+            scale_of = lambda n: self.layer_decay ** (top - lids[n])            # noqa: E731
+        else:
+            scale_of = lambda n: 1.0                                            # noqa: E731
         # Parameters that do not live in the model's flat buffer (DualViT's cls_head) are stepped by a stock
-        # torch.optim.AdamW with the same hyper-parameters; their lr follows param_groups[0] / [1].  (Not in the clipped mode.)
+        # torch.optim.AdamW with their group's hyper-parameters, read from param_groups at each step.  (Not in the clipped mode.)
         in_flat = {id(p) for p in model._plist()} if hasattr(model, "_plist") else None
-        extra_decay, extra_nodecay = [], []
+        members = {(1.0, False): [], (1.0, True): []}
+        flat_keys, outside = [], []
         for n, p in model.named_parameters():
-            is_nd = any(k in n for k in no_decay)
+            key = (scale_of(n), any(k in n for k in no_decay))
+            frozen = not p.requires_grad or any(n.startswith(f) for f in self.freeze)
             if in_flat is not None and id(p) not in in_flat:
-                if p.requires_grad:
-                    (extra_nodecay if is_nd else extra_decay).append(p)
-                    (nodecay if is_nd else decay).append(p)
+                if not frozen:
+                    members.setdefault(key, []).append(p)
+                    outside.append((p, key))
                 continue
-            if not p.requires_grad or n == "mask_token":        # mask_token never receives a gradient
-                self._groups_of.append(2)
-            elif is_nd:
-                self._groups_of.append(1); nodecay.append(p)
+            if frozen or n == "mask_token":                     # mask_token never receives a gradient
+                flat_keys.append(None)
             else:
-                self._groups_of.append(0); decay.append(p)
-        self.param_groups = [dict(params=decay, lr=lr, weight_decay=weight_decay, betas=tuple(betas), eps=eps),
-                             dict(params=nodecay, lr=lr, weight_decay=0.0, betas=tuple(betas), eps=eps)]
+                members.setdefault(key, []).append(p)
+                flat_keys.append(key)
+        keys = sorted(members, key=lambda k: (-k[0], k[1]))
+        self._gids = [k if k < 2 else k + 1 for k in range(len(keys))]          # table index of each param_group
+        self._ngroups = self._gids[-1] + 1
+        if self._ngroups > _lib.ADAMW_MAX_GROUPS:
+            raise ValueError(f"FusedAdamW: {len(keys)} parameter groups need {self._ngroups} table entries, "
+                             f"hsimae_adamw_step_groups takes {_lib.ADAMW_MAX_GROUPS}")
+        gid_of = dict(zip(keys, self._gids))
+        self._groups_of = [2 if k is None else gid_of[k] for k in flat_keys]
+        self.param_groups = []
+        for scale, is_nd in keys:
+            g = dict(params=members[(scale, is_nd)], lr=lr, weight_decay=0.0 if is_nd else weight_decay, betas=tuple(betas), eps=eps)
+            if self.layer_decay is not None:
+                g["lr_scale"] = scale
+            self.param_groups.append(g)
         self._extra = None
-        # In the clipped mode the optimizer steps the outside parameters itself (its own moments, hsimae_adamw_step_ctl with
-        # their reference group for every element): a host-side optimizer could not honour a skip decided on the device.
-        self._outside = [(p, 0) for p in extra_decay] + [(p, 1) for p in extra_nodecay] if self._clip else []
+        # In the clipped mode the optimizer steps the outside parameters itself (its own moments, the grouped step with their
+        # group's id for every element): a host-side optimizer could not honour a skip decided on the device.
+        outside.sort(key=lambda pk: gid_of[pk[1]])                # decayed before not, as the stock optimizer's state lists them
+        self._outside = [(p, gid_of[k]) for p, k in outside] if self._clip else []
         self._out_m = [None] * len(self._outside)
         self._out_v = [None] * len(self._outside)
         if len(self._outside) > _lib.CLIP_MAX_SEGS - 1:
             raise NotImplementedError(f"FusedAdamW(max_grad_norm / skip_nonfinite): {len(self._outside)} parameters outside the flat "
                                       f"buffer, one hsimae_grad_norm call takes {_lib.CLIP_MAX_SEGS - 1}")
-        if (extra_decay or extra_nodecay) and not self._clip:
-            groups = [(0, dict(params=extra_decay, weight_decay=weight_decay)), (1, dict(params=extra_nodecay, weight_decay=0.0))]
-            groups = [(i, g) for i, g in groups if g["params"]]
-            self._extra_of = [i for i, _ in groups]          # which reference group each extra group follows
-            self._extra = torch.optim.AdamW([g for _, g in groups], lr=lr, betas=tuple(betas), eps=eps)
+        if outside and not self._clip:
+            self._extra_of = sorted({keys.index(k) for _, k in outside})        # which param_group each extra group follows
+            groups = [dict(params=[p for p, k in outside if keys.index(k) == i], weight_decay=self.param_groups[i]["weight_decay"])
+                      for i in self._extra_of]
+            self._extra = torch.optim.AdamW(groups, lr=lr, betas=tuple(betas), eps=eps)
         self.step_count = 0
         self._flat_id = None
         self.exp_avg = self.exp_avg_sq = self._group = None
@@ -161,6 +230,29 @@ class FusedAdamW:
             self._mask_cache[key] = grp
         return grp
 
+    def _defaults_agree(self):
+        """The two default groups still describe ONE learning rate and weight decay (what hsimae_adamw_step takes)."""
+        if self._grouped or len(self.param_groups) != 2:
+            return False
+        g0, g1 = self.param_groups
+        return (g1["lr"] == g0["lr"] and g1["weight_decay"] == 0 and g0.get("lr_scale", 1.0) == 1.0 and g1.get("lr_scale", 1.0) == 1.0)
+
+    @staticmethod
+    def _effective_lr(g):
+        return float(g["lr"]) * float(g.get("lr_scale", 1.0))      # fp64; rounded once to fp32 where it enters the table
+
+    def lr_range(self):
+        """(smallest, largest) effective learning rate over the groups that hold parameters; host values, no device read."""
+        lrs = [self._effective_lr(g) for g in self.param_groups if g["params"]] or [self._effective_lr(self.param_groups[0])]
+        return min(lrs), max(lrs)
+
+    def _table(self):
+        """param_groups as hsimae_adamw_step_groups takes them: entry id = {lr * lr_scale, weight_decay}; id 2 is the hole."""
+        table = (_lib.AdamWGroup * self._ngroups)()
+        for g, gid in zip(self.param_groups, self._gids):
+            table[gid] = _lib.AdamWGroup(self._effective_lr(g), float(g["weight_decay"]))
+        return table
+
     @torch.no_grad()
     def step(self):
         self._bind()
@@ -174,14 +266,21 @@ class FusedAdamW:
             self._step_clipped(group, float(b1), float(b2), stream)
             m._packed_version = -1
             return
-        _lib.check(_lib.load().hsimae_adamw_step(
-            m._flat.data_ptr(), m._flat_grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-            group.data_ptr(), m._flat.numel(), float(g0["lr"]), float(b1), float(b2), float(g0["eps"]),
-            float(g0["weight_decay"]), self.step_count, stream), "hsimae_adamw_step")
+        if self._defaults_agree():
+            _lib.check(_lib.load().hsimae_adamw_step(
+                m._flat.data_ptr(), m._flat_grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
+                group.data_ptr(), m._flat.numel(), float(g0["lr"]), float(b1), float(b2), float(g0["eps"]),
+                float(g0["weight_decay"]), self.step_count, stream), "hsimae_adamw_step")
+        else:
+            _lib.check(_lib.load().hsimae_adamw_step_groups(
+                m._flat.data_ptr(), m._flat_grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
+                group.data_ptr(), 0, m._flat.numel(), self._table(), self._ngroups, float(b1), float(b2), float(g0["eps"]),
+                self.step_count, None, stream), "hsimae_adamw_step_groups")
         m._packed_version = -1                    # packed bf16 images are stale now
         if self._extra is not None:
             for ge, gi in zip(self._extra.param_groups, self._extra_of):
-                ge["lr"] = self.param_groups[gi]["lr"]
+                ge["lr"] = self._effective_lr(self.param_groups[gi])
+                ge["weight_decay"] = self.param_groups[gi]["weight_decay"]
             self._extra.step()
 
     # ------------------------------------------------------------------ gradient norm / clipping / skip (off by default)
@@ -254,14 +353,14 @@ class FusedAdamW:
         ctl = self._ctl.data_ptr()
         _lib.check(lib.hsimae_grad_norm(segs, 1 + len(live), max_norm, int(self.skip_nonfinite), self.step_count, b1, b2,
                                         self._partials.data_ptr(), ctl, stream), "hsimae_grad_norm")
-        _lib.check(lib.hsimae_adamw_step_ctl(
+        table, ng, eps = self._table(), self._ngroups, float(g0["eps"])
+        _lib.check(lib.hsimae_adamw_step_groups(
             flat.data_ptr(), m._flat_grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), group.data_ptr(), 0,
-            flat.numel(), float(g0["lr"]), b1, b2, float(g0["eps"]), float(g0["weight_decay"]), ctl, stream), "hsimae_adamw_step_ctl")
+            flat.numel(), table, ng, b1, b2, eps, self.step_count, ctl, stream), "hsimae_adamw_step_groups")
         for k, p, g, gid in live:
-            _lib.check(lib.hsimae_adamw_step_ctl(
+            _lib.check(lib.hsimae_adamw_step_groups(
                 p.data_ptr(), g.data_ptr(), self._out_m[k].data_ptr(), self._out_v[k].data_ptr(), None, gid, p.numel(),
-                float(self.param_groups[gid]["lr"]), b1, b2, float(g0["eps"]), float(g0["weight_decay"]), ctl, stream),
-                "hsimae_adamw_step_ctl")
+                table, ng, b1, b2, eps, self.step_count, ctl, stream), "hsimae_adamw_step_groups")
 
     def state_dict(self):
         sd = {"step": self.step_count, "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq,
@@ -274,6 +373,9 @@ class FusedAdamW:
         return sd
 
     def load_state_dict(self, sd):
+        if len(sd["param_groups"]) != len(self.param_groups):
+            raise ValueError(f"checkpoint carries {len(sd['param_groups'])} parameter groups, this optimizer has {len(self.param_groups)} "
+                             "(built with another layer_decay / freeze, or for another depth)")
         self.step_count = int(sd["step"])
         self.exp_avg, self.exp_avg_sq = sd["exp_avg"], sd["exp_avg_sq"]
         for g, s in zip(self.param_groups, sd["param_groups"]):

@@ -676,6 +676,33 @@ int hsimae_adamw_step_ctl(float* params, const float* grads, float* exp_avg, flo
                           int32_t group_uniform, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
                           const hsimae_clip_ctl* ctl, void* stream);
 
+/* ------------------------------------------------------------------ AdamW with a learning rate and a weight decay per group id
+ * (what torch.optim.AdamW does with one param_group per layer: layer-wise learning-rate decay, a head stepped faster than the
+ * encoder, frozen layers), still ONE launch over the flat buffer and no host wait.
+ * ADDED under HSIMAE_VERSION 108 like the entry points above: nothing that 108 already had changes; hsimae_adamw_step is as it
+ * was, and hsimae_adamw_step_ctl is this entry point with the two-entry table {(lr, weight_decay), (lr, 0)}.
+ *
+ * hsimae_adamw_step_groups: an element's id (one byte per element in `group`; group NULL: every element has `group_uniform`)
+ *   indexes `table` directly, and the element is stepped with table[id].lr and table[id].weight_decay by hsimae_adamw_step's
+ *   arithmetic; the decay multiply is applied when weight_decay != 0.  Id 2 keeps its meaning: frozen or absent, never read,
+ *   never written, left out of hsimae_grad_norm; table[2] is ignored.  An id >= ngroups found in device memory is treated as
+ *   frozen too: the table is never indexed past ngroups.  `table` is HOST memory and is copied into the launch (512 bytes of
+ *   kernel argument, staged into LDS once per workgroup): the caller need not keep it alive.
+ *   ctl != NULL: the gradient is multiplied by ctl->coef, the bias corrections are read from ctl and nothing is written when
+ *   ctl->apply is 0, exactly as hsimae_adamw_step_ctl does; `step` is ignored.  ctl == NULL: coef = 1 and the bias corrections
+ *   are formed on the host from `step` (fp64 pow, rounded to fp32), as hsimae_adamw_step forms them.
+ *   Any n >= 0 and any 4-byte alignment (16-byte loads when all four arrays are 16-byte and `group` 4-byte aligned).
+ *   Refusals, before any launch: n < 0, ngroups outside 1 .. HSIMAE_ADAMW_MAX_GROUPS, group NULL with group_uniform neither 2
+ *   nor inside 0 .. ngroups - 1, ctl NULL with step < 1, an lr or weight_decay (other than table[2]'s) that is negative or NaN
+ *   -> HSIMAE_EDIMS; a NULL array or table with n > 0 -> HSIMAE_ENULL; an array not 4-byte or ctl not 8-byte aligned ->
+ *   HSIMAE_EALIGN.  n == 0, or a uniform id of 2: HSIMAE_OK and no launch. */
+#define HSIMAE_ADAMW_MAX_GROUPS 64
+typedef struct { float lr; float weight_decay; } hsimae_adamw_group;
+int hsimae_adamw_step_groups(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* group,
+                             int32_t group_uniform, int64_t n, const hsimae_adamw_group* table /* host */, int32_t ngroups,
+                             float beta1, float beta2, float eps, int32_t step, const hsimae_clip_ctl* ctl /* device, may be NULL */,
+                             void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
