@@ -14,7 +14,7 @@ if not _os.environ.get("HSIMAE_KEEP_HW_QUEUES"):
     _os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 from .model import HSIMAE, swiglu_hidden, sincos_table  # noqa: F401
-from .optim import FusedAdamW  # noqa: F401
+from .optim import FusedAdamW, FusedLAMB  # noqa: F401
 from .data import HSIdataset4PT, DeviceLoader  # noqa: F401
 from .sched import CosineLRScheduler  # noqa: F401
 from .pretrain import mask_pretraining  # noqa: F401

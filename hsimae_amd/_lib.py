@@ -154,9 +154,15 @@ class AdamWGroup(C.Structure):
     _fields_ = [("lr", f32), ("weight_decay", f32)]
 
 
+class LambTensor(C.Structure):
+    """hsimae_lamb_tensor: one entry of hsimae_lamb_step's tensor table (DEVICE memory, built on the host and uploaded once)."""
+    _fields_ = [("off", i64), ("n", i64), ("chunk0", i32), ("reserved", i32)]
+
+
 ADAMW_MAX_GROUPS = 64   # HSIMAE_ADAMW_MAX_GROUPS
 CLIP_GRID = 1024        # HSIMAE_CLIP_GRID: doubles of scratch hsimae_grad_norm needs in `partials`
 CLIP_MAX_SEGS = 8       # HSIMAE_CLIP_MAX_SEGS
+LAMB_CHUNK = 4096       # HSIMAE_LAMB_CHUNK: floats of one tensor behind one workgroup of hsimae_lamb_step
 
 
 class BuildInfo(C.Structure):
@@ -210,6 +216,8 @@ SYMBOLS = {
     "hsimae_grad_norm": (C.c_int, [C.POINTER(GradSeg), i32, f32, i32, i32, f32, f32, vp, vp, vp]),
     "hsimae_adamw_step_ctl": (C.c_int, [vp, vp, vp, vp, vp, i32, i64, f32, f32, f32, f32, f32, vp, vp]),
     "hsimae_adamw_step_groups": (C.c_int, [vp, vp, vp, vp, vp, i32, i64, C.POINTER(AdamWGroup), i32, f32, f32, f32, i32, vp, vp]),
+    "hsimae_lamb_step": (C.c_int, [vp, vp, vp, vp, vp, i32, i64, vp, i32, i32, C.POINTER(AdamWGroup), i32, f32, f32, f32, f32, i32,
+                                   vp, vp, vp, vp, vp]),
     "hsimae_cube_gather": (C.c_int, [C.POINTER(CubeParams), vp]),
     "hsimae_scene_windows": (C.c_int, [C.POINTER(SceneParams), vp]),
     "hsimae_class_argmax": (C.c_int, [C.POINTER(SceneParams), vp, i32, i32, i32, vp, vp]),

@@ -422,6 +422,7 @@ extern "C" unsigned hs_variant_bits_scene();
 extern "C" unsigned hs_variant_bits_gwpca();
 extern "C" unsigned hs_variant_bits_cls();
 extern "C" unsigned hs_variant_bits_clip();
+extern "C" unsigned hs_variant_bits_lamb();
 #ifndef HS_KERNEL_SOURCE_HASH
 #define HS_KERNEL_SOURCE_HASH 0ULL
 #endif
@@ -439,7 +440,7 @@ int hsimae_version(void) { return HSIMAE_VERSION; }
 int hsimae_build_info(hsimae_build_info_t* out) {
     if (!out) return HSIMAE_ENULL;
     out->abi_version = HSIMAE_VERSION;
-    out->variant_bits = hs_variant_bits() | hs_variant_bits_gemm() | hs_variant_bits_attn() | hs_variant_bits_attn_wide() | hs_variant_bits_wgrad() | hs_variant_bits_elem() | hs_variant_bits_pack() | hs_variant_bits_fused_dec() | hs_variant_bits_fused_enc() | hs_variant_bits_loader() | hs_variant_bits_scene() | hs_variant_bits_gwpca() | hs_variant_bits_cls() | hs_variant_bits_clip();
+    out->variant_bits = hs_variant_bits() | hs_variant_bits_gemm() | hs_variant_bits_attn() | hs_variant_bits_attn_wide() | hs_variant_bits_wgrad() | hs_variant_bits_elem() | hs_variant_bits_pack() | hs_variant_bits_fused_dec() | hs_variant_bits_fused_enc() | hs_variant_bits_loader() | hs_variant_bits_scene() | hs_variant_bits_gwpca() | hs_variant_bits_cls() | hs_variant_bits_clip() | hs_variant_bits_lamb();
     out->kernel_source_hash = HS_KERNEL_SOURCE_HASH;
     out->flags_hash = HS_BUILD_FLAGS_HASH;
     out->default_flags = HS_BUILD_DEFAULT_FLAGS;
@@ -1006,6 +1007,13 @@ int hsimae_adamw_step_groups(float* params, const float* grads, float* exp_avg, 
                              float beta2, float eps, int32_t step, const hsimae_clip_ctl* ctl, void* stream) {
     return hs_adamw_groups(params, grads, exp_avg, exp_avg_sq, group, group_uniform, n, table, ngroups, beta1, beta2, eps, step, ctl,
                            S(stream));
+}
+int hsimae_lamb_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* group,
+                     int32_t group_uniform, int64_t n, const hsimae_lamb_tensor* tensors, int32_t ntensors, int32_t nchunks,
+                     const hsimae_adamw_group* table, int32_t ngroups, float beta1, float beta2, float eps, float trust_clip,
+                     int32_t always_adapt, double* partials, float* ratios, int32_t* bad, const hsimae_clip_ctl* ctl, void* stream) {
+    return hs_lamb_step(params, grads, exp_avg, exp_avg_sq, group, group_uniform, n, tensors, ntensors, nchunks, table, ngroups, beta1,
+                        beta2, eps, trust_clip, always_adapt, partials, ratios, bad, ctl, S(stream));
 }
 int hsimae_loss_partials(int32_t N, int32_t T) { return hs_loss_partials(N, T); }
 int hsimae_loss(const hsimae_loss_params* p, void* stream) { return p ? hs_loss(*p, S(stream)) : HSIMAE_ENULL; }

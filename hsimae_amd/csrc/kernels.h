@@ -118,3 +118,8 @@ int hs_adamw_ctl(float* p, const float* g, float* m, float* v, const unsigned ch
 int hs_adamw_groups(float* p, const float* g, float* m, float* v, const unsigned char* group, int group_uniform, int64_t n,
                     const hsimae_adamw_group* table, int ngroups, float b1, float b2, float eps, int step, const hsimae_clip_ctl* ctl,
                     hipStream_t s);
+// lamb.hip: LAMB's per-tensor trust ratios and step over the flat buffer (moments + partial sums, ratios, apply)
+int hs_lamb_step(float* p, const float* g, float* m, float* v, const unsigned char* group, int group_uniform, int64_t n,
+                 const hsimae_lamb_tensor* tensors, int ntensors, int nchunks, const hsimae_adamw_group* table, int ngroups, float b1,
+                 float b2, float eps, float trust_clip, int always_adapt, double* partials, float* ratios, int* bad,
+                 const hsimae_clip_ctl* ctl, hipStream_t s);

@@ -27,7 +27,7 @@ from . import _lib
 from .classify import ClassLoss, ScoreMeter
 from .data import DeviceLoader
 from .finetune import DualViT, HSIViT
-from .optim import FusedAdamW
+from .optim import FusedAdamW, FusedLAMB
 from .pretrain import seed_everything
 from .scene_data import SceneCubes, device_scene, unlabeled_pixels
 from .sched import CosineLRScheduler
@@ -105,11 +105,13 @@ def scores(gt, pred):
 def dual_branch_finetuning(data_list, labeled_index, unlabeled_data, gt, save_dir, model_name, pretrained=None,
                            lr=1e-3, wd=5e-3, depth=12, dim=144, dec_depth=2, dec_dim=72, s_depth=6,
                            epochs=100, mask_ratio=0.5, lamda=5, batch_size=32, device="cuda:0", log=print,
-                           max_grad_norm=None, skip_nonfinite=False, layer_decay=None, freeze=()):
+                           max_grad_norm=None, skip_nonfinite=False, layer_decay=None, freeze=(), optimizer="adamw"):
     """`max_grad_norm` / `skip_nonfinite` go to FusedAdamW; when either is set every epoch logs the largest gradient norm it saw and
     the number of steps skipped so far, both read in the epoch's one wait for its losses.  `layer_decay` / `freeze` go to FusedAdamW
     too (layer-wise learning-rate decay, name prefixes left out of the step); with `layer_decay` every epoch also logs the smallest
-    and largest effective learning rate it stepped with, from the host's param_groups."""
+    and largest effective learning rate it stepped with, from the host's param_groups.  `optimizer`: "adamw" (the default) or
+    "lamb": FusedLAMB with the same arguments and max_grad_norm 1.0 where it was left None; every epoch then also logs the smallest
+    and largest trust ratio among the adapted tensors, in the same wait."""
     device = torch.device(device)
     h, w, c = data_list[0].shape
 
@@ -121,13 +123,13 @@ def dual_branch_finetuning(data_list, labeled_index, unlabeled_data, gt, save_di
 
     return _finetune(datasets, h, c, gt, save_dir, model_name, pretrained, lr, wd, depth, dim, dec_depth, dec_dim, s_depth, epochs,
                      mask_ratio, lamda, batch_size, device, log, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite,
-                     layer_decay=layer_decay, freeze=freeze)
+                     layer_decay=layer_decay, freeze=freeze, optimizer=optimizer)
 
 
 def dual_branch_finetuning_scene(scene, labeled_index, gt, save_dir, model_name, pretrained=None,
                                  lr=1e-3, wd=5e-3, depth=12, dim=144, dec_depth=2, dec_dim=72, s_depth=6,
                                  epochs=100, mask_ratio=0.5, lamda=5, batch_size=32, device="cuda:0", log=print,
-                                 max_grad_norm=None, skip_nonfinite=False, layer_decay=None, freeze=()):
+                                 max_grad_norm=None, skip_nonfinite=False, layer_decay=None, freeze=(), optimizer="adamw"):
     """`dual_branch_finetuning` from the scene itself: `scene` is the processed [H, W, C] `HSI_data` (get_scene_set_dual's third
     result; a device tensor is used in place), `labeled_index` the labeled pixels r * W + c and `gt` their labels.  The same
     loop, with `data_list[i]` = the padded window of pixel i and `unlabeled_data` = the scene's non-overlapping 9 x 9 tiles,
@@ -151,11 +153,11 @@ def dual_branch_finetuning_scene(scene, labeled_index, gt, save_dir, model_name,
 
     return _finetune(datasets, 9, c, gt, save_dir, model_name, pretrained, lr, wd, depth, dim, dec_depth, dec_dim, s_depth, epochs,
                      mask_ratio, lamda, batch_size, device, log, check, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite,
-                     layer_decay=layer_decay, freeze=freeze)
+                     layer_decay=layer_decay, freeze=freeze, optimizer=optimizer)
 
 
 def _finetune(datasets, h, c, gt, save_dir, model_name, pretrained, lr, wd, depth, dim, dec_depth, dec_dim, s_depth, epochs, mask_ratio,
-              lamda, batch_size, device, log, check_data=None, max_grad_norm=None, skip_nonfinite=False, layer_decay=None, freeze=()):
+              lamda, batch_size, device, log, check_data=None, max_grad_norm=None, skip_nonfinite=False, layer_decay=None, freeze=(), optimizer="adamw"):
     """The loop of Model_Finetuning.py:66-240.  `datasets()` -> (labeled, unlabeled, validation), called where the reference
     splits the labeled set (after the model's initialisation draws); `check_data()` once per epoch, with the loss's check."""
     n_class = int(np.max(gt) + 1)
@@ -171,9 +173,16 @@ def _finetune(datasets, h, c, gt, save_dir, model_name, pretrained, lr, wd, dept
         model_dict.update({k: v for k, v in loaded.items() if k in model_dict})
         model.load_state_dict(model_dict)
 
-    optimizer = FusedAdamW(model, lr=lr, weight_decay=wd, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite,
-                           layer_decay=layer_decay, freeze=freeze)
-    clipped = max_grad_norm is not None or skip_nonfinite
+    if optimizer not in ("adamw", "lamb"):
+        raise ValueError(f'optimizer must be "adamw" or "lamb", got {optimizer!r}')
+    lamb = optimizer == "lamb"
+    if lamb:
+        optimizer = FusedLAMB(model, lr=lr, weight_decay=wd, max_grad_norm=1.0 if max_grad_norm is None else max_grad_norm,
+                              skip_nonfinite=skip_nonfinite, layer_decay=layer_decay, freeze=freeze)
+    else:
+        optimizer = FusedAdamW(model, lr=lr, weight_decay=wd, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite,
+                               layer_decay=layer_decay, freeze=freeze)
+    clipped = max_grad_norm is not None or skip_nonfinite or lamb
     scheduler = CosineLRScheduler(optimizer, t_initial=epochs, lr_min=lr * 0.01, warmup_t=int(np.ceil(0.1 * epochs)),
                                   warmup_lr_init=lr * 0.01)
     criterion = ClassLoss(ignore_index=0)
@@ -214,11 +223,14 @@ def _finetune(datasets, h, c, gt, save_dir, model_name, pretrained, lr, wd, dept
                 meter.update(y, criterion.last_pred)
         val_value = list(meter.compute())
         if clipped:                                                             # the same wait also brings the norm and the count
-            tr, va, norm_max, skipped = torch.stack([train_loss, val_loss, optimizer.grad_norm_max.double(),
-                                                     optimizer.skipped_steps.double()]).tolist()
+            read = torch.stack([train_loss, val_loss, optimizer.grad_norm_max.double(), optimizer.skipped_steps.double()])
+            if lamb:
+                read = torch.cat([read, optimizer.trust_ratio_range()])
+            vals = read.tolist()                                                # the epoch's one wait
+            tr, va, norm_max, skipped = vals[:4]
             optimizer.reset_grad_norm_max()
             log(f"epoch {epoch}: train loss {tr / len(train_dl):.6f}, largest gradient norm {norm_max:.6g}, "
-                f"{int(skipped)} steps skipped so far")
+                f"{int(skipped)} steps skipped so far" + (f", trust ratio {vals[4]:.6g} .. {vals[5]:.6g}" if lamb else ""))
         else:
             tr, va = torch.stack([train_loss, val_loss]).tolist()               # the epoch's one wait for its losses
         if layer_decay is not None:

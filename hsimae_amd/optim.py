@@ -12,11 +12,15 @@ coefficient and the decision to skip a non-finite step in device memory, and the
 
 `layer_decay` / `freeze` (both off by default) and `param_groups` whose values differ are honoured by `hsimae_adamw_step_groups`: the
 id byte the kernel already reads per element indexes a table of {lr, weight_decay} pairs that travels in the launch, so the step
-stays one launch however many groups there are, and composes with the clipping above."""
+stays one launch however many groups there are, and composes with the clipping above.
+
+`FusedLAMB` (below) is the large-batch variant: the same buffers, ids, table and control block, with Adam's update scaled per parameter
+tensor by |w| / |update| (`hsimae_lamb_step`, csrc/lamb.hip)."""
 from __future__ import annotations
 
 import re
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -327,7 +331,9 @@ class FusedAdamW:
     def reset_grad_norm_max(self):
         self._ensure_ctl()["norm_max"].zero_()
 
-    def _step_clipped(self, group, b1, b2, stream):
+    def _grad_norm(self, group, b1, b2, stream):
+        """hsimae_grad_norm over the flat gradient buffer and the `.grad` of the live parameters outside it; fills the control block.
+        Returns those parameters as [(index into _outside, parameter, contiguous fp32 gradient, group id)], their moments in place."""
         m, lib = self.model, _lib.load()
         flat = m._flat
         self._ensure_ctl(flat.device)
@@ -341,18 +347,24 @@ class FusedAdamW:
             if g.dtype != torch.float32 or not g.is_contiguous():
                 g = g.float().contiguous()
             if not p.is_contiguous() or p.dtype != torch.float32:
-                raise RuntimeError("FusedAdamW: a parameter outside the flat buffer must be a contiguous fp32 tensor")
+                raise RuntimeError(f"{type(self).__name__}: a parameter outside the flat buffer must be a contiguous fp32 tensor")
             if self._out_m[k] is None or self._out_m[k].device != p.device:
                 z = torch.zeros(p.numel(), dtype=torch.float32, device=p.device)
                 self._out_m[k] = z if self._out_m[k] is None else self._out_m[k].to(p.device)
                 self._out_v[k] = z.clone() if self._out_v[k] is None else self._out_v[k].to(p.device)
             live.append((k, p, g, gid))
             segs[len(live)] = _lib.GradSeg(g.data_ptr(), None, g.numel())
-        g0 = self.param_groups[0]
         max_norm = float("inf") if self.max_grad_norm is None else self.max_grad_norm
-        ctl = self._ctl.data_ptr()
         _lib.check(lib.hsimae_grad_norm(segs, 1 + len(live), max_norm, int(self.skip_nonfinite), self.step_count, b1, b2,
-                                        self._partials.data_ptr(), ctl, stream), "hsimae_grad_norm")
+                                        self._partials.data_ptr(), self._ctl.data_ptr(), stream), "hsimae_grad_norm")
+        return live
+
+    def _step_clipped(self, group, b1, b2, stream):
+        m, lib = self.model, _lib.load()
+        flat = m._flat
+        live = self._grad_norm(group, b1, b2, stream)
+        g0 = self.param_groups[0]
+        ctl = self._ctl.data_ptr()
         table, ng, eps = self._table(), self._ngroups, float(g0["eps"])
         _lib.check(lib.hsimae_adamw_step_groups(
             flat.data_ptr(), m._flat_grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), group.data_ptr(), 0,
@@ -372,7 +384,12 @@ class FusedAdamW:
             sd["outside_exp_avg"], sd["outside_exp_avg_sq"] = list(self._out_m), list(self._out_v)
         return sd
 
+    _KIND = "adamw"                                  # what state_dict()["optimizer"] names; a checkpoint without the key is AdamW's
+
     def load_state_dict(self, sd):
+        kind = sd.get("optimizer", "adamw")
+        if kind != self._KIND:
+            raise ValueError(f"checkpoint was written by the {kind} optimizer, this one is {self._KIND}: its moments mean something else")
         if len(sd["param_groups"]) != len(self.param_groups):
             raise ValueError(f"checkpoint carries {len(sd['param_groups'])} parameter groups, this optimizer has {len(self.param_groups)} "
                              "(built with another layer_decay / freeze, or for another depth)")
@@ -408,3 +425,143 @@ class FusedAdamW:
                 if st is not None and "exp_avg" in st:
                     self._out_m[k] = st["exp_avg"].detach().float().reshape(-1).clone()
                     self._out_v[k] = st["exp_avg_sq"].detach().float().reshape(-1).clone()
+
+
+# ---------------------------------------------------------------------------------------------------------------------- LAMB
+def lamb_tensor_table(offs, sizes):
+    """The tensor table of hsimae_lamb_step for tensors at `offs` with `sizes` floats: (rows, nchunks).  rows is a numpy record
+    array laid out as hsimae_lamb_tensor {off, n, chunk0, reserved}; chunk0 is the prefix sum of ceil(size / HSIMAE_LAMB_CHUNK)."""
+    offs, sizes = np.asarray(offs, dtype=np.int64), np.asarray(sizes, dtype=np.int64)
+    per = (sizes + _lib.LAMB_CHUNK - 1) // _lib.LAMB_CHUNK
+    ends = np.cumsum(per)
+    nchunks = int(ends[-1]) if len(ends) else 0
+    if nchunks >= 2 ** 31:
+        raise ValueError(f"{nchunks} chunks do not fit hsimae_lamb_tensor.chunk0")
+    rows = np.zeros(len(offs), dtype=np.dtype([("off", "<i8"), ("n", "<i8"), ("chunk0", "<i4"), ("reserved", "<i4")]))
+    assert rows.dtype.itemsize == _lib.C.sizeof(_lib.LambTensor)
+    rows["off"], rows["n"], rows["chunk0"] = offs, sizes, ends - per
+    return rows, nchunks
+
+
+class FusedLAMB(FusedAdamW):
+    """LAMB (You et al., "Large Batch Optimization for Deep Learning", 2020; apex FusedLAMB, timm Lamb) on FusedAdamW's buffers:
+    Adam's update u = m_hat / (sqrt(v_hat) + eps) + weight_decay * p, applied as p -= lr * r * u with one trust ratio
+    r = |p| / |u| per parameter tensor (1 where either norm is 0).  With every r = 1 it is AdamW's step.
+
+    max_grad_norm: as FusedAdamW's (the clip happens inside the step); None only measures the norm.  The gradient norm is always
+    formed: the step reads the clip coefficient, the skip decision and the bias corrections from the device-side control block.
+    trust_clip: an upper bound on r (timm's trust_clip=True is trust_clip=1.0); None: no bound.
+    always_adapt: False leaves tensors whose weight decay is 0 (biases, norms) at r = 1, as timm does.
+    layer_decay / freeze / param_groups / skip_nonfinite / strict: FusedAdamW's.
+
+    step() is hsimae_grad_norm (two launches) and hsimae_lamb_step (three) over the flat buffer, then one hsimae_lamb_step per
+    live parameter outside it (DualViT's head); no ATen op, no host wait.  `trust_ratios` holds the last applied step's ratios."""
+    _KIND = "lamb"
+
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, no_decay=("bias", "norm"), strict=True,
+                 max_grad_norm=1.0, skip_nonfinite=False, layer_decay=None, freeze=(), trust_clip=None, always_adapt=False):
+        if max_grad_norm is not None and not float(max_grad_norm) > 0:
+            raise ValueError(f"max_grad_norm must be greater than 0 (or None), got {max_grad_norm}")
+        # the parent in its clipped mode (it owns the outside parameters' moments and the control block); inf only measures
+        super().__init__(model, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, no_decay=no_decay, strict=strict,
+                         max_grad_norm=float("inf") if max_grad_norm is None else max_grad_norm, skip_nonfinite=skip_nonfinite,
+                         layer_decay=layer_decay, freeze=freeze)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.trust_clip = None if trust_clip is None else float(trust_clip)
+        if self.trust_clip is not None and not self.trust_clip > 0:
+            raise ValueError(f"trust_clip must be greater than 0 (or None), got {trust_clip}")
+        self.always_adapt = bool(always_adapt)
+        in_flat = {id(p) for p in model._plist()} if hasattr(model, "_plist") else None
+        self.trust_ratio_names = [n for n, p in model.named_parameters() if in_flat is None or id(p) in in_flat]
+        self._lamb_id = None
+        self._tensors = self._lamb_partials = self._ratios = self._bad = None
+        self._out_tab = [None] * len(self._outside)                # per outside parameter: (table, nchunks, partials)
+        self._out_ratios = None
+
+    def _bind(self):
+        super()._bind()
+        flat = self.model._flat
+        if self._lamb_id != flat.data_ptr():
+            rows, self._nchunks = lamb_tensor_table(self.model._offs, self.model._sizes)
+            self._tensors = torch.from_numpy(rows.view(np.uint8).copy()).to(flat.device)      # one upload
+            self._ntensors = len(rows)
+            self._lamb_partials = torch.zeros(2 * self._nchunks, dtype=torch.float64, device=flat.device)
+            if self._ratios is None or self._ratios.numel() != self._ntensors:
+                self._ratios = torch.ones(self._ntensors, dtype=torch.float32, device=flat.device)
+            else:
+                self._ratios = self._ratios.to(flat.device)
+            if self._bad is None:
+                self._bad = torch.zeros((), dtype=torch.int32, device=flat.device)
+            else:
+                self._bad = self._bad.to(flat.device)
+            if self._out_ratios is None:
+                self._out_ratios = torch.ones(len(self._outside), dtype=torch.float32, device=flat.device)
+            self._lamb_id = flat.data_ptr()
+
+    @property
+    def trust_ratios(self):
+        """One fp32 trust ratio per tensor of the flat buffer (`trust_ratio_names` order), as the last applied step used them; 1 for
+        a tensor that is frozen or not adapted (device tensor; reading it from the host is the caller's wait)."""
+        self._bind()
+        return self._ratios
+
+    @property
+    def trust_ratios_outside(self):
+        """The ratios of the parameters outside the flat buffer (DualViT's cls_head.weight, cls_head.bias), in that order."""
+        self._bind()
+        return self._out_ratios
+
+    @property
+    def table_error(self):
+        """0-d int32 device tensor: not 0 once a step has met an inconsistent tensor table (hsimae_lamb_step's `bad`)."""
+        self._bind()
+        return self._bad
+
+    def adapted(self):
+        """Host list of bool per flat tensor: does the step form a trust ratio for it (live, and decayed or always_adapt)."""
+        wd = {gid: float(g["weight_decay"]) for g, gid in zip(self.param_groups, self._gids)}
+        return [gid != 2 and (self.always_adapt or wd[gid] != 0.0) for gid in self._groups_of]
+
+    def trust_ratio_range(self):
+        """(smallest, largest) trust ratio among the adapted tensors of the flat buffer, a 2-element fp64 device tensor (not part of
+        step(): the loops call it once per epoch, in their one device read)."""
+        r = self.trust_ratios
+        sel = torch.tensor(self.adapted(), dtype=torch.bool, device=r.device)
+        r = r[sel].double()
+        return torch.stack([r.min(), r.max()]) if r.numel() else torch.ones(2, dtype=torch.float64, device=self._ratios.device)
+
+    @torch.no_grad()
+    def step(self):
+        self._bind()
+        m, lib = self.model, _lib.load()
+        flat = m._flat
+        g0 = self.param_groups[0]
+        self.step_count += 1
+        b1, b2, eps = float(g0["betas"][0]), float(g0["betas"][1]), float(g0["eps"])
+        stream = torch.cuda.current_stream(flat.device).cuda_stream
+        group = self._sync_grads()
+        live = self._grad_norm(group, b1, b2, stream)
+        for k, p, g, gid in live:                                  # a one-tensor table per live parameter outside the flat buffer
+            if self._out_tab[k] is None or self._out_tab[k][0].device != p.device:
+                rows, nch = lamb_tensor_table([0], [p.numel()])
+                self._out_tab[k] = (torch.from_numpy(rows.view(np.uint8).copy()).to(p.device), nch,
+                                    torch.zeros(2 * nch, dtype=torch.float64, device=p.device))
+        ctl = self._ctl.data_ptr()
+        table, ng = self._table(), self._ngroups
+        clip, adapt, bad = (self.trust_clip or 0.0), int(self.always_adapt), self._bad.data_ptr()
+        _lib.check(lib.hsimae_lamb_step(
+            flat.data_ptr(), m._flat_grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), group.data_ptr(), 0,
+            flat.numel(), self._tensors.data_ptr(), self._ntensors, self._nchunks, table, ng, b1, b2, eps, clip, adapt,
+            self._lamb_partials.data_ptr(), self._ratios.data_ptr(), bad, ctl, stream), "hsimae_lamb_step")
+        for k, p, g, gid in live:
+            tab, nch, part = self._out_tab[k]
+            _lib.check(lib.hsimae_lamb_step(
+                p.data_ptr(), g.data_ptr(), self._out_m[k].data_ptr(), self._out_v[k].data_ptr(), None, gid, p.numel(),
+                tab.data_ptr(), 1, nch, table, ng, b1, b2, eps, clip, adapt, part.data_ptr(),
+                self._out_ratios.data_ptr() + 4 * k, bad, ctl, stream), "hsimae_lamb_step")
+        m._packed_version = -1                    # packed bf16 images are stale now
+
+    def state_dict(self):
+        sd = super().state_dict()
+        sd["optimizer"] = "lamb"                  # the trust ratios are not state: every step forms them anew
+        return sd

@@ -17,7 +17,7 @@ import torch
 from .checkpoint import load_resume, save_final, save_resume
 from .data import DeviceLoader, HSIdataset4PT
 from .model import HSIMAE
-from .optim import FusedAdamW
+from .optim import FusedAdamW, FusedLAMB
 from .sched import CosineLRScheduler
 
 
@@ -63,13 +63,19 @@ def dp_context(device):
 
 def mask_pretraining(data_cubes, save_path, model_name, img_size=9, bands=32, mask_ratio=0.50, lr=5e-3, wd=5e-2, bs=512,
                      epochs=100, depth=12, dim=64, s_depth=6, dec_dim=48, dec_depth=2, resume_path=None, device="cuda:0",
-                     log=print, max_grad_norm=None, skip_nonfinite=False):
-    """`max_grad_norm` / `skip_nonfinite` go to FusedAdamW (gradient clipping and the non-finite step skip, decided on the device);
+                     log=print, max_grad_norm=None, skip_nonfinite=False, optimizer="adamw"):
+    """`optimizer`: "adamw" (the reference's recipe, the default) or "lamb": FusedLAMB with the same lr, wd and betas and
+    max_grad_norm 1.0 where the caller left it None (LAMB's usual pre-normalisation); every epoch then also logs the smallest and
+    largest trust ratio among the adapted tensors, as the epoch's last step left them.  No large-batch recipe has been measured.
+
+    `max_grad_norm` / `skip_nonfinite` go to FusedAdamW (gradient clipping and the non-finite step skip, decided on the device);
     when either is set every epoch logs the largest gradient norm it saw and the number of steps skipped so far.
 
     `bs` is the GLOBAL batch, as in the reference; under a data-parallel launch each rank takes bs / world cubes of every
     batch (same permutation and python-random stream on every rank), gradients are averaged with the bucketed RCCL
     all-reduce overlapped with the backward (hsimae_amd/parallel.py), and rank 0 writes the files."""
+    if optimizer not in ("adamw", "lamb"):
+        raise ValueError(f'optimizer must be "adamw" or "lamb", got {optimizer!r}')
     device = torch.device(device)
     rank, world, device = dp_context(device)
     if bs % world:
@@ -88,8 +94,13 @@ def mask_pretraining(data_cubes, save_path, model_name, img_size=9, bands=32, ma
         os.makedirs(save_path, exist_ok=True)
 
     train_dataload = DeviceLoader(train_dataset, batch_size=bs // world, shuffle=True, rank=rank, world=world)
-    optimizer = FusedAdamW(model, lr=lr, weight_decay=wd, betas=(0.9, 0.95), max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
-    clipped = max_grad_norm is not None or skip_nonfinite
+    lamb = optimizer == "lamb"
+    if lamb:
+        optimizer = FusedLAMB(model, lr=lr, weight_decay=wd, betas=(0.9, 0.95), max_grad_norm=1.0 if max_grad_norm is None else max_grad_norm,
+                              skip_nonfinite=skip_nonfinite)
+    else:
+        optimizer = FusedAdamW(model, lr=lr, weight_decay=wd, betas=(0.9, 0.95), max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+    clipped = max_grad_norm is not None or skip_nonfinite or lamb
     iters = epochs * len(train_dataload)
     scheduler = CosineLRScheduler(optimizer, t_initial=iters, lr_min=1e-6, warmup_t=int(np.ceil(iters * 0.05)))
 
@@ -127,7 +138,13 @@ def mask_pretraining(data_cubes, save_path, model_name, img_size=9, bands=32, ma
             dist.all_reduce(t)
             epoch_loss = float(t.item()) / world
         epoch_loss_list.append(epoch_loss)
-        if clipped:                                     # one read per epoch; step() itself never waits
+        if lamb:                                        # one read per epoch; step() itself never waits
+            norm_max, skipped, r_lo, r_hi = torch.cat([torch.stack([optimizer.grad_norm_max.double(), optimizer.skipped_steps.double()]),
+                                                       optimizer.trust_ratio_range()]).tolist()
+            optimizer.reset_grad_norm_max()
+            log(f"epoch {epoch}: loss {epoch_loss:.6f}, largest gradient norm {norm_max:.6g}, {int(skipped)} steps skipped so far, "
+                f"trust ratio {r_lo:.6g} .. {r_hi:.6g}")
+        elif clipped:                                   # one read per epoch; step() itself never waits
             norm_max, skipped = torch.stack([optimizer.grad_norm_max.double(), optimizer.skipped_steps.double()]).tolist()
             optimizer.reset_grad_norm_max()
             log(f"epoch {epoch}: loss {epoch_loss:.6f}, largest gradient norm {norm_max:.6g}, {int(skipped)} steps skipped so far")

@@ -703,6 +703,39 @@ int hsimae_adamw_step_groups(float* params, const float* grads, float* exp_avg, 
                              float beta1, float beta2, float eps, int32_t step, const hsimae_clip_ctl* ctl /* device, may be NULL */,
                              void* stream);
 
+/* ------------------------------------------------------------------ LAMB: Adam's update scaled per parameter tensor by |w| / |update|
+ * (You et al., "Large Batch Optimization for Deep Learning", 2020; the optimizer of apex FusedLAMB and timm Lamb), on the flat buffer
+ * hsimae_adamw_step_groups steps, with its id byte per element, its {lr, weight_decay} table and hsimae_grad_norm's control block.
+ * ADDED under HSIMAE_VERSION 108 like the entry points above: nothing that 108 already had changes.
+ *
+ * hsimae_lamb_step: for every tensor T of `tensors` (device memory: `off` and `n` in floats into the four arrays, `chunk0` the
+ *   prefix sum of ceil(n / HSIMAE_LAMB_CHUNK) over the tensors in front of it; `nchunks` the total), with k the id byte of the
+ *   tensor's FIRST element (group NULL: `group_uniform`), in fp32 unless stated:
+ *     gc = g * ctl->coef;   m' = m + (gc - m) (1 - beta1);   v' = v beta2 + gc gc (1 - beta2)          (hsimae_adamw_step's forms)
+ *     u  = (m' ctl->inv_bc1) / (sqrtf(v') ctl->inv_sqrt_bc2 + eps)   [+ table[k].weight_decay p   when that is != 0]
+ *     r  = (float)sqrt(sum_T p^2 / sum_T u^2), sums and root in fp64, when (weight_decay != 0 or always_adapt) and both sums are > 0,
+ *          otherwise 1;   r = min(r, trust_clip) when trust_clip > 0
+ *     p' = p - (table[k].lr r) u
+ *   With every r = 1 this is AdamW's step.  ratios[T] = r.  k == 2 or k >= ngroups: the tensor is frozen; nothing of it is read but
+ *   that byte, nothing is written (its gradient may hold NaN) and ratios[T] = 1.  `grads` is never written.
+ *   Three launches on `stream`, no atomics, every sum in a fixed order: two runs agree bit for bit.  `partials` (2 nchunks doubles)
+ *   is scratch.  `ctl` is required; when ctl->apply is 0 nothing is read from the arrays and nothing is written, `ratios` keeps the
+ *   values of the last applied step.  A chunk whose table entry is inconsistent (off < 0, off + n > n_total, the chunk outside
+ *   [chunk0, chunk0 + ceil(n / HSIMAE_LAMB_CHUNK)), chunk0 not the prefix sum) writes nothing and sets *bad = 1; `bad` is never
+ *   cleared here.  `table` is HOST memory, copied into the launch.
+ *   Refusals, before any launch: a NULL among params, grads, the moments, tensors, table, partials, ratios, bad, ctl ->
+ *   HSIMAE_ENULL; n < 0, ntensors < 1, nchunks < 1, ngroups outside 1 .. HSIMAE_ADAMW_MAX_GROUPS, group NULL with group_uniform
+ *   neither 2 nor inside 0 .. ngroups - 1, an lr or weight_decay (other than table[2]'s) negative or NaN -> HSIMAE_EDIMS; an array,
+ *   ratios or bad not 4-byte, partials, tensors or ctl not 8-byte aligned -> HSIMAE_EALIGN.  n == 0: HSIMAE_OK and no launch. */
+#define HSIMAE_LAMB_CHUNK 4096
+typedef struct { int64_t off; int64_t n; int32_t chunk0; int32_t reserved; } hsimae_lamb_tensor;   /* device table, 24 bytes */
+int hsimae_lamb_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* group,
+                     int32_t group_uniform, int64_t n, const hsimae_lamb_tensor* tensors /* device */, int32_t ntensors,
+                     int32_t nchunks, const hsimae_adamw_group* table /* host */, int32_t ngroups, float beta1, float beta2, float eps,
+                     float trust_clip /* <= 0: none */, int32_t always_adapt, double* partials /* device, 2 * nchunks */,
+                     float* ratios /* device, ntensors */, int32_t* bad /* device */, const hsimae_clip_ctl* ctl /* device, required */,
+                     void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

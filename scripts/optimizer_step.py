@@ -1,11 +1,13 @@
-"""What a clipped optimizer step costs, at Base and Huge, three figures taken on the same GPU in one run:
+"""What a clipped optimizer step costs, at Base and Huge, four figures taken on the same GPU in one run:
 
   1. plain        FusedAdamW.step()                                          (one launch)
   2. torch_clip   torch.nn.utils.clip_grad_norm_(...) + FusedAdamW.step()    (what a user had before max_grad_norm existed)
   3. fused_clip   FusedAdamW(max_grad_norm=..., skip_nonfinite=True).step()  (hsimae_grad_norm + hsimae_adamw_step_ctl)
+  4. lamb         FusedLAMB(max_grad_norm=..., skip_nonfinite=True).step()   (hsimae_grad_norm + hsimae_lamb_step: five launches;
+                  from its traffic, 10 array passes against 7, about 10 / 7 of fused_clip plus two small launches)
 
 Gradients are present (one forward + backward first), every figure is the mean over --steps steps between two HIP events after
---warmup steps, repeated --repeats times with the three variants interleaved; the spread is max - min over the repeats.
+--warmup steps, repeated --repeats times with the four variants interleaved; the spread is max - min over the repeats.
 max_norm is far above the norm, so that torch's in-place clip leaves the gradients as they are (the time does not depend on the
 coefficient).  Prints one JSON line per model and writes all of them to --out.
 
@@ -21,7 +23,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.getcwd())
-from hsimae_amd import HSIMAE, FusedAdamW  # noqa: E402
+from hsimae_amd import HSIMAE, FusedAdamW, FusedLAMB  # noqa: E402
 
 MODELS = {"base": (96, 128, 8, "bf16"), "large": (96, 256, 16, "bf16"), "huge": (192, 512, 32, "bf16")}     # bench.py's widths; the
 # step works on the fp32 masters and does not depend on the GEMM operand type, so the one backward that provides gradients runs in bf16
@@ -40,13 +42,14 @@ def measure(name, steps, warmup, repeats, batch, dev):
     model(x, mask_ratio=0.75)[0].backward()
     kw = dict(lr=1e-5, weight_decay=5e-2, betas=(0.9, 0.95))
     plain, clipped = FusedAdamW(model, **kw), FusedAdamW(model, max_grad_norm=1e9, skip_nonfinite=True, **kw)
+    lamb = FusedLAMB(model, max_grad_norm=1e9, skip_nonfinite=True, **kw)
     with_grad = [p for p in model.parameters() if p.grad is not None]
 
     def torch_clip():
         torch.nn.utils.clip_grad_norm_(with_grad, 1e9)
         plain.step()
 
-    variants = {"plain": plain.step, "torch_clip": torch_clip, "fused_clip": clipped.step}
+    variants = {"plain": plain.step, "torch_clip": torch_clip, "fused_clip": clipped.step, "lamb": lamb.step}
     times = {k: [] for k in variants}
     for fn in variants.values():
         for _ in range(warmup):
@@ -61,7 +64,7 @@ def measure(name, steps, warmup, repeats, batch, dev):
             b.record()
             b.synchronize()
             times[k].append(a.elapsed_time(b) / steps)
-    if int(clipped.skipped_steps) != 0 or not torch.isfinite(model._flat).all():
+    if int(clipped.skipped_steps) != 0 or int(lamb.skipped_steps) != 0 or int(lamb.table_error) != 0 or not torch.isfinite(model._flat).all():
         raise RuntimeError("the measured steps were not clean")
     res = {"model": name, "precision": precision, "parameters": int(model._flat.numel()), "tensors_with_grad": len(with_grad),
            "steps": steps, "warmup": warmup, "repeats": repeats, "gpu": torch.cuda.get_device_name(dev)}
@@ -70,6 +73,10 @@ def measure(name, steps, warmup, repeats, batch, dev):
     spread = max(r["max"] - r["min"] for r in (res["torch_clip_ms"], res["fused_clip_ms"]))
     res["ratio_fused_clip_to_plain"] = res["fused_clip_ms"]["median"] / res["plain_ms"]["median"]
     res["spread_ms"] = spread
+    res["ratio_lamb_to_fused_clip"] = res["lamb_ms"]["median"] / res["fused_clip_ms"]["median"]
+    res["lamb_spread_ms"] = res["lamb_ms"]["max"] - res["lamb_ms"]["min"]
+    ratios = lamb.trust_ratios[torch.tensor(lamb.adapted(), device=dev)]
+    res["lamb_trust_ratio_range"] = [float(ratios.min()), float(ratios.max())]
     res["fused_clip_faster_than_torch_clip_by_more_than_spread"] = res["torch_clip_ms"]["median"] - res["fused_clip_ms"]["median"] > spread
     return res
 
