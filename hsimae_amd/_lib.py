@@ -163,6 +163,7 @@ ADAMW_MAX_GROUPS = 64   # HSIMAE_ADAMW_MAX_GROUPS
 CLIP_GRID = 1024        # HSIMAE_CLIP_GRID: doubles of scratch hsimae_grad_norm needs in `partials`
 CLIP_MAX_SEGS = 8       # HSIMAE_CLIP_MAX_SEGS
 LAMB_CHUNK = 4096       # HSIMAE_LAMB_CHUNK: floats of one tensor behind one workgroup of hsimae_lamb_step
+EMA_MAX_GRID = 2048     # HSIMAE_EMA_MAX_GRID: workgroups (of 256 threads) hsimae_ema_update / hsimae_ema_swap launch at most
 
 
 class BuildInfo(C.Structure):
@@ -218,6 +219,8 @@ SYMBOLS = {
     "hsimae_adamw_step_groups": (C.c_int, [vp, vp, vp, vp, vp, i32, i64, C.POINTER(AdamWGroup), i32, f32, f32, f32, i32, vp, vp]),
     "hsimae_lamb_step": (C.c_int, [vp, vp, vp, vp, vp, i32, i64, vp, i32, i32, C.POINTER(AdamWGroup), i32, f32, f32, f32, f32, i32,
                                    vp, vp, vp, vp, vp]),
+    "hsimae_ema_update": (C.c_int, [vp, vp, i64, C.c_double, i32, i32, vp, vp]),
+    "hsimae_ema_swap": (C.c_int, [vp, vp, i64, vp]),
     "hsimae_cube_gather": (C.c_int, [C.POINTER(CubeParams), vp]),
     "hsimae_scene_windows": (C.c_int, [C.POINTER(SceneParams), vp]),
     "hsimae_class_argmax": (C.c_int, [C.POINTER(SceneParams), vp, i32, i32, i32, vp, vp]),

@@ -423,6 +423,7 @@ extern "C" unsigned hs_variant_bits_gwpca();
 extern "C" unsigned hs_variant_bits_cls();
 extern "C" unsigned hs_variant_bits_clip();
 extern "C" unsigned hs_variant_bits_lamb();
+extern "C" unsigned hs_variant_bits_ema();
 #ifndef HS_KERNEL_SOURCE_HASH
 #define HS_KERNEL_SOURCE_HASH 0ULL
 #endif
@@ -440,7 +441,7 @@ int hsimae_version(void) { return HSIMAE_VERSION; }
 int hsimae_build_info(hsimae_build_info_t* out) {
     if (!out) return HSIMAE_ENULL;
     out->abi_version = HSIMAE_VERSION;
-    out->variant_bits = hs_variant_bits() | hs_variant_bits_gemm() | hs_variant_bits_attn() | hs_variant_bits_attn_wide() | hs_variant_bits_wgrad() | hs_variant_bits_elem() | hs_variant_bits_pack() | hs_variant_bits_fused_dec() | hs_variant_bits_fused_enc() | hs_variant_bits_loader() | hs_variant_bits_scene() | hs_variant_bits_gwpca() | hs_variant_bits_cls() | hs_variant_bits_clip() | hs_variant_bits_lamb();
+    out->variant_bits = hs_variant_bits() | hs_variant_bits_gemm() | hs_variant_bits_attn() | hs_variant_bits_attn_wide() | hs_variant_bits_wgrad() | hs_variant_bits_elem() | hs_variant_bits_pack() | hs_variant_bits_fused_dec() | hs_variant_bits_fused_enc() | hs_variant_bits_loader() | hs_variant_bits_scene() | hs_variant_bits_gwpca() | hs_variant_bits_cls() | hs_variant_bits_clip() | hs_variant_bits_lamb() | hs_variant_bits_ema();
     out->kernel_source_hash = HS_KERNEL_SOURCE_HASH;
     out->flags_hash = HS_BUILD_FLAGS_HASH;
     out->default_flags = HS_BUILD_DEFAULT_FLAGS;
@@ -1015,6 +1016,11 @@ int hsimae_lamb_step(float* params, const float* grads, float* exp_avg, float* e
     return hs_lamb_step(params, grads, exp_avg, exp_avg_sq, group, group_uniform, n, tensors, ntensors, nchunks, table, ngroups, beta1,
                         beta2, eps, trust_clip, always_adapt, partials, ratios, bad, ctl, S(stream));
 }
+int hsimae_ema_update(float* ema, const float* params, int64_t n, double decay, int32_t warmup, int32_t step,
+                      const hsimae_clip_ctl* ctl, void* stream) {
+    return hs_ema_update(ema, params, n, decay, warmup, step, ctl, S(stream));
+}
+int hsimae_ema_swap(float* a, float* b, int64_t n, void* stream) { return hs_ema_swap(a, b, n, S(stream)); }
 int hsimae_loss_partials(int32_t N, int32_t T) { return hs_loss_partials(N, T); }
 int hsimae_loss(const hsimae_loss_params* p, void* stream) { return p ? hs_loss(*p, S(stream)) : HSIMAE_ENULL; }
 

@@ -123,3 +123,7 @@ int hs_lamb_step(float* p, const float* g, float* m, float* v, const unsigned ch
                  const hsimae_lamb_tensor* tensors, int ntensors, int nchunks, const hsimae_adamw_group* table, int ngroups, float b1,
                  float b2, float eps, float trust_clip, int always_adapt, double* partials, float* ratios, int* bad,
                  const hsimae_clip_ctl* ctl, hipStream_t s);
+// ema.hip: the moving average of the weights behind the step (skipped with it), and the exchange of weights and averages
+int hs_ema_update(float* ema, const float* params, int64_t n, double decay, int warmup, int step, const hsimae_clip_ctl* ctl,
+                  hipStream_t s);
+int hs_ema_swap(float* a, float* b, int64_t n, hipStream_t s);

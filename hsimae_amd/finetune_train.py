@@ -16,6 +16,7 @@ are not multiples of the kernels' 32-deep k-step) run zero-padded to 160 / 96 in
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import random
@@ -27,7 +28,7 @@ from . import _lib
 from .classify import ClassLoss, ScoreMeter
 from .data import DeviceLoader
 from .finetune import DualViT, HSIViT
-from .optim import FusedAdamW, FusedLAMB
+from .optim import FusedAdamW, FusedLAMB, weights_state_dict
 from .pretrain import seed_everything
 from .scene_data import SceneCubes, device_scene, unlabeled_pixels
 from .sched import CosineLRScheduler
@@ -102,16 +103,40 @@ def scores(gt, pred):
     return float(oa), float(ca.mean()), float(kappa), ca
 
 
+def val_score(oa, aa, kappa):
+    """The reference's per-epoch `val_aa` (Model_Finetuning.py: the mean of OA, AA and kappa; it only plots it)."""
+    return (oa + aa + kappa) / 3
+
+
+def best_epoch(scores):
+    """Index of the epoch `keep_best` keeps: the reference's Utils/Early_Stop.py rule with delta = 0, i.e. an epoch whose score is
+    >= the best so far replaces it, so among equal scores the LAST wins.  A NaN never replaces a number; the first epoch is always
+    taken.  None for an empty list."""
+    best = at = None
+    for i, s in enumerate(scores):
+        if best is None or best != best or s >= best:
+            best, at = s, i
+    return at
+
+
 def dual_branch_finetuning(data_list, labeled_index, unlabeled_data, gt, save_dir, model_name, pretrained=None,
                            lr=1e-3, wd=5e-3, depth=12, dim=144, dec_depth=2, dec_dim=72, s_depth=6,
                            epochs=100, mask_ratio=0.5, lamda=5, batch_size=32, device="cuda:0", log=print,
-                           max_grad_norm=None, skip_nonfinite=False, layer_decay=None, freeze=(), optimizer="adamw"):
+                           max_grad_norm=None, skip_nonfinite=False, layer_decay=None, freeze=(), optimizer="adamw",
+                           ema_decay=None, ema_warmup=True, keep_best=False):
     """`max_grad_norm` / `skip_nonfinite` go to FusedAdamW; when either is set every epoch logs the largest gradient norm it saw and
     the number of steps skipped so far, both read in the epoch's one wait for its losses.  `layer_decay` / `freeze` go to FusedAdamW
     too (layer-wise learning-rate decay, name prefixes left out of the step); with `layer_decay` every epoch also logs the smallest
     and largest effective learning rate it stepped with, from the host's param_groups.  `optimizer`: "adamw" (the default) or
     "lamb": FusedLAMB with the same arguments and max_grad_norm 1.0 where it was left None; every epoch then also logs the smallest
-    and largest trust ratio among the adapted tensors, in the same wait."""
+    and largest trust ratio among the adapted tensors, in the same wait.
+
+    `ema_decay` / `ema_warmup` go to the optimizer: it keeps a moving average of the weights on the device, every epoch's
+    validation runs on the AVERAGED weights (inside `swap_ema()`, and its log line says so), and next to `model_name`, which stays
+    the raw last-epoch weights, `<stem>_ema.pkl` is written with the same keys.  `keep_best`: the epoch whose validation
+    `val_score` is the best so far (`best_epoch`'s rule; on the weights that were validated, the averaged ones with `ema_decay`)
+    is copied device to device at the epoch's existing wait, and `<stem>_best.pkl` is written at the end.  The return value is
+    unchanged: the last epoch's scores.  Whether either helps OA / AA / kappa on a real scene has not been measured."""
     device = torch.device(device)
     h, w, c = data_list[0].shape
 
@@ -123,13 +148,15 @@ def dual_branch_finetuning(data_list, labeled_index, unlabeled_data, gt, save_di
 
     return _finetune(datasets, h, c, gt, save_dir, model_name, pretrained, lr, wd, depth, dim, dec_depth, dec_dim, s_depth, epochs,
                      mask_ratio, lamda, batch_size, device, log, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite,
-                     layer_decay=layer_decay, freeze=freeze, optimizer=optimizer)
+                     layer_decay=layer_decay, freeze=freeze, optimizer=optimizer, ema_decay=ema_decay, ema_warmup=ema_warmup,
+                     keep_best=keep_best)
 
 
 def dual_branch_finetuning_scene(scene, labeled_index, gt, save_dir, model_name, pretrained=None,
                                  lr=1e-3, wd=5e-3, depth=12, dim=144, dec_depth=2, dec_dim=72, s_depth=6,
                                  epochs=100, mask_ratio=0.5, lamda=5, batch_size=32, device="cuda:0", log=print,
-                                 max_grad_norm=None, skip_nonfinite=False, layer_decay=None, freeze=(), optimizer="adamw"):
+                                 max_grad_norm=None, skip_nonfinite=False, layer_decay=None, freeze=(), optimizer="adamw",
+                                 ema_decay=None, ema_warmup=True, keep_best=False):
     """`dual_branch_finetuning` from the scene itself: `scene` is the processed [H, W, C] `HSI_data` (get_scene_set_dual's third
     result; a device tensor is used in place), `labeled_index` the labeled pixels r * W + c and `gt` their labels.  The same
     loop, with `data_list[i]` = the padded window of pixel i and `unlabeled_data` = the scene's non-overlapping 9 x 9 tiles,
@@ -153,11 +180,13 @@ def dual_branch_finetuning_scene(scene, labeled_index, gt, save_dir, model_name,
 
     return _finetune(datasets, 9, c, gt, save_dir, model_name, pretrained, lr, wd, depth, dim, dec_depth, dec_dim, s_depth, epochs,
                      mask_ratio, lamda, batch_size, device, log, check, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite,
-                     layer_decay=layer_decay, freeze=freeze, optimizer=optimizer)
+                     layer_decay=layer_decay, freeze=freeze, optimizer=optimizer, ema_decay=ema_decay, ema_warmup=ema_warmup,
+                     keep_best=keep_best)
 
 
 def _finetune(datasets, h, c, gt, save_dir, model_name, pretrained, lr, wd, depth, dim, dec_depth, dec_dim, s_depth, epochs, mask_ratio,
-              lamda, batch_size, device, log, check_data=None, max_grad_norm=None, skip_nonfinite=False, layer_decay=None, freeze=(), optimizer="adamw"):
+              lamda, batch_size, device, log, check_data=None, max_grad_norm=None, skip_nonfinite=False, layer_decay=None, freeze=(), optimizer="adamw",
+              ema_decay=None, ema_warmup=True, keep_best=False):
     """The loop of Model_Finetuning.py:66-240.  `datasets()` -> (labeled, unlabeled, validation), called where the reference
     splits the labeled set (after the model's initialisation draws); `check_data()` once per epoch, with the loss's check."""
     n_class = int(np.max(gt) + 1)
@@ -178,10 +207,11 @@ def _finetune(datasets, h, c, gt, save_dir, model_name, pretrained, lr, wd, dept
     lamb = optimizer == "lamb"
     if lamb:
         optimizer = FusedLAMB(model, lr=lr, weight_decay=wd, max_grad_norm=1.0 if max_grad_norm is None else max_grad_norm,
-                              skip_nonfinite=skip_nonfinite, layer_decay=layer_decay, freeze=freeze)
+                              skip_nonfinite=skip_nonfinite, layer_decay=layer_decay, freeze=freeze, ema_decay=ema_decay,
+                              ema_warmup=ema_warmup)
     else:
         optimizer = FusedAdamW(model, lr=lr, weight_decay=wd, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite,
-                               layer_decay=layer_decay, freeze=freeze)
+                               layer_decay=layer_decay, freeze=freeze, ema_decay=ema_decay, ema_warmup=ema_warmup)
     clipped = max_grad_norm is not None or skip_nonfinite or lamb
     scheduler = CosineLRScheduler(optimizer, t_initial=epochs, lr_min=lr * 0.01, warmup_t=int(np.ceil(0.1 * epochs)),
                                   warmup_lr_init=lr * 0.01)
@@ -196,6 +226,9 @@ def _finetune(datasets, h, c, gt, save_dir, model_name, pretrained, lr, wd, dept
     log(f"train {len(train_ds)} labeled / {len(unl_ds)} unlabeled cubes, {len(train_dl)} iterations per epoch")
 
     epoch_loss_list, val_loss_list, val_value = [], [], None
+    ema = ema_decay is not None
+    head = [p for n, p in model.named_parameters() if n.startswith("cls_head.")]
+    val_scores, best_flat, best_head = [], None, None
     for epoch in range(epochs):
         model.train()
         seed_everything(42 + epoch); labeled_iter = iter(train_dl)              # `stable(loader, 42 + epoch)` twice
@@ -213,7 +246,7 @@ def _finetune(datasets, h, c, gt, save_dir, model_name, pretrained, lr, wd, dept
             train_loss += loss.detach()
 
         model.eval()
-        with torch.no_grad():
+        with torch.no_grad(), (optimizer.swap_ema() if ema else contextlib.nullcontext()):
             seed_everything(42 + epoch)
             val_loss = torch.zeros((), dtype=torch.float64, device=device)
             meter.reset()
@@ -221,7 +254,17 @@ def _finetune(datasets, h, c, gt, save_dir, model_name, pretrained, lr, wd, dept
                 outputs = model(x, mask_ratio=mask_ratio)
                 val_loss += criterion(outputs, y)
                 meter.update(y, criterion.last_pred)
-        val_value = list(meter.compute())
+            val_value = list(meter.compute())
+            if ema or keep_best:
+                val_scores.append(val_score(*val_value[:3]))
+                log(f"epoch {epoch}: validated on the {'EMA' if ema else 'raw'} weights: OA {val_value[0]:.6f}, AA {val_value[1]:.6f}, "
+                    f"kappa {val_value[2]:.6f}, val_aa {val_scores[-1]:.6f}")
+            if keep_best and best_epoch(val_scores) == epoch:                   # the weights just validated, device to device
+                if best_flat is None:
+                    best_flat, best_head = torch.empty_like(model._flat), [torch.empty_like(p) for p in head]
+                best_flat.copy_(model._flat)
+                for b, p in zip(best_head, head):
+                    b.copy_(p)
         if clipped:                                                             # the same wait also brings the norm and the count
             read = torch.stack([train_loss, val_loss, optimizer.grad_norm_max.double(), optimizer.skipped_steps.double()])
             if lamb:
@@ -243,6 +286,13 @@ def _finetune(datasets, h, c, gt, save_dir, model_name, pretrained, lr, wd, dept
         scheduler.step(epoch)
 
     torch.save(model.state_dict(), os.path.join(save_dir, model_name))
+    stem = os.path.join(save_dir, os.path.splitext(model_name)[0])
+    if ema:
+        torch.save(optimizer.ema_state_dict(), stem + "_ema.pkl")
+    if keep_best and best_flat is not None:
+        at = best_epoch(val_scores)
+        torch.save(weights_state_dict(model, best_flat, list(zip(head, best_head))), stem + "_best.pkl")
+        log(f"best epoch {at}: val_aa {val_scores[at]:.6f} on the {'EMA' if ema else 'raw'} weights -> {stem}_best.pkl")
     return val_value, epoch_loss_list, val_loss_list
 
 

@@ -15,10 +15,16 @@ id byte the kernel already reads per element indexes a table of {lr, weight_deca
 stays one launch however many groups there are, and composes with the clipping above.
 
 `FusedLAMB` (below) is the large-batch variant: the same buffers, ids, table and control block, with Adam's update scaled per parameter
-tensor by |w| / |update| (`hsimae_lamb_step`, csrc/lamb.hip)."""
+tensor by |w| / |update| (`hsimae_lamb_step`, csrc/lamb.hip).
+
+`ema_decay` (off by default) keeps an exponential moving average of the weights next to them: one `hsimae_ema_update` over the flat
+buffer behind the step's own launches, which reads the same control block, so a skipped step leaves the average alone and the
+step still waits for nothing.  `ema_state_dict()` reads the average, `swap_ema()` evaluates with it."""
 from __future__ import annotations
 
+import contextlib
 import re
+from collections import OrderedDict
 
 import numpy as np
 import torch
@@ -56,9 +62,23 @@ def layer_ids(model, depth=None, s_depth=None):
     return out
 
 
+def weights_state_dict(model, flat, outside=()):
+    """`model.state_dict()` with every parameter of the flat buffer read from `flat` (a tensor laid out like `model._flat`) and
+    every parameter of `outside` [(parameter, tensor)] from its tensor: the same keys, dtypes and shapes, fresh tensors."""
+    held = {id(p): flat[o:o + s] for p, o, s in zip(model._params_cache, model._offs, model._sizes)}
+    held.update({id(p): t for p, t in outside})
+    by_name = dict(model.named_parameters())
+    out = OrderedDict()
+    for k, v in model.state_dict().items():
+        p = by_name.get(k)
+        t = held.get(id(p)) if p is not None else None
+        out[k] = v.detach().clone() if t is None else t.to(v.device).reshape(v.shape).to(v.dtype).clone()
+    return out
+
+
 class FusedAdamW:
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, no_decay=("bias", "norm"), strict=True,
-                 max_grad_norm=None, skip_nonfinite=False, layer_decay=None, freeze=()):
+                 max_grad_norm=None, skip_nonfinite=False, layer_decay=None, freeze=(), ema_decay=None, ema_warmup=True):
         """max_grad_norm: clip the global gradient 2-norm to it, with torch.nn.utils.clip_grad_norm_'s coefficient
         min(1, max_norm / (norm + 1e-6)); `float("inf")` only measures.  skip_nonfinite: a step whose norm is Inf or NaN
         changes nothing (no parameter, no moment, no weight decay, no advance of the bias-correction count).
@@ -78,8 +98,22 @@ class FusedAdamW:
         freeze: name prefixes; a matching parameter is left out for good, exactly as one with requires_grad=False is: no update, no
         weight decay, its moments stay zero, and it is not part of the gradient norm.  `freeze` only selects what the optimizer
         steps: it does NOT shorten the backward pass, the frozen layers' gradients are still computed.
-        Whatever is written into `param_groups` (by hand or by a scheduler with per-group values) is honoured at the next step."""
+        Whatever is written into `param_groups` (by hand or by a scheduler with per-group values) is honoured at the next step.
+
+        ema_decay: a float in [0, 1); `self.ema` then holds an fp32 moving average of the flat parameter buffer (and one tensor per
+        live parameter outside it), started from the weights as they are before this optimizer's first step (what timm's ModelEma
+        copies) and moved by every APPLIED step: ema += (1 - d) * (p - ema), d = min(ema_decay, (1 + t) / (10 + t)) with
+        ema_warmup (TensorFlow's num_updates rule; t counts applied steps), d = ema_decay without.  A frozen parameter stays bit-equal
+        to its average.  The average never feeds back into the step.  Like timm's it is fp32: at ema_decay = 0.9999 an increment
+        below half an ulp of the average is lost."""
         self.model = model
+        if ema_decay is not None:
+            if isinstance(ema_decay, bool) or not isinstance(ema_decay, (int, float, np.floating, np.integer)) or not 0.0 <= float(ema_decay) < 1.0:
+                raise ValueError(f"ema_decay must be a float in [0, 1) (or None), got {ema_decay!r}")
+            ema_decay = float(ema_decay)
+        self.ema_decay, self.ema_warmup = ema_decay, bool(ema_warmup)
+        self.ema = None
+        self._swapped = False
         self.layer_decay = None if layer_decay is None else float(layer_decay)
         if self.layer_decay is not None and not 0.0 < self.layer_decay <= 1.0:
             raise ValueError(f"layer_decay must lie in (0, 1] (or be None), got {layer_decay}")
@@ -139,6 +173,8 @@ class FusedAdamW:
         # group's id for every element): a host-side optimizer could not honour a skip decided on the device.
         outside.sort(key=lambda pk: gid_of[pk[1]])                # decayed before not, as the stock optimizer's state lists them
         self._outside = [(p, gid_of[k]) for p, k in outside] if self._clip else []
+        self._ema_params = [p for p, _ in outside] if self.ema_decay is not None else []      # in both modes
+        self._ema_out = [None] * len(self._ema_params)
         self._out_m = [None] * len(self._outside)
         self._out_v = [None] * len(self._outside)
         if len(self._outside) > _lib.CLIP_MAX_SEGS - 1:
@@ -170,6 +206,13 @@ class FusedAdamW:
             self._group_host = grp
             self._group = grp.to(flat.device)
             self._mask_cache = {}
+            if self.ema_decay is not None:              # first bind: the weights before the first step; later: the average moves along
+                self.ema = flat.clone() if self.ema is None or self.ema.numel() != flat.numel() else self.ema.to(flat.device)
+                for k, p in enumerate(self._ema_params):
+                    if not p.is_contiguous() or p.dtype != torch.float32:
+                        raise RuntimeError(f"{type(self).__name__}: a parameter outside the flat buffer must be a contiguous fp32 tensor")
+                    e = self._ema_out[k]
+                    self._ema_out[k] = p.detach().reshape(-1).clone() if e is None or e.numel() != p.numel() else e.to(p.device)
             self._flat_id = flat.data_ptr()
 
     def zero_grad(self, set_to_none: bool = True):
@@ -259,6 +302,7 @@ class FusedAdamW:
 
     @torch.no_grad()
     def step(self):
+        self._refuse_inside_swap("step()")
         self._bind()
         m = self.model
         g0 = self.param_groups[0]
@@ -269,6 +313,7 @@ class FusedAdamW:
         if self._clip:
             self._step_clipped(group, float(b1), float(b2), stream)
             m._packed_version = -1
+            self._ema_update(stream)
             return
         if self._defaults_agree():
             _lib.check(_lib.load().hsimae_adamw_step(
@@ -286,6 +331,64 @@ class FusedAdamW:
                 ge["lr"] = self._effective_lr(self.param_groups[gi])
                 ge["weight_decay"] = self.param_groups[gi]["weight_decay"]
             self._extra.step()
+        self._ema_update(stream)
+
+    # ------------------------------------------------------------------ moving average of the weights (off by default)
+    def _ema_pairs(self):
+        return [(self.ema, self.model._flat)] + list(zip(self._ema_out, self._ema_params))
+
+    def _ema_update(self, stream):
+        """One hsimae_ema_update over the flat buffer and one per live parameter outside it, behind the step's launches.  With a
+        control block the kernel takes the skip decision and the count of applied steps from it; without one no step is skipped."""
+        if self.ema_decay is None:
+            return
+        lib = _lib.load()
+        ctl = None if self._ctl is None else self._ctl.data_ptr()
+        for e, p in self._ema_pairs():
+            _lib.check(lib.hsimae_ema_update(e.data_ptr(), p.data_ptr(), e.numel(), self.ema_decay, int(self.ema_warmup),
+                                             self.step_count, ctl, stream), "hsimae_ema_update")
+
+    def _need_ema(self, what):
+        if self.ema_decay is None:
+            raise RuntimeError(f"{type(self).__name__} was built without ema_decay: there is no average for {what}")
+
+    def _refuse_inside_swap(self, what):
+        if self._swapped:
+            raise RuntimeError(f"{type(self).__name__}: {what} inside swap_ema(): the model holds the averaged weights")
+
+    def _exchange(self):
+        m = self.model
+        stream = torch.cuda.current_stream(m._flat.device).cuda_stream
+        for e, p in self._ema_pairs():
+            _lib.check(_lib.load().hsimae_ema_swap(p.data_ptr(), e.data_ptr(), e.numel(), stream), "hsimae_ema_swap")
+        m._packed_version = -1                    # the packed bf16 images are stale now ...
+        if hasattr(m, "_head_pack"):
+            m._head_pack = None                   # ... and so is DualViT's packed head: a kernel write does not advance Parameter._version
+
+    @contextlib.contextmanager
+    def swap_ema(self):
+        """`with opt.swap_ema():` the model holds the averaged weights (and `self.ema` the raw ones); on exit they are exchanged
+        back, bit for bit.  Two launches of hsimae_ema_swap per buffer in all, no copy.  It cannot be nested, and step() refuses to
+        run inside it."""
+        self._need_ema("swap_ema()")
+        self._refuse_inside_swap("swap_ema()")
+        self._bind()
+        self._exchange()
+        self._swapped = True
+        try:
+            yield self
+        finally:
+            self._exchange()
+            self._swapped = False
+
+    def ema_state_dict(self):
+        """The averaged weights under `model.state_dict()`'s keys, dtypes and shapes (fresh tensors); entries that are not
+        parameters, and parameters the optimizer does not step, are the model's own.  Loads wherever the model's state_dict does."""
+        self._need_ema("ema_state_dict()")
+        self._bind()
+        if self._swapped:                          # the model holds the average right now
+            return OrderedDict((k, v.detach().clone()) for k, v in self.model.state_dict().items())
+        return weights_state_dict(self.model, self.ema, list(zip(self._ema_params, self._ema_out)))
 
     # ------------------------------------------------------------------ gradient norm / clipping / skip (off by default)
     def _ensure_ctl(self, device=None):
@@ -382,6 +485,9 @@ class FusedAdamW:
             sd["skipped"] = (self._views["skipped"].clone() if self._ctl is not None
                              else torch.as_tensor(self._skipped_loaded or 0, dtype=torch.int64))
             sd["outside_exp_avg"], sd["outside_exp_avg_sq"] = list(self._out_m), list(self._out_v)
+        if self.ema_decay is not None:
+            self._refuse_inside_swap("state_dict()")
+            sd["ema"], sd["outside_ema"], sd["ema_decay"] = self.ema, list(self._ema_out), self.ema_decay
         return sd
 
     _KIND = "adamw"                                  # what state_dict()["optimizer"] names; a checkpoint without the key is AdamW's
@@ -401,6 +507,13 @@ class FusedAdamW:
             self._extra.load_state_dict(sd["extra"])
         if self._clip:
             self._load_clip_state(sd)
+        if self.ema_decay is not None:            # a checkpoint without an average: it starts from the loaded weights at the next bind
+            self._refuse_inside_swap("load_state_dict()")
+            self.ema = sd.get("ema")
+            oe = sd.get("outside_ema")
+            if oe is not None and len(oe) != len(self._ema_params):
+                raise ValueError(f"checkpoint carries averages for {len(oe)} outside parameters, the model has {len(self._ema_params)}")
+            self._ema_out = [None] * len(self._ema_params) if oe is None or self.ema is None else [None if t is None else t.reshape(-1) for t in oe]
         self._flat_id = None
 
     def _load_clip_state(self, sd):
@@ -452,20 +565,21 @@ class FusedLAMB(FusedAdamW):
     formed: the step reads the clip coefficient, the skip decision and the bias corrections from the device-side control block.
     trust_clip: an upper bound on r (timm's trust_clip=True is trust_clip=1.0); None: no bound.
     always_adapt: False leaves tensors whose weight decay is 0 (biases, norms) at r = 1, as timm does.
-    layer_decay / freeze / param_groups / skip_nonfinite / strict: FusedAdamW's.
+    layer_decay / freeze / param_groups / skip_nonfinite / strict / ema_decay / ema_warmup: FusedAdamW's.
 
     step() is hsimae_grad_norm (two launches) and hsimae_lamb_step (three) over the flat buffer, then one hsimae_lamb_step per
     live parameter outside it (DualViT's head); no ATen op, no host wait.  `trust_ratios` holds the last applied step's ratios."""
     _KIND = "lamb"
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, no_decay=("bias", "norm"), strict=True,
-                 max_grad_norm=1.0, skip_nonfinite=False, layer_decay=None, freeze=(), trust_clip=None, always_adapt=False):
+                 max_grad_norm=1.0, skip_nonfinite=False, layer_decay=None, freeze=(), trust_clip=None, always_adapt=False,
+                 ema_decay=None, ema_warmup=True):
         if max_grad_norm is not None and not float(max_grad_norm) > 0:
             raise ValueError(f"max_grad_norm must be greater than 0 (or None), got {max_grad_norm}")
         # the parent in its clipped mode (it owns the outside parameters' moments and the control block); inf only measures
         super().__init__(model, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, no_decay=no_decay, strict=strict,
                          max_grad_norm=float("inf") if max_grad_norm is None else max_grad_norm, skip_nonfinite=skip_nonfinite,
-                         layer_decay=layer_decay, freeze=freeze)
+                         layer_decay=layer_decay, freeze=freeze, ema_decay=ema_decay, ema_warmup=ema_warmup)
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.trust_clip = None if trust_clip is None else float(trust_clip)
         if self.trust_clip is not None and not self.trust_clip > 0:
@@ -532,6 +646,7 @@ class FusedLAMB(FusedAdamW):
 
     @torch.no_grad()
     def step(self):
+        self._refuse_inside_swap("step()")
         self._bind()
         m, lib = self.model, _lib.load()
         flat = m._flat
@@ -560,6 +675,7 @@ class FusedLAMB(FusedAdamW):
                 tab.data_ptr(), 1, nch, table, ng, b1, b2, eps, clip, adapt, part.data_ptr(),
                 self._out_ratios.data_ptr() + 4 * k, bad, ctl, stream), "hsimae_lamb_step")
         m._packed_version = -1                    # packed bf16 images are stale now
+        self._ema_update(stream)
 
     def state_dict(self):
         sd = super().state_dict()

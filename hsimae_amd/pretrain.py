@@ -63,13 +63,17 @@ def dp_context(device):
 
 def mask_pretraining(data_cubes, save_path, model_name, img_size=9, bands=32, mask_ratio=0.50, lr=5e-3, wd=5e-2, bs=512,
                      epochs=100, depth=12, dim=64, s_depth=6, dec_dim=48, dec_depth=2, resume_path=None, device="cuda:0",
-                     log=print, max_grad_norm=None, skip_nonfinite=False, optimizer="adamw"):
+                     log=print, max_grad_norm=None, skip_nonfinite=False, optimizer="adamw", ema_decay=None, ema_warmup=True):
     """`optimizer`: "adamw" (the reference's recipe, the default) or "lamb": FusedLAMB with the same lr, wd and betas and
     max_grad_norm 1.0 where the caller left it None (LAMB's usual pre-normalisation); every epoch then also logs the smallest and
     largest trust ratio among the adapted tensors, as the epoch's last step left them.  No large-batch recipe has been measured.
 
     `max_grad_norm` / `skip_nonfinite` go to FusedAdamW (gradient clipping and the non-finite step skip, decided on the device);
     when either is set every epoch logs the largest gradient norm it saw and the number of steps skipped so far.
+
+    `ema_decay` / `ema_warmup` go to the optimizer: it keeps a moving average of the weights on the device, `<stem>_ema.pkl` is
+    written next to `model_name` (same keys; `model_name` stays the raw weights), and the per-epoch resume file carries the average
+    in the optimizer's state.
 
     `bs` is the GLOBAL batch, as in the reference; under a data-parallel launch each rank takes bs / world cubes of every
     batch (same permutation and python-random stream on every rank), gradients are averaged with the bucketed RCCL
@@ -97,9 +101,10 @@ def mask_pretraining(data_cubes, save_path, model_name, img_size=9, bands=32, ma
     lamb = optimizer == "lamb"
     if lamb:
         optimizer = FusedLAMB(model, lr=lr, weight_decay=wd, betas=(0.9, 0.95), max_grad_norm=1.0 if max_grad_norm is None else max_grad_norm,
-                              skip_nonfinite=skip_nonfinite)
+                              skip_nonfinite=skip_nonfinite, ema_decay=ema_decay, ema_warmup=ema_warmup)
     else:
-        optimizer = FusedAdamW(model, lr=lr, weight_decay=wd, betas=(0.9, 0.95), max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+        optimizer = FusedAdamW(model, lr=lr, weight_decay=wd, betas=(0.9, 0.95), max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite,
+                               ema_decay=ema_decay, ema_warmup=ema_warmup)
     clipped = max_grad_norm is not None or skip_nonfinite or lamb
     iters = epochs * len(train_dataload)
     scheduler = CosineLRScheduler(optimizer, t_initial=iters, lr_min=1e-6, warmup_t=int(np.ceil(iters * 0.05)))
@@ -152,4 +157,6 @@ def mask_pretraining(data_cubes, save_path, model_name, img_size=9, bands=32, ma
             save_resume(resume_path, model, optimizer, scheduler, epoch + 1, iter_num, epoch_loss_list, device)
     if rank == 0:
         save_final(model, save_path, model_name, epoch_loss_list, val_loss_list)
+        if ema_decay is not None:
+            torch.save(optimizer.ema_state_dict(), os.path.join(save_path, os.path.splitext(model_name)[0] + "_ema.pkl"))
     return model, epoch_loss_list

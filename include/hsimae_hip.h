@@ -736,6 +736,35 @@ int hsimae_lamb_step(float* params, const float* grads, float* exp_avg, float* e
                      float* ratios /* device, ntensors */, int32_t* bad /* device */, const hsimae_clip_ctl* ctl /* device, required */,
                      void* stream);
 
+/* ------------------------------------------------------------------ an exponential moving average (EMA) of the weights, kept next
+ * to them in device memory (timm's ModelEma, TensorFlow's ExponentialMovingAverage), and the exchange of weights and averages for
+ * an evaluation.  What eager torch does with one foreach op over every parameter tensor and a host-side `if` on whether the step
+ * was skipped is one launch that reads hsimae_grad_norm's control block: no host wait.
+ * ADDED under HSIMAE_VERSION 108 like the entry points above: nothing that 108 already had changes.
+ *
+ * hsimae_ema_update: with t = step - (ctl ? ctl->skipped : 0), the number of applied optimizer steps including this one (the count
+ *   ctl's bias corrections use), evaluated in fp64:
+ *     d = warmup ? min(decay, (1 + t) / (10 + t)) : decay;     a = (float)(1 - d)
+ *   and then per element, in fp32, exactly this sequence:
+ *     s = p - ema (one rounding);   ema' = fmaf(a, s, ema) (one rounding)
+ *   An element whose p equals its ema bit for bit keeps its bits (a select, not arithmetic: -0.0 stays -0.0, a NaN keeps its
+ *   payload), so a parameter that is never stepped stays bit-equal to its average for good.  There is no group array: the average
+ *   covers every element.  `params` is never written.  ctl != NULL and ctl->apply == 0: nothing is read from the arrays and nothing
+ *   is written; a skipped step moves neither the average nor its warm-up count.
+ *   Any n >= 0 and any 4-byte alignment: 16-byte loads and stores where both arrays are 16-byte aligned, one element per thread
+ *   behind that body (all of them otherwise); at most HSIMAE_EMA_MAX_GRID workgroups of 256 threads, which stride over the rest.
+ *   One launch on `stream`, no atomics, no LDS.  The average is fp32, as timm's is: at decay = 0.9999 an increment a (p - ema)
+ *   smaller than half an ulp of ema is lost.
+ *   Refusals, before any launch: n < 0, decay NaN or outside [0, 1), step < 1 -> HSIMAE_EDIMS; a NULL array with n > 0 ->
+ *   HSIMAE_ENULL; an array not 4-byte or ctl not 8-byte aligned -> HSIMAE_EALIGN.  n == 0: HSIMAE_OK and no launch.
+ * hsimae_ema_swap: exchanges a[0 .. n) and b[0 .. n) as 32-bit words (NaN payloads included); the same freedom of size and
+ *   alignment, one launch.  Refusals: n < 0, or the two ranges overlap -> HSIMAE_EDIMS; a NULL array with n > 0 -> HSIMAE_ENULL;
+ *   an array not 4-byte aligned -> HSIMAE_EALIGN.  n == 0: HSIMAE_OK and no launch. */
+#define HSIMAE_EMA_MAX_GRID 2048
+int hsimae_ema_update(float* ema, const float* params, int64_t n, double decay, int32_t warmup, int32_t step,
+                      const hsimae_clip_ctl* ctl /* device, may be NULL */, void* stream);
+int hsimae_ema_swap(float* a, float* b, int64_t n, void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

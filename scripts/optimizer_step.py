@@ -1,10 +1,13 @@
-"""What a clipped optimizer step costs, at Base and Huge, four figures taken on the same GPU in one run:
+"""What a clipped optimizer step costs, at Base and Huge, four figures (seven with the moving average) taken on the same GPU in one run:
 
   1. plain        FusedAdamW.step()                                          (one launch)
   2. torch_clip   torch.nn.utils.clip_grad_norm_(...) + FusedAdamW.step()    (what a user had before max_grad_norm existed)
   3. fused_clip   FusedAdamW(max_grad_norm=..., skip_nonfinite=True).step()  (hsimae_grad_norm + hsimae_adamw_step_ctl)
   4. lamb         FusedLAMB(max_grad_norm=..., skip_nonfinite=True).step()   (hsimae_grad_norm + hsimae_lamb_step: five launches;
                   from its traffic, 10 array passes against 7, about 10 / 7 of fused_clip plus two small launches)
+  5. plain_ema, fused_clip_ema, lamb_ema   1, 3 and 4 built with ema_decay=0.9999: one hsimae_ema_update more per step.  From its
+                  traffic the update moves 12 bytes per element (average read and written, weight read) next to the AdamW kernel's
+                  29 (four arrays read, three written, one id byte): 12 / 29 = 0.41 of the plain step is what to expect.
 
 Gradients are present (one forward + backward first), every figure is the mean over --steps steps between two HIP events after
 --warmup steps, repeated --repeats times with the four variants interleaved; the spread is max - min over the repeats.
@@ -43,13 +46,17 @@ def measure(name, steps, warmup, repeats, batch, dev):
     kw = dict(lr=1e-5, weight_decay=5e-2, betas=(0.9, 0.95))
     plain, clipped = FusedAdamW(model, **kw), FusedAdamW(model, max_grad_norm=1e9, skip_nonfinite=True, **kw)
     lamb = FusedLAMB(model, max_grad_norm=1e9, skip_nonfinite=True, **kw)
+    ema = dict(ema_decay=0.9999, ema_warmup=True)
+    plain_ema, clipped_ema = FusedAdamW(model, **kw, **ema), FusedAdamW(model, max_grad_norm=1e9, skip_nonfinite=True, **kw, **ema)
+    lamb_ema = FusedLAMB(model, max_grad_norm=1e9, skip_nonfinite=True, **kw, **ema)
     with_grad = [p for p in model.parameters() if p.grad is not None]
 
     def torch_clip():
         torch.nn.utils.clip_grad_norm_(with_grad, 1e9)
         plain.step()
 
-    variants = {"plain": plain.step, "torch_clip": torch_clip, "fused_clip": clipped.step, "lamb": lamb.step}
+    variants = {"plain": plain.step, "torch_clip": torch_clip, "fused_clip": clipped.step, "lamb": lamb.step,
+                "plain_ema": plain_ema.step, "fused_clip_ema": clipped_ema.step, "lamb_ema": lamb_ema.step}
     times = {k: [] for k in variants}
     for fn in variants.values():
         for _ in range(warmup):
@@ -64,6 +71,8 @@ def measure(name, steps, warmup, repeats, batch, dev):
             b.record()
             b.synchronize()
             times[k].append(a.elapsed_time(b) / steps)
+    if int(clipped_ema.skipped_steps) != 0 or int(lamb_ema.skipped_steps) != 0 or not torch.isfinite(plain_ema.ema).all():
+        raise RuntimeError("the measured steps were not clean")
     if int(clipped.skipped_steps) != 0 or int(lamb.skipped_steps) != 0 or int(lamb.table_error) != 0 or not torch.isfinite(model._flat).all():
         raise RuntimeError("the measured steps were not clean")
     res = {"model": name, "precision": precision, "parameters": int(model._flat.numel()), "tensors_with_grad": len(with_grad),
@@ -77,6 +86,11 @@ def measure(name, steps, warmup, repeats, batch, dev):
     res["lamb_spread_ms"] = res["lamb_ms"]["max"] - res["lamb_ms"]["min"]
     ratios = lamb.trust_ratios[torch.tensor(lamb.adapted(), device=dev)]
     res["lamb_trust_ratio_range"] = [float(ratios.min()), float(ratios.max())]
+    for k in ("plain", "fused_clip", "lamb"):                       # what the average adds to each step, beside 12 / 29 of the plain one
+        res[f"ema_adds_to_{k}_ms"] = res[k + "_ema_ms"]["median"] - res[k + "_ms"]["median"]
+        res[f"ema_spread_{k}_ms"] = max(res[k + "_ema_ms"]["max"] - res[k + "_ema_ms"]["min"], res[k + "_ms"]["max"] - res[k + "_ms"]["min"])
+    res["ratio_ema_to_plain_step"] = res["ema_adds_to_plain_ms"] / res["plain_ms"]["median"]
+    res["ratio_ema_to_plain_step_from_traffic"] = 12 / 29
     res["fused_clip_faster_than_torch_clip_by_more_than_spread"] = res["torch_clip_ms"]["median"] - res["fused_clip_ms"]["median"] > spread
     return res
 
