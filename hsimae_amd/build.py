@@ -55,8 +55,9 @@ def _stale(target: str, deps: list[str]) -> bool:
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
-    hdrs = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "kernels.h"), os.path.join(CSRC, "plan.h"),
-            os.path.join(HERE, "..", "include", "hsimae_hip.h")]
+    # every header makes every object stale (as kernel_source_hash() lists the directory)
+    hdrs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h"))
+    hdrs.append(os.path.join(HERE, "..", "include", "hsimae_hip.h"))
     # one object directory per flag list, so that a changed HSIMAE_HIPCC_EXTRA never links objects of another build
     objdir = os.path.join(HERE, "build", flags_hash(FLAGS))
     os.makedirs(objdir, exist_ok=True)

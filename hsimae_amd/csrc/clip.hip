@@ -4,18 +4,16 @@
 //   grad_sumsq_kernel   a FIXED grid of CLIP_GRID workgroups walks up to 8 segments {g, group, n} grid-stride: 16-byte loads over
 //                       the aligned body of each segment, the <= 3 elements before and after it one per thread of workgroup 0.
 //                       An element whose group id is 2 (frozen, or without a gradient this step: it may hold NaN) never enters
-//                       the sum.  Squares and sums are fp64 (|g| = 1e30 squares to 1e60).  Per thread four accumulators, added
-//                       pairwise; per wave the xor shuffle tree; per workgroup its four waves in order -> partials[CLIP_GRID].
+//                       the sum.  Squares and sums are fp64 (|g| = 1e30 squares to 1e60); block_sum -> partials[CLIP_GRID].
 //                       No atomics: the order of every addition is fixed by the grid, so two runs are bit-identical.
 //   clip_finish_kernel  one workgroup: thread t adds partials t, t + 256, ... in order, then the LDS tree of loss_final_kernel;
 //                       thread 0 fills the control block.
-//   adamw_groups_kernel adamw_kernel's arithmetic on g * coef (one fp32 multiply) with a learning rate and a weight decay PER GROUP
-//                       ID: up to 64 {lr, weight_decay} pairs travel in the launch and are staged into LDS.  With a control block
-//                       the bias corrections are read from it and nothing is written when ctl->apply is 0; without one coef = 1.
-//                       Any n (float4 body where the four arrays are 16-byte aligned, one element per thread behind it), group
-//                       ids per element or one id for all.  hsimae_adamw_step_ctl is this kernel with a two-entry table.
-#include "common.h"
-#include "kernels.h"
+//   adamw_groups_kernel adamw_one on g * coef with a learning rate and a weight decay PER GROUP ID: up to 64 {lr, weight_decay}
+//                       pairs travel in the launch.  With a control block the bias corrections are read from it and nothing is
+//                       written when ctl->apply is 0; without one coef = 1.  Any n, group ids per element or one id for all.
+//                       hsimae_adamw_step_ctl is this kernel with a two-entry table.
+// The table, adamw_one, block_sum and the launchers' shared checks are in optim.h.
+#include "optim.h"
 
 namespace {
 
@@ -24,8 +22,6 @@ static_assert(CLIP_GRID % 256 == 0, "clip_finish_kernel gives every thread the s
 static_assert(sizeof(hsimae_clip_ctl) == 48, "hsimae_amd/_lib.py ClipCtl mirrors this layout");
 
 struct ClipSegs { hsimae_grad_seg s[HSIMAE_CLIP_MAX_SEGS]; int n; };
-
-__device__ __forceinline__ double sq64(float x) { return (double)x * (double)x; }
 
 // a float4 of gradients with its four group ids: a lane with id 2 is not summed (a select, never a product: NaN * 0 is NaN)
 __device__ __forceinline__ void acc4(double (&a)[4], const float4 G, const uchar4 r) {
@@ -42,7 +38,6 @@ __device__ __forceinline__ uchar4 ids_at(const uint8_t* grp, int64_t i, bool ali
 }
 
 __global__ __launch_bounds__(256) void grad_sumsq_kernel(ClipSegs segs, double* partials) {
-    __shared__ double wsum[4];
     double a[4] = {0.0, 0.0, 0.0, 0.0};
     const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)CLIP_GRID * 256;
     for (int k = 0; k < segs.n; ++k) {                                          // uniform
@@ -50,8 +45,7 @@ __global__ __launch_bounds__(256) void grad_sumsq_kernel(ClipSegs segs, double* 
         const uint8_t* grp = segs.s[k].group;
         const int64_t n = segs.s[k].n;
         if (n <= 0) continue;
-        int64_t head = (int64_t)(((16u - (unsigned)((uintptr_t)g & 15u)) & 15u) >> 2);       // floats before the 16-byte boundary
-        if (head > n) head = n;
+        const int64_t head = min((int64_t)head_floats(g), n);
         const int64_t n4 = (n - head) >> 2;
         const float4* g4 = reinterpret_cast<const float4*>(g + head);
         const uint8_t* gb = grp ? grp + head : nullptr;
@@ -70,11 +64,7 @@ __global__ __launch_bounds__(256) void grad_sumsq_kernel(ClipSegs segs, double* 
             if (!grp || grp[e] != 2) a[0] += sq64(g[e]);
         }
     }
-    double s = (a[0] + a[1]) + (a[2] + a[3]);
-    for (int o = 1; o < 64; o <<= 1) s += __shfl_xor(s, o);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) partials[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+    block_sum(partials + blockIdx.x, a);
 }
 
 __global__ __launch_bounds__(256) void clip_finish_kernel(const double* partials, float max_norm, int skip_nonfinite, int step,
@@ -107,24 +97,7 @@ __global__ __launch_bounds__(256) void clip_finish_kernel(const double* partials
     if (finite) ctl->norm_max = fmaxf(ctl->norm_max, (float)norm);
 }
 
-// one element of adamw_kernel (elem.hip), its gradient scaled by coef first, with that element's own lr and weight decay
-// (wd == 0 is "no decay": the multiply is left out, as adamw_kernel leaves it out for id 1)
-__device__ __forceinline__ void adamw_one(float& p, float g, float& m, float& v, float lr, float wd, float b1, float b2, float eps,
-                                          float inv_bc1, float inv_sqrt_bc2, float coef) {
-    const float gc = g * coef;
-    float x = p;
-    if (wd != 0.f) x *= 1.f - lr * wd;
-    const float mn = m + (gc - m) * (1.f - b1);                                  // lerp, as torch does it
-    const float vn = v * b2 + gc * gc * (1.f - b2);
-    const float denom = sqrtf(vn) * inv_sqrt_bc2 + eps;
-    p = x - lr * inv_bc1 * (mn / denom);
-    m = mn; v = vn;
-}
-
-struct GroupTable { hsimae_adamw_group e[HSIMAE_ADAMW_MAX_GROUPS]; };            // by value in the launch: 512 bytes of kernarg
-static_assert(sizeof(GroupTable) == 512, "the table travels as a kernel argument");
-
-// The grouped step.  The table is staged into LDS once per workgroup (64 lanes, one entry each); an element's id indexes it.
+// The grouped step.  An element's id indexes the table staged into LDS.
 // Id 2 and every id >= ngroups are frozen: never read, never written, so the table is never indexed past ngroups.
 // ctl != NULL: coef, apply and the bias corrections come from the control block; NULL: coef = 1 and the launcher's corrections.
 __global__ __launch_bounds__(256) void adamw_groups_kernel(float* p, const float* g, float* m, float* v, const uint8_t* group,
@@ -137,11 +110,7 @@ __global__ __launch_bounds__(256) void adamw_groups_kernel(float* p, const float
         if (ctl->apply == 0) return;                                            // a skipped step writes nothing
         coef = ctl->coef; inv_bc1 = ctl->inv_bc1; inv_sqrt_bc2 = ctl->inv_sqrt_bc2;
     }
-    if (threadIdx.x < HSIMAE_ADAMW_MAX_GROUPS) {
-        const int k = threadIdx.x < (unsigned)ngroups ? (int)threadIdx.x : 0;   // entries behind ngroups are never used
-        tab[threadIdx.x] = make_float2(table.e[k].lr, table.e[k].weight_decay);
-    }
-    __syncthreads();
+    stage_table(tab, table, ngroups);
     const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
     const unsigned char gu = (unsigned char)group_uniform;
     const unsigned ng = (unsigned)ngroups;
@@ -172,8 +141,6 @@ __global__ __launch_bounds__(256) void adamw_groups_kernel(float* p, const float
     }
 }
 
-inline bool misaligned(const void* p, uintptr_t mask) { return ((uintptr_t)p & mask) != 0; }
-
 }  // namespace
 
 int hs_grad_norm(const hsimae_grad_seg* segs, int nseg, float max_norm, int skip_nonfinite, int step, float beta1, float beta2,
@@ -201,26 +168,18 @@ int hs_adamw_groups(float* p, const float* g, float* m, float* v, const unsigned
                     const hsimae_adamw_group* table, int ngroups, float b1, float b2, float eps, int step, const hsimae_clip_ctl* ctl,
                     hipStream_t s) {
     if (n < 0 || ngroups < 1 || ngroups > HSIMAE_ADAMW_MAX_GROUPS) return HS_EDIMS;
-    if (!group && group_uniform != 2 && (group_uniform < 0 || group_uniform >= ngroups)) return HS_EDIMS;   // 2 is frozen in any table
+    if (bad_group_uniform(group, group_uniform, ngroups)) return HS_EDIMS;
     if (!ctl && step < 1) return HS_EDIMS;
     if (n == 0) return HS_OK;
     if (!p || !g || !m || !v || !table) return HS_ENULL;
     GroupTable t;
-    for (int k = 0; k < HSIMAE_ADAMW_MAX_GROUPS; ++k) {
-        t.e[k] = k < ngroups ? table[k] : hsimae_adamw_group{0.f, 0.f};
-        if (k != 2 && !(t.e[k].lr >= 0.f && t.e[k].weight_decay >= 0.f)) return HS_EDIMS;   // negative or NaN; table[2] is ignored
-    }
+    if (fill_group_table(t, table, ngroups) != HS_OK) return HS_EDIMS;
     if (misaligned(p, 3) || misaligned(g, 3) || misaligned(m, 3) || misaligned(v, 3) || misaligned(ctl, 7)) return HS_EALIGN;
     if (!group && group_uniform == 2) return HS_OK;                              // all frozen: nothing to do
     float inv_bc1 = 0.f, inv_sqrt_bc2 = 0.f;                                     // read from ctl when there is one
-    if (!ctl) {
-        const double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);   // as hs_adamw forms them
-        inv_bc1 = (float)(1.0 / bc1);
-        inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
-    }
-    const bool vec = !(misaligned(p, 15) || misaligned(g, 15) || misaligned(m, 15) || misaligned(v, 15) || misaligned(group, 3));
-    const int64_t n4 = vec ? n / 4 : 0, work = vec ? n4 + 3 : n;
-    const int grid = (int)std::min<int64_t>((work + 255) / 256, 2048);
+    if (!ctl) bias_corrections(b1, b2, step, inv_bc1, inv_sqrt_bc2);
+    int64_t n4;
+    const int grid = body_and_grid({p, g, m, v}, group, n, 2048, n4);
     hipLaunchKernelGGL(adamw_groups_kernel, dim3(grid), dim3(256), 0, s, p, g, m, v, group, group_uniform, n, n4, ngroups, t, b1, b2,
                        eps, inv_bc1, inv_sqrt_bc2, ctl);
     return (int)hipGetLastError();

@@ -2,6 +2,7 @@
 // LayerNorm backward, decoder sequence assembly (fwd/bwd), normalised-pixel MSE loss + recons.
 #include "common.h"
 #include "kernels.h"
+#include "optim.h"
 #include "plan.h"
 #include <algorithm>
 #include <cmath>
@@ -497,6 +498,7 @@ __global__ __launch_bounds__(256) void loss_final_kernel(const float* partial, i
 // ------------------------------------------------------------------ fused AdamW over the flat parameter buffer
 // torch.optim.AdamW semantics (decoupled decay, bias correction), one launch for all 535 tensors
 // (Model_Pretraining.py:80-86,102).  group[i]: 0 = weight decay, 1 = no decay ('bias' / 'norm' names), 2 = frozen.
+// The arithmetic of adamw_one (optim.h) with coef = 1, written out: 1 - lr * wd is then formed once, outside the loop.
 __global__ __launch_bounds__(256) void adamw_kernel(float4* p, const float4* g, float4* m, float4* v, const uchar4* group,
                                                     int64_t n4, float lr, float b1, float b2, float eps, float wd,
                                                     float inv_bc1, float inv_sqrt_bc2) {
@@ -743,12 +745,13 @@ int hs_adamw(float* p, const float* g, float* m, float* v, const unsigned char* 
              float eps, float wd, int step, hipStream_t s) {
     if (n <= 0) return HS_OK;
     if (n % 4 || step < 1) return HS_EDIMS;
-    const double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
+    float inv_bc1, inv_sqrt_bc2;
+    bias_corrections(b1, b2, step, inv_bc1, inv_sqrt_bc2);
     const int64_t n4 = n / 4;
     const int grid = (int)std::min<int64_t>((n4 + 255) / 256, 2048);
     hipLaunchKernelGGL(adamw_kernel, dim3(grid), dim3(256), 0, s, reinterpret_cast<float4*>(p), reinterpret_cast<const float4*>(g),
                        reinterpret_cast<float4*>(m), reinterpret_cast<float4*>(v), reinterpret_cast<const uchar4*>(group), n4, lr, b1,
-                       b2, eps, wd, (float)(1.0 / bc1), (float)(1.0 / sqrt(bc2)));
+                       b2, eps, wd, inv_bc1, inv_sqrt_bc2);
     return (int)hipGetLastError();
 }
 

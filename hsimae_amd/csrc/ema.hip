@@ -7,11 +7,9 @@
 //                       its average).  ctl->apply == 0: the kernel returns before it reads either array.
 //   ema_swap_kernel     exchanges two arrays as 32-bit words, so NaN payloads travel unchanged.
 //
-// Both are adamw_groups_kernel's shape (clip.hip): a 16-byte body where both arrays are 16-byte aligned, one element per thread
-// behind it (everything when they are not), a grid of at most HSIMAE_EMA_MAX_GRID workgroups that strides over the rest.  Plain vector
-// loads and stores; no atomics, no LDS.
-#include "common.h"
-#include "kernels.h"
+// Both have the streaming shape of body_and_grid (optim.h), with at most HSIMAE_EMA_MAX_GRID workgroups.  Plain vector loads and
+// stores; no atomics, no LDS.
+#include "optim.h"
 
 namespace {
 
@@ -55,16 +53,6 @@ __global__ __launch_bounds__(256) void ema_swap_kernel(uint32_t* a, uint32_t* b,
     }
 }
 
-inline bool misaligned(const void* p, uintptr_t mask) { return ((uintptr_t)p & mask) != 0; }
-
-// n4 (float4s of the aligned body, 0 when either array is not 16-byte aligned) and the grid that covers body and tail
-inline int ema_grid(const void* a, const void* b, int64_t n, int64_t& n4) {
-    const bool vec = !(misaligned(a, 15) || misaligned(b, 15));
-    n4 = vec ? n / 4 : 0;
-    const int64_t work = vec ? n4 + 3 : n;
-    return (int)std::min<int64_t>((work + 255) / 256, EMA_MAX_GRID);
-}
-
 }  // namespace
 
 int hs_ema_update(float* ema, const float* params, int64_t n, double decay, int warmup, int step, const hsimae_clip_ctl* ctl,
@@ -74,7 +62,7 @@ int hs_ema_update(float* ema, const float* params, int64_t n, double decay, int 
     if (!ema || !params) return HS_ENULL;
     if (misaligned(ema, 3) || misaligned(params, 3) || misaligned(ctl, 7)) return HS_EALIGN;
     int64_t n4;
-    const int grid = ema_grid(ema, params, n, n4);
+    const int grid = body_and_grid({ema, params}, nullptr, n, EMA_MAX_GRID, n4);
     hipLaunchKernelGGL(ema_update_kernel, dim3(grid), dim3(256), 0, s, ema, params, n, n4, decay, warmup ? 1 : 0, step, ctl);
     return (int)hipGetLastError();
 }
@@ -87,7 +75,7 @@ int hs_ema_swap(float* a, float* b, int64_t n, hipStream_t s) {
     const uintptr_t ua = (uintptr_t)a, ub = (uintptr_t)b, bytes = (uintptr_t)n * 4;
     if (ua < ub + bytes && ub < ua + bytes) return HS_EDIMS;                     // the ranges overlap
     int64_t n4;
-    const int grid = ema_grid(a, b, n, n4);
+    const int grid = body_and_grid({a, b}, nullptr, n, EMA_MAX_GRID, n4);
     hipLaunchKernelGGL(ema_swap_kernel, dim3(grid), dim3(256), 0, s, reinterpret_cast<uint32_t*>(a), reinterpret_cast<uint32_t*>(b), n, n4);
     return (int)hipGetLastError();
 }

@@ -3,8 +3,7 @@
 //
 //   lamb_moments_kernel  one workgroup of 256 per CHUNK: at most HSIMAE_LAMB_CHUNK consecutive floats of ONE tensor.  The workgroup
 //                        finds its tensor by binary search on hsimae_lamb_tensor.chunk0 (uniform), reads p, g, m, v, writes m', v'
-//                        in place and partials[2 chunk] = sum p^2, partials[2 chunk + 1] = sum u^2 in fp64, in grad_sumsq_kernel's
-//                        order: four accumulators per thread added pairwise, the xor shuffle tree per wave, the four waves in order.
+//                        in place and partials[2 chunk] = sum p^2, partials[2 chunk + 1] = sum u^2 in fp64 (block_sum, optim.h).
 //                        16-byte accesses over the aligned body of the chunk, the <= 3 elements before and behind it one per thread.
 //   lamb_ratio_kernel    one wave per tensor: lane l adds the tensor's chunk partials l, l + 64, ... in order, then the same tree;
 //                        lane 0 writes ratios[T] = (float)sqrt(sum p^2 / sum u^2) in fp64 (1 where the tensor is not adapted).
@@ -16,8 +15,7 @@
 // frozen: nothing of the tensor is read but that byte, nothing is written, its ratio is 1.  ctl->apply == 0: all three kernels return
 // before any read of p, g, m, v and any write.  A chunk whose table entry is inconsistent writes nothing and sets *bad; the three
 // kernels apply the same test to an entry, so a tensor is stepped whole (moments, ratio, parameters) or not at all.
-#include "common.h"
-#include "kernels.h"
+#include "optim.h"
 
 namespace {
 
@@ -25,31 +23,11 @@ constexpr int CHUNK = HSIMAE_LAMB_CHUNK;
 static_assert(CHUNK == 4096, "a thread of lamb_moments_kernel holds at most four float4 of its chunk");
 static_assert(sizeof(hsimae_lamb_tensor) == 24, "hsimae_amd/_lib.py LambTensor mirrors this layout");
 
-struct GroupTable { hsimae_adamw_group e[HSIMAE_ADAMW_MAX_GROUPS]; };            // by value in the launch: 512 bytes of kernarg
-static_assert(sizeof(GroupTable) == 512, "the table travels as a kernel argument");
-
-__device__ __forceinline__ double sq64(float x) { return (double)x * (double)x; }
-
-// the update direction of one element, from the NEW moments: both kernels call this and nothing else
+// the update direction of one element, from the NEW moments (adam_moments): both kernels call this and nothing else
 __device__ __forceinline__ float lamb_u(float p, float mn, float vn, float wd, float eps, float inv_bc1, float inv_sqrt_bc2) {
     float u = (mn * inv_bc1) / (sqrtf(vn) * inv_sqrt_bc2 + eps);
     if (wd != 0.f) u += wd * p;
     return u;
-}
-
-// adamw_one's moments (clip.hip), unchanged
-__device__ __forceinline__ void lamb_moments(float g, float& m, float& v, float b1, float b2, float coef) {
-    const float gc = g * coef;
-    m = m + (gc - m) * (1.f - b1);
-    v = v * b2 + gc * gc * (1.f - b2);
-}
-
-__device__ __forceinline__ void stage_table(float2* tab, const GroupTable& table, int ngroups) {
-    if (threadIdx.x < HSIMAE_ADAMW_MAX_GROUPS) {
-        const int k = threadIdx.x < (unsigned)ngroups ? (int)threadIdx.x : 0;   // entries behind ngroups are never used
-        tab[threadIdx.x] = make_float2(table.e[k].lr, table.e[k].weight_decay);
-    }
-    __syncthreads();
 }
 
 struct ChunkOf { int tensor; int64_t start; int len; int id; };                  // len 0: nothing to do (frozen, or a bad entry)
@@ -84,25 +62,8 @@ __device__ __forceinline__ ChunkOf find_chunk(const hsimae_lamb_tensor* tensors,
     return c;
 }
 
-// floats of the chunk in front of the first 16-byte boundary; `vec` says that the four arrays share their alignment
-__device__ __forceinline__ int head_of(const float* p, int len, bool vec) {
-    if (!vec) return len;
-    const int head = (int)(((16u - (unsigned)((uintptr_t)p & 15u)) & 15u) >> 2);
-    return head < len ? head : len;
-}
-
-// grad_sumsq_kernel's order for two sums at once; thread 0 of the workgroup returns with the totals
-__device__ __forceinline__ void block_sum2(double (&a)[4], double (&b)[4], double* out) {
-    __shared__ double wsum[2][4];
-    double s = (a[0] + a[1]) + (a[2] + a[3]), t = (b[0] + b[1]) + (b[2] + b[3]);
-    for (int o = 1; o < 64; o <<= 1) { s += __shfl_xor(s, o); t += __shfl_xor(t, o); }
-    if ((threadIdx.x & 63) == 0) { wsum[0][threadIdx.x >> 6] = s; wsum[1][threadIdx.x >> 6] = t; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        out[0] = ((wsum[0][0] + wsum[0][1]) + wsum[0][2]) + wsum[0][3];
-        out[1] = ((wsum[1][0] + wsum[1][1]) + wsum[1][2]) + wsum[1][3];
-    }
-}
+// floats of the chunk in front of its 16-byte body; `vec` says that the four arrays share their alignment (else: the whole chunk)
+__device__ __forceinline__ int chunk_head(const float* p, int len, bool vec) { return vec ? min((int)head_floats(p), len) : len; }
 
 __global__ __launch_bounds__(256) void lamb_moments_kernel(const float* p, const float* g, float* m, float* v, const uint8_t* group,
                                                            int group_uniform, int64_t n_total, const hsimae_lamb_tensor* tensors,
@@ -116,7 +77,7 @@ __global__ __launch_bounds__(256) void lamb_moments_kernel(const float* p, const
     if (c.len == 0) return;                                                      // uniform
     const float wd = tab[c.id].y;
     p += c.start; g += c.start; m += c.start; v += c.start;
-    const int head = head_of(p, c.len, vec != 0), n4 = (c.len - head) >> 2, tail0 = head + 4 * n4;
+    const int head = chunk_head(p, c.len, vec != 0), n4 = (c.len - head) >> 2, tail0 = head + 4 * n4;
     double sp[4] = {0.0, 0.0, 0.0, 0.0}, su[4] = {0.0, 0.0, 0.0, 0.0};
     const float4* p4 = reinterpret_cast<const float4*>(p + head);
     const float4* g4 = reinterpret_cast<const float4*>(g + head);
@@ -136,7 +97,7 @@ __global__ __launch_bounds__(256) void lamb_moments_kernel(const float* p, const
         float* mm = &M[k].x; float* vv = &V[k].x;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            lamb_moments(gg[e], mm[e], vv[e], b1, b2, coef);
+            adam_moments(gg[e], mm[e], vv[e], b1, b2, coef);
             const float u = lamb_u(pp[e], mm[e], vv[e], wd, eps, inv_bc1, inv_sqrt_bc2);
             sp[e] += sq64(pp[e]);
             su[e] += sq64(u);
@@ -147,13 +108,13 @@ __global__ __launch_bounds__(256) void lamb_moments_kernel(const float* p, const
         const int e = t < head ? t : tail0 + (t - head);
         float mn = m[e], vn = v[e];
         const float pe = p[e];
-        lamb_moments(g[e], mn, vn, b1, b2, coef);
+        adam_moments(g[e], mn, vn, b1, b2, coef);
         const float u = lamb_u(pe, mn, vn, wd, eps, inv_bc1, inv_sqrt_bc2);
         sp[0] += sq64(pe);
         su[0] += sq64(u);
         m[e] = mn; v[e] = vn;
     }
-    block_sum2(sp, su, partials + 2 * (int64_t)blockIdx.x);
+    block_sum(partials + 2 * (int64_t)blockIdx.x, sp, su);
 }
 
 __global__ __launch_bounds__(256) void lamb_ratio_kernel(const uint8_t* group, int group_uniform, int64_t n_total,
@@ -202,7 +163,7 @@ __global__ __launch_bounds__(256) void lamb_apply_kernel(float* p, const float* 
     if (c.len == 0) return;
     const float wd = tab[c.id].y, step = tab[c.id].x * ratios[c.tensor];
     p += c.start; m += c.start; v += c.start;
-    const int head = head_of(p, c.len, vec != 0), n4 = (c.len - head) >> 2, tail0 = head + 4 * n4;
+    const int head = chunk_head(p, c.len, vec != 0), n4 = (c.len - head) >> 2, tail0 = head + 4 * n4;
     float4* p4 = reinterpret_cast<float4*>(p + head);
     const float4* m4 = reinterpret_cast<const float4*>(m + head);
     const float4* v4 = reinterpret_cast<const float4*>(v + head);
@@ -229,8 +190,6 @@ __global__ __launch_bounds__(256) void lamb_apply_kernel(float* p, const float* 
     }
 }
 
-inline bool misaligned(const void* p, uintptr_t mask) { return ((uintptr_t)p & mask) != 0; }
-
 }  // namespace
 
 int hs_lamb_step(float* p, const float* g, float* m, float* v, const unsigned char* group, int group_uniform, int64_t n,
@@ -239,12 +198,9 @@ int hs_lamb_step(float* p, const float* g, float* m, float* v, const unsigned ch
                  const hsimae_clip_ctl* ctl, hipStream_t s) {
     if (!p || !g || !m || !v || !tensors || !table || !partials || !ratios || !bad || !ctl) return HS_ENULL;
     if (n < 0 || ntensors < 1 || nchunks < 1 || ngroups < 1 || ngroups > HSIMAE_ADAMW_MAX_GROUPS) return HS_EDIMS;
-    if (!group && group_uniform != 2 && (group_uniform < 0 || group_uniform >= ngroups)) return HS_EDIMS;   // as the grouped step
+    if (bad_group_uniform(group, group_uniform, ngroups)) return HS_EDIMS;
     GroupTable t;
-    for (int k = 0; k < HSIMAE_ADAMW_MAX_GROUPS; ++k) {
-        t.e[k] = k < ngroups ? table[k] : hsimae_adamw_group{0.f, 0.f};
-        if (k != 2 && !(t.e[k].lr >= 0.f && t.e[k].weight_decay >= 0.f)) return HS_EDIMS;   // negative or NaN; table[2] is ignored
-    }
+    if (fill_group_table(t, table, ngroups) != HS_OK) return HS_EDIMS;
     if (misaligned(p, 3) || misaligned(g, 3) || misaligned(m, 3) || misaligned(v, 3) || misaligned(ratios, 3) || misaligned(bad, 3) ||
         misaligned(partials, 7) || misaligned(tensors, 7) || misaligned(ctl, 7))
         return HS_EALIGN;

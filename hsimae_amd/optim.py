@@ -138,7 +138,7 @@ class FusedAdamW:
             scale_of = lambda n: 1.0                                            # noqa: E731
         # Parameters that do not live in the model's flat buffer (DualViT's cls_head) are stepped by a stock
         # torch.optim.AdamW with their group's hyper-parameters, read from param_groups at each step.  (Not in the clipped mode.)
-        in_flat = {id(p) for p in model._plist()} if hasattr(model, "_plist") else None
+        self._in_flat = in_flat = {id(p) for p in model._plist()} if hasattr(model, "_plist") else None
         members = {(1.0, False): [], (1.0, True): []}
         flat_keys, outside = [], []
         for n, p in model.named_parameters():
@@ -209,11 +209,14 @@ class FusedAdamW:
             if self.ema_decay is not None:              # first bind: the weights before the first step; later: the average moves along
                 self.ema = flat.clone() if self.ema is None or self.ema.numel() != flat.numel() else self.ema.to(flat.device)
                 for k, p in enumerate(self._ema_params):
-                    if not p.is_contiguous() or p.dtype != torch.float32:
-                        raise RuntimeError(f"{type(self).__name__}: a parameter outside the flat buffer must be a contiguous fp32 tensor")
+                    self._need_fp32(p)
                     e = self._ema_out[k]
                     self._ema_out[k] = p.detach().reshape(-1).clone() if e is None or e.numel() != p.numel() else e.to(p.device)
             self._flat_id = flat.data_ptr()
+
+    def _need_fp32(self, p):
+        if not p.is_contiguous() or p.dtype != torch.float32:
+            raise RuntimeError(f"{type(self).__name__}: a parameter outside the flat buffer must be a contiguous fp32 tensor")
 
     def zero_grad(self, set_to_none: bool = True):
         zg = getattr(self.model, "zero_grad", None)
@@ -304,34 +307,47 @@ class FusedAdamW:
     def step(self):
         self._refuse_inside_swap("step()")
         self._bind()
-        m = self.model
-        g0 = self.param_groups[0]
+        m, g0 = self.model, self.param_groups[0]
         self.step_count += 1
-        b1, b2 = g0["betas"]
         stream = torch.cuda.current_stream(m._flat.device).cuda_stream
+        hp = (float(g0["betas"][0]), float(g0["betas"][1]), float(g0["eps"]), stream)
         group = self._sync_grads()
-        if self._clip:
-            self._step_clipped(group, float(b1), float(b2), stream)
-            m._packed_version = -1
-            self._ema_update(stream)
-            return
-        if self._defaults_agree():
-            _lib.check(_lib.load().hsimae_adamw_step(
-                m._flat.data_ptr(), m._flat_grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-                group.data_ptr(), m._flat.numel(), float(g0["lr"]), float(b1), float(b2), float(g0["eps"]),
-                float(g0["weight_decay"]), self.step_count, stream), "hsimae_adamw_step")
-        else:
-            _lib.check(_lib.load().hsimae_adamw_step_groups(
-                m._flat.data_ptr(), m._flat_grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-                group.data_ptr(), 0, m._flat.numel(), self._table(), self._ngroups, float(b1), float(b2), float(g0["eps"]),
-                self.step_count, None, stream), "hsimae_adamw_step_groups")
+        live = self._grad_norm(group, hp) if self._clip else []     # the control block decides the size of this step
+        table = self._table() if self._clip or not self._defaults_agree() else None
+        self._step_flat(group, table, hp)
+        self._step_outside(live, table, hp)
         m._packed_version = -1                    # packed bf16 images are stale now
-        if self._extra is not None:
+        self._ema_update(stream)
+
+    def _ctl_ptr(self):
+        return None if self._ctl is None else self._ctl.data_ptr()       # there is one in the clipped mode only
+
+    def _adamw_groups(self, p, g, m, v, ids, gid, n, table, hp):
+        """One hsimae_adamw_step_groups over n elements: `ids` holds an id per element, or is None and `gid` is the id of all."""
+        b1, b2, eps, stream = hp
+        _lib.check(_lib.load().hsimae_adamw_step_groups(
+            p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), None if ids is None else ids.data_ptr(), gid, n, table,
+            self._ngroups, b1, b2, eps, self.step_count, self._ctl_ptr(), stream), "hsimae_adamw_step_groups")
+
+    def _step_flat(self, group, table, hp):
+        m = self.model
+        flat, grad = m._flat, m._flat_grad
+        if table is not None:
+            self._adamw_groups(flat, grad, self.exp_avg, self.exp_avg_sq, group, 0, flat.numel(), table, hp)
+            return
+        g0, (b1, b2, eps, stream) = self.param_groups[0], hp       # one lr, one weight decay, no control block
+        _lib.check(_lib.load().hsimae_adamw_step(
+            flat.data_ptr(), grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), group.data_ptr(), flat.numel(),
+            float(g0["lr"]), b1, b2, eps, float(g0["weight_decay"]), self.step_count, stream), "hsimae_adamw_step")
+
+    def _step_outside(self, live, table, hp):
+        for k, p, g, gid in live:                  # the clipped mode: the grouped step with the parameter's id for every element
+            self._adamw_groups(p, g, self._out_m[k], self._out_v[k], None, gid, p.numel(), table, hp)
+        if self._extra is not None:                # the unclipped mode: the stock optimizer
             for ge, gi in zip(self._extra.param_groups, self._extra_of):
                 ge["lr"] = self._effective_lr(self.param_groups[gi])
                 ge["weight_decay"] = self.param_groups[gi]["weight_decay"]
             self._extra.step()
-        self._ema_update(stream)
 
     # ------------------------------------------------------------------ moving average of the weights (off by default)
     def _ema_pairs(self):
@@ -342,11 +358,9 @@ class FusedAdamW:
         control block the kernel takes the skip decision and the count of applied steps from it; without one no step is skipped."""
         if self.ema_decay is None:
             return
-        lib = _lib.load()
-        ctl = None if self._ctl is None else self._ctl.data_ptr()
         for e, p in self._ema_pairs():
-            _lib.check(lib.hsimae_ema_update(e.data_ptr(), p.data_ptr(), e.numel(), self.ema_decay, int(self.ema_warmup),
-                                             self.step_count, ctl, stream), "hsimae_ema_update")
+            _lib.check(_lib.load().hsimae_ema_update(e.data_ptr(), p.data_ptr(), e.numel(), self.ema_decay, int(self.ema_warmup),
+                                                     self.step_count, self._ctl_ptr(), stream), "hsimae_ema_update")
 
     def _need_ema(self, what):
         if self.ema_decay is None:
@@ -434,10 +448,10 @@ class FusedAdamW:
     def reset_grad_norm_max(self):
         self._ensure_ctl()["norm_max"].zero_()
 
-    def _grad_norm(self, group, b1, b2, stream):
+    def _grad_norm(self, group, hp):
         """hsimae_grad_norm over the flat gradient buffer and the `.grad` of the live parameters outside it; fills the control block.
         Returns those parameters as [(index into _outside, parameter, contiguous fp32 gradient, group id)], their moments in place."""
-        m, lib = self.model, _lib.load()
+        m, (b1, b2, _, stream) = self.model, hp
         flat = m._flat
         self._ensure_ctl(flat.device)
         segs = (_lib.GradSeg * _lib.CLIP_MAX_SEGS)()
@@ -449,8 +463,7 @@ class FusedAdamW:
                 continue
             if g.dtype != torch.float32 or not g.is_contiguous():
                 g = g.float().contiguous()
-            if not p.is_contiguous() or p.dtype != torch.float32:
-                raise RuntimeError(f"{type(self).__name__}: a parameter outside the flat buffer must be a contiguous fp32 tensor")
+            self._need_fp32(p)
             if self._out_m[k] is None or self._out_m[k].device != p.device:
                 z = torch.zeros(p.numel(), dtype=torch.float32, device=p.device)
                 self._out_m[k] = z if self._out_m[k] is None else self._out_m[k].to(p.device)
@@ -458,24 +471,9 @@ class FusedAdamW:
             live.append((k, p, g, gid))
             segs[len(live)] = _lib.GradSeg(g.data_ptr(), None, g.numel())
         max_norm = float("inf") if self.max_grad_norm is None else self.max_grad_norm
-        _lib.check(lib.hsimae_grad_norm(segs, 1 + len(live), max_norm, int(self.skip_nonfinite), self.step_count, b1, b2,
-                                        self._partials.data_ptr(), self._ctl.data_ptr(), stream), "hsimae_grad_norm")
+        _lib.check(_lib.load().hsimae_grad_norm(segs, 1 + len(live), max_norm, int(self.skip_nonfinite), self.step_count, b1, b2,
+                                                self._partials.data_ptr(), self._ctl.data_ptr(), stream), "hsimae_grad_norm")
         return live
-
-    def _step_clipped(self, group, b1, b2, stream):
-        m, lib = self.model, _lib.load()
-        flat = m._flat
-        live = self._grad_norm(group, b1, b2, stream)
-        g0 = self.param_groups[0]
-        ctl = self._ctl.data_ptr()
-        table, ng, eps = self._table(), self._ngroups, float(g0["eps"])
-        _lib.check(lib.hsimae_adamw_step_groups(
-            flat.data_ptr(), m._flat_grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), group.data_ptr(), 0,
-            flat.numel(), table, ng, b1, b2, eps, self.step_count, ctl, stream), "hsimae_adamw_step_groups")
-        for k, p, g, gid in live:
-            _lib.check(lib.hsimae_adamw_step_groups(
-                p.data_ptr(), g.data_ptr(), self._out_m[k].data_ptr(), self._out_v[k].data_ptr(), None, gid, p.numel(),
-                table, ng, b1, b2, eps, self.step_count, ctl, stream), "hsimae_adamw_step_groups")
 
     def state_dict(self):
         sd = {"step": self.step_count, "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq,
@@ -585,8 +583,7 @@ class FusedLAMB(FusedAdamW):
         if self.trust_clip is not None and not self.trust_clip > 0:
             raise ValueError(f"trust_clip must be greater than 0 (or None), got {trust_clip}")
         self.always_adapt = bool(always_adapt)
-        in_flat = {id(p) for p in model._plist()} if hasattr(model, "_plist") else None
-        self.trust_ratio_names = [n for n, p in model.named_parameters() if in_flat is None or id(p) in in_flat]
+        self.trust_ratio_names = [n for n, p in model.named_parameters() if self._in_flat is None or id(p) in self._in_flat]
         self._lamb_id = None
         self._tensors = self._lamb_partials = self._ratios = self._bad = None
         self._out_tab = [None] * len(self._outside)                # per outside parameter: (table, nchunks, partials)
@@ -644,38 +641,34 @@ class FusedLAMB(FusedAdamW):
         r = r[sel].double()
         return torch.stack([r.min(), r.max()]) if r.numel() else torch.ones(2, dtype=torch.float64, device=self._ratios.device)
 
-    @torch.no_grad()
-    def step(self):
-        self._refuse_inside_swap("step()")
-        self._bind()
-        m, lib = self.model, _lib.load()
-        flat = m._flat
-        g0 = self.param_groups[0]
-        self.step_count += 1
-        b1, b2, eps = float(g0["betas"][0]), float(g0["betas"][1]), float(g0["eps"])
-        stream = torch.cuda.current_stream(flat.device).cuda_stream
-        group = self._sync_grads()
-        live = self._grad_norm(group, b1, b2, stream)
+    def _grad_norm(self, group, hp):
+        live = super()._grad_norm(group, hp)
         for k, p, g, gid in live:                                  # a one-tensor table per live parameter outside the flat buffer
             if self._out_tab[k] is None or self._out_tab[k][0].device != p.device:
                 rows, nch = lamb_tensor_table([0], [p.numel()])
                 self._out_tab[k] = (torch.from_numpy(rows.view(np.uint8).copy()).to(p.device), nch,
                                     torch.zeros(2 * nch, dtype=torch.float64, device=p.device))
-        ctl = self._ctl.data_ptr()
-        table, ng = self._table(), self._ngroups
-        clip, adapt, bad = (self.trust_clip or 0.0), int(self.always_adapt), self._bad.data_ptr()
-        _lib.check(lib.hsimae_lamb_step(
-            flat.data_ptr(), m._flat_grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), group.data_ptr(), 0,
-            flat.numel(), self._tensors.data_ptr(), self._ntensors, self._nchunks, table, ng, b1, b2, eps, clip, adapt,
-            self._lamb_partials.data_ptr(), self._ratios.data_ptr(), bad, ctl, stream), "hsimae_lamb_step")
+        return live
+
+    def _lamb(self, p, g, m, v, ids, gid, n, tensors, ntensors, nchunks, partials, ratios_ptr, table, hp):
+        """One hsimae_lamb_step over n elements in `ntensors` tensors: `ids` holds an id per element, or is None and `gid` is the id
+        of all."""
+        b1, b2, eps, stream = hp
+        _lib.check(_lib.load().hsimae_lamb_step(
+            p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), None if ids is None else ids.data_ptr(), gid, n, tensors.data_ptr(),
+            ntensors, nchunks, table, self._ngroups, b1, b2, eps, (self.trust_clip or 0.0), int(self.always_adapt), partials.data_ptr(),
+            ratios_ptr, self._bad.data_ptr(), self._ctl_ptr(), stream), "hsimae_lamb_step")
+
+    def _step_flat(self, group, table, hp):
+        m = self.model
+        self._lamb(m._flat, m._flat_grad, self.exp_avg, self.exp_avg_sq, group, 0, m._flat.numel(), self._tensors, self._ntensors,
+                   self._nchunks, self._lamb_partials, self._ratios.data_ptr(), table, hp)
+
+    def _step_outside(self, live, table, hp):
         for k, p, g, gid in live:
             tab, nch, part = self._out_tab[k]
-            _lib.check(lib.hsimae_lamb_step(
-                p.data_ptr(), g.data_ptr(), self._out_m[k].data_ptr(), self._out_v[k].data_ptr(), None, gid, p.numel(),
-                tab.data_ptr(), 1, nch, table, ng, b1, b2, eps, clip, adapt, part.data_ptr(),
-                self._out_ratios.data_ptr() + 4 * k, bad, ctl, stream), "hsimae_lamb_step")
-        m._packed_version = -1                    # packed bf16 images are stale now
-        self._ema_update(stream)
+            self._lamb(p, g, self._out_m[k], self._out_v[k], None, gid, p.numel(), tab, 1, nch, part,
+                       self._out_ratios.data_ptr() + 4 * k, table, hp)
 
     def state_dict(self):
         sd = super().state_dict()
