@@ -19,16 +19,14 @@ namespace {
 #define CK0(expr) do { int _e0 = (expr); if (_e0) return _e0; } while (0)
 
 inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-struct BlkP {            // resolved pointers of one block
-    const float *n1w, *n1b, *bqkv, *pb, *n2w, *n2b, *w1b, *w3b, *w2b;
-    const hs_bf16 *qkv, *p, *w1, *w3, *w2, *qkvT, *pT, *w13T, *w2T;
-    const float *qf, *kf, *vf, *pf, *w1f, *w3f;     // fp32 master weights (row-major), staged as bf16 by the fused decoder backward
+struct BlkP : BlockW {   // resolved pointers of one block of a pass: what the launchers take (kernels.h) + the fp8 images
     struct I8 { const uint8_t* w; const uint8_t* s; } qkv8, p8, w1_8, w3_8, w2_8, qkvT8, pT8, w13T8, w2T8;     // MX e4m3 images (BlockPlan::gemm_fp8)
 };
 
-BlkP resolve(const BlkOff& o, const BlkW& w, const float* P, const hs_bf16* wpk, const WLayout& WL) {
+BlkP resolve(const BlkOff& o, const BlkW& w, const float* P, const hs_bf16* wpk, const WLayout& WL, int h) {
     const float* fbase = reinterpret_cast<const float*>(wpk + WL.bf16_elems);
     BlkP b;
+    b.h = h;
     b.n1w = P + o.n1w; b.n1b = P + o.n1b; b.bqkv = fbase + w.bqkv; b.pb = P + o.pb; b.n2w = P + o.n2w; b.n2b = P + o.n2b;
     b.w1b = P + o.w1b; b.w3b = P + o.w3b; b.w2b = P + o.w2b;
     b.qkv = wpk + w.qkv; b.p = wpk + w.p; b.w1 = wpk + w.w1; b.w3 = wpk + w.w3; b.w2 = wpk + w.w2;
@@ -157,25 +155,52 @@ struct Emitter {
     }
 };
 
-template <class B>                                     // BlkP, DecBlockPtrs or the ABI's hsimae_mlp_weights: the same member names
-EncMlpPtrs mlp_ptrs(const B& b, int h) {
-    EncMlpPtrs m;
-    m.n2w = b.n2w; m.n2b = b.n2b; m.w1b = b.w1b; m.w3b = b.w3b; m.w2b = b.w2b;
-    m.w1 = b.w1; m.w3 = b.w3; m.w2 = b.w2; m.w2T = b.w2T; m.w13T = b.w13T; m.h = h;
-    return m;
+// The C ABI's per-kernel weight structs as a BlockW: what a struct does not have stays NULL
+BlockW block_w(const hsimae_mlp_weights& w) {
+    BlockW b{};
+    b.n2w = w.n2w; b.n2b = w.n2b; b.w1b = w.w1b; b.w3b = w.w3b; b.w2b = w.w2b;
+    b.w1 = w.w1; b.w3 = w.w3; b.w2 = w.w2; b.w2T = w.w2T; b.w13T = w.w13T; b.h = w.hidden;
+    return b;
+}
+BlockW block_w(const hsimae_attn_block_weights& w) {
+    BlockW b{};
+    b.n1w = w.n1w; b.n1b = w.n1b; b.bqkv = w.bqkv; b.pb = w.pb; b.qkv = w.qkv; b.p = w.p; b.qkvT = w.qkvT; b.pT = w.pT;
+    return b;
+}
+BlockW block_w(const hsimae_dec_block_weights& w) {
+    BlockW b{};
+    b.n1w = w.n1w; b.n1b = w.n1b; b.bqkv = w.bqkv; b.pb = w.pb; b.n2w = w.n2w; b.n2b = w.n2b;
+    b.w1b = w.w1b; b.w3b = w.w3b; b.w2b = w.w2b;
+    b.qkv = w.qkv; b.p = w.p; b.w1 = w.w1; b.w3 = w.w3; b.w2 = w.w2; b.w2T = w.w2T;
+    b.qf = w.qf; b.kf = w.kf; b.vf = w.vf; b.pf = w.pf; b.w1f = w.w1f; b.w3f = w.w3f; b.h = w.hidden;
+    return b;
 }
 
-DecBlockPtrs dec_ptrs(const BlkP& b, int h) {
-    DecBlockPtrs d;
-    d.n1w = b.n1w; d.n1b = b.n1b; d.bqkv = b.bqkv; d.pb = b.pb; d.n2w = b.n2w; d.n2b = b.n2b;
-    d.w1b = b.w1b; d.w3b = b.w3b; d.w2b = b.w2b;
-    d.qkv = b.qkv; d.p = b.p; d.w1 = b.w1; d.w3 = b.w3; d.w2 = b.w2;
-    d.qkvT = b.qkvT; d.pT = b.pT; d.w13T = b.w13T; d.w2T = b.w2T; d.h = h;
-    d.qf = b.qf; d.kf = b.kf; d.vf = b.vf; d.pf = b.pf; d.w1f = b.w1f; d.w3f = b.w3f;
-    return d;
+// The 18 gradients of one block inside the flat gradient buffer, as the fused decoder backward commits them
+DecBlockGrads dec_grads(float* grads, const BlkOff& o, HsDet det) {
+    DecBlockGrads g;
+    g.n1w = grads + o.n1w; g.n1b = grads + o.n1b; g.qw = grads + o.qw; g.qb = grads + o.qb;
+    g.kw = grads + o.kw; g.kb = grads + o.kb; g.vw = grads + o.vw; g.vb = grads + o.vb;
+    g.pw = grads + o.pw; g.pb = grads + o.pb; g.n2w = grads + o.n2w; g.n2b = grads + o.n2b;
+    g.w1w = grads + o.w1w; g.w1b = grads + o.w1b; g.w2w = grads + o.w2w; g.w2b = grads + o.w2b;
+    g.w3w = grads + o.w3w; g.w3b = grads + o.w3b;
+    g.det = det;
+    return g;
 }
 
 GemmParams gp() { GemmParams p; std::memset(&p, 0, sizeof(p)); return p; }
+
+// Weight and bias gradient of one linear outside the blocks: dW [N][K] at grads + dW, db [N] at grads + db, from dO [M][ldo] and A [M][lda].
+// tiles: the tile count the row split is sized for (each call site's own: decoder_pred has always passed 1, whatever the decoder width)
+int wgrad_one(const void* dO, bool dO_f32, int ldo, const hs_bf16* A, int lda, int N, int K, int64_t M, int tiles, float* grads,
+              int64_t dW, int64_t db, int64_t* det_acc, hipStream_t s) {
+    WgradParams wg; std::memset(&wg, 0, sizeof(wg));
+    WgradTask& t = wg.t[0]; t.dO = dO; t.dO_f32 = dO_f32; t.ldo = ldo; t.A = A; t.lda = lda; t.N = N; t.K = K;
+    t.dW = grads + dW; t.ldw = K; t.db = grads + db;
+    wg.det_base = grads; wg.det_acc = det_acc;
+    wg.ntasks = 1; wg.M = (int)M; wg.msplit = wgrad_msplit(tiles, M);
+    return hs_wgrad(wg, s);
+}
 
 // One transformer Block forward (Models.py:303-306): 5 launches.
 // rs_a / rs_m: optional per-row DropPath factors of the attention / MLP branch (Models.py:304-305), NULL = none.
@@ -185,14 +210,18 @@ int block_fwd(const BlkP& P, const BlockPlan& pl, const float* x_in, const BlkBu
     const int d = pl.d, dp = pl.dp, heads = pl.heads, h = pl.h, hp = pl.hp, Ts = pl.Ts, nsamples = pl.nsamples;
     const int64_t M = pl.M;
     auto w8 = [&](GemmParams& q, const BlkP::I8& a) { if (pl.gemm_fp8) { q.prec = HSIMAE_PREC_FP8; q.W8 = a.w; q.S8 = a.s; } };
-    if (pl.attn_fwd == ATTN_FWD_BLK128) {
-        // LN1 + q|k|v + attention + projection + residual in one persistent kernel (attn.hip blk128_fwd_kernel)
-        CK(hs_attn_block_fwd(x_in, P.n1w, P.n1b, P.qkv, P.bqkv, P.p, P.pb, b.u, pl.save_qkv ? b.qkv : nullptr, b.o, b.lse, b.x1, rs_a, Ts,
-                             nsamples, mode, len_l, s));
-    } else if (pl.attn_fwd == ATTN_FWD_BLK256) {
-        // the same half at D = 256 (attn_wide.hip blk256_fwd_kernel: 16 waves = 16 heads, weights streamed from L2)
-        CK(hs_attn_block256_fwd(x_in, P.n1w, P.n1b, P.qkv, P.bqkv, P.p, P.pb, b.u, b.qkv, b.o, b.lse, b.x1, rs_a, Ts, nsamples, mode,
-                                len_l, s));
+    if (pl.attn_fwd != ATTN_FWD_LAYERED) {
+        AttnBlockFwd f;
+        f.x = x_in; f.u = b.u; f.qkv = b.qkv; f.o = b.o; f.lse = b.lse; f.x1 = b.x1; f.rowscale = rs_a;
+        f.Ts = Ts; f.nsamples = nsamples; f.mode = mode; f.len_l = len_l;
+        if (pl.attn_fwd == ATTN_FWD_BLK128) {
+            // LN1 + q|k|v + attention + projection + residual in one persistent kernel (attn.hip blk128_fwd_kernel)
+            if (!pl.save_qkv) f.qkv = nullptr;
+            CK(hs_attn_block_fwd(P, f, s));
+        } else {
+            // the same half at D = 256 (attn_wide.hip blk256_fwd_kernel: 16 waves = 16 heads, weights streamed from L2)
+            CK(hs_attn_block256_fwd(P, f, s));
+        }
     } else {
     p.A = x_in; p.lda = dp; p.M = (int)M; p.N = 3 * dp; p.K = dp; p.n_valid = 3 * dp; p.W = P.qkv; p.bias = P.bqkv;
     p.gamma = P.n1w; p.beta = P.n1b; p.u_out = b.u; p.ldu = dp; p.out = b.qkv; p.ldo = 3 * dp; p.ln_width = d;
@@ -208,7 +237,7 @@ int block_fwd(const BlkP& P, const BlockPlan& pl, const float* x_in, const BlkBu
     w8(p, P.p8);
     CK(hs_gemm(p, A_BF16, E_RES_F32, s));
     }
-    if (pl.mlp_fused) return hs_enc_mlp_fwd(b.x1, res2, b.x2, (int)M, d, mlp_ptrs(P, h), s, rs_m);
+    if (pl.mlp_fused) return hs_enc_mlp_fwd(b.x1, res2, b.x2, (int)M, d, P, s, rs_m);
     p = gp();
     p.A = b.x1; p.lda = dp; p.M = (int)M; p.N = hp; p.K = dp; p.n_valid = h; p.W = P.w1; p.W2 = P.w3; p.bias = P.w1b;
     p.bias2 = P.w3b; p.gamma = P.n2w; p.beta = P.n2b; p.u_out = b.u2; p.ldu = dp; p.out = b.g; p.ldo = hp;
@@ -232,14 +261,18 @@ int block_bwd(const BlkP& P, const BlockPlan& pl, const BlkOff& o, float* grads,
     const int64_t M = pl.M;
     LnBwdParams l; std::memset(&l, 0, sizeof(l));
     l.M = (int)M; l.d = d; l.ld = dp; l.det_base = grads; l.det_acc = det_acc;
+    const HsDet det{grads, reinterpret_cast<long long*>(det_acc)};
     auto w8 = [&](GemmParams& q, const BlkP::I8& a) { if (pl.gemm_fp8) { q.prec = HSIMAE_PREC_FP8; q.W8 = a.w; q.S8 = a.s; } };
     bool g1b_done = false;
     // g / dh1 / dh3 as 64-column planes (include/hsimae_hip.h, hsimae_wgrad_task) of prow rows (plan.h: the arena reserves kPlanePadRows)
     const int hp64 = rup(hp, 64), prow = pl.plane_rows;
     if (pl.mlp_fused) {
         // recompute u2 / h1 / h3 / g inside the tile; emits dx1 and the wgrad operands u2, dh1|dh3, g, bf16 dY and dx1
-        CK(hs_enc_mlp_bwd(b.x1, G0, G1, b.u2, w.dh13, b.g, w.g0b, w.g1b, (int)M, d, mlp_ptrs(P, h), grads + o.n2w,
-                          grads + o.n2b, s, rs_m, rs_a, HsDet{grads, reinterpret_cast<long long*>(det_acc)}, prow));
+        EncMlpBwd m;
+        m.x1 = b.x1; m.dy = G0; m.dx1 = G1; m.u2 = b.u2; m.dh13 = w.dh13; m.g = b.g; m.dyb = w.g0b; m.dx1b = w.g1b;
+        m.g_n2w = grads + o.n2w; m.g_n2b = grads + o.n2b; m.rs_mlp = rs_m; m.rs_attn = rs_a; m.det = det;
+        m.M = (int)M; m.d = d; m.plane_rows = prow;
+        CK(hs_enc_mlp_bwd(P, m, s));
     } else {
         p.A = G0; p.lda = dp; p.M = (int)M; p.N = hp; p.K = dp; p.n_valid = hp; p.W = P.w2T; p.out = w.dh13; p.ldo = 2 * hp;
         p.h13 = b.h13; p.ldh = 2 * hp; p.hoff = hp; p.a_rowscale = rs_m;        // DropPath: the branch saw rs_m * dY
@@ -301,18 +334,20 @@ int block_bwd(const BlkP& P, const BlockPlan& pl, const BlkOff& o, float* grads,
     AttnParams a; std::memset(&a, 0, sizeof(a));
     a.qkv = b.qkv; a.ld = 3 * dp; a.d = d; a.heads = heads; a.hd = d / heads; a.Ts = Ts; a.nsamples = nsamples;
     a.mode = mode; a.len_l = len_l; a.o = b.o; a.ldo = dp; a.lse = b.lse; a.dout = w.dob; a.lddo = dp; a.dqkv = w.dqkv; a.kv_off = dp;
-    // round 5, D = 256 (Large): dO, the attention backward, du and the LayerNorm-1 backward as ONE persistent launch
-    // (attn_wide.hip blk256_bwd_kernel), from the saved q|k|v
-    if (pl.attn_bwd == ATTN_BWD_BLK256) {
-        CK(hs_attn_block256_bwd(b.qkv, b.lse, w.g1b, G1, x_in, P.n1w, P.pT, P.qkvT, w.dqkv, dx_out, grads + o.n1w, grads + o.n1b, grads,
-                                reinterpret_cast<long long*>(det_acc), Ts, nsamples, mode, len_l, accumulate, s));
-        return run_wgrad();
-    }
-    // round 4: the same at d = 128 (attn.hip blk128_bwd_kernel); q|k|v recomputed from u when the forward did not save them
+    // dO, the attention backward, du and the LayerNorm-1 backward as ONE persistent launch: round 5 at D = 256 (Large; attn_wide.hip
+    // blk256_bwd_kernel, from the saved q|k|v), round 4 at d = 128 (attn.hip blk128_bwd_kernel; q|k|v recomputed from u when the
+    // forward did not save them)
     if (pl.attn_bwd != ATTN_BWD_LAYERED) {
-        CK(hs_attn_block_bwd(pl.save_qkv ? b.qkv : nullptr, b.u, P.qkv, P.bqkv, b.o, b.lse, w.g1b, G1, x_in, P.n1w, P.pT, P.qkvT, w.dqkv, dx_out,
-                             grads + o.n1w, grads + o.n1b, grads, reinterpret_cast<long long*>(det_acc), Ts, nsamples, mode, len_l,
-                             accumulate, s));
+        AttnBlockBwd r;
+        r.qkv = b.qkv; r.u = b.u; r.o = b.o; r.lse = b.lse; r.dx1b = w.g1b; r.dx1 = G1; r.x = x_in; r.dqkv = w.dqkv; r.dx = dx_out;
+        r.dgamma = grads + o.n1w; r.dbeta = grads + o.n1b; r.det = det;
+        r.Ts = Ts; r.nsamples = nsamples; r.mode = mode; r.len_l = len_l; r.accumulate = accumulate;
+        if (pl.attn_bwd == ATTN_BWD_BLK256) {
+            CK(hs_attn_block256_bwd(P, r, s));
+        } else {
+            if (!pl.save_qkv) r.qkv = nullptr;
+            CK(hs_attn_block_bwd(P, r, s));
+        }
         return run_wgrad();
     }
     p = gp();
@@ -388,15 +423,15 @@ int decoder_stack_fwd(const Ctx& c, const hsimae_io* io, uint32_t sc, float* pre
     const BlockPlan lay = dec_block_plan(c, sc);
     const float* z = w.yfull;
     for (int i = 0; i < g.ddepth; ++i) {
-        const BlkP bp = resolve(c.L.bd[i], c.W.bd[i], P, io->wpk, c.W);
+        const BlkP bp = resolve(c.L.bd[i], c.W.bd[i], P, io->wpk, c.W, g.hdec);
         const BlkBuf& b = w.bd[i];
         if (!dec.fused) {
             CK(block_fwd(bp, lay, z, b, 0, 9, nullptr, s));
         } else if (dec.split) {
-            CK(hs_dec_attn_fwd(z, b.x1, b.o, b.lse, c.N, g.TL, dec_ptrs(bp, g.hdec), s));
-            CK(hs_enc_mlp_fwd(b.x1, nullptr, b.x2, (int)c.Md, g.Dd, mlp_ptrs(bp, g.hdec), s));
+            CK(hs_dec_attn_fwd(z, b.x1, b.o, b.lse, c.N, g.TL, bp, s));
+            CK(hs_enc_mlp_fwd(b.x1, nullptr, b.x2, (int)c.Md, g.Dd, bp, s));
         } else {
-            CK(hs_dec_block_fwd(z, b.x1, b.x2, b.o, b.lse, c.N, g.TL, dec_ptrs(bp, g.hdec), s));
+            CK(hs_dec_block_fwd(z, b.x1, b.x2, b.o, b.lse, c.N, g.TL, bp, s));
         }
         z = b.x2;
     }
@@ -542,12 +577,12 @@ static int forward_impl(const hsimae_config* cfg, const hsimae_io* io, void* str
         const float* xb = w.x0;
         for (int i = 0; i < g.sdepth; ++i) {
             // spatial stack: attend within one kept band group (Models.py:553,556)
-            BlkP b1 = resolve(c.L.b1[i], c.W.b1[i], P, io->wpk, c.W);
+            BlkP b1 = resolve(c.L.b1[i], c.W.b1[i], P, io->wpk, c.W, g.h);
             const DropRs r1 = drop_rs(io, i, c.Me), r2d = drop_rs(io, g.sdepth + i, c.Me);
             CK(block_fwd(b1, enc, xa, w.b1[i], 1, c.len_l, nullptr, s, r1.a, r1.m));
             xa = w.b1[i].x2;
             // spectral stack: attend within one kept position (Models.py:554,559)
-            BlkP b2 = resolve(c.L.b2[i], c.W.b2[i], P, io->wpk, c.W);
+            BlkP b2 = resolve(c.L.b2[i], c.W.b2[i], P, io->wpk, c.W, g.h);
             const bool last = (i == g.sdepth - 1);
             const float* r2 = last ? xa : nullptr;                      // x1 + x2 fused into the last epilogue (Models.py:564)
             if (last && forked) {                                       // needs the spatial stack's result: rejoin first
@@ -560,7 +595,7 @@ static int forward_impl(const hsimae_config* cfg, const hsimae_io* io, void* str
         x = xb;
     }
     for (int i = 0; i < g.nfus; ++i) {
-        BlkP bp = resolve(c.L.bf[i], c.W.bf[i], P, io->wpk, c.W);
+        BlkP bp = resolve(c.L.bf[i], c.W.bf[i], P, io->wpk, c.W, g.h);
         const DropRs rf = drop_rs(io, (g.has_axis ? 2 * g.sdepth : 0) + i, c.Me);
         CK(block_fwd(bp, enc, x, w.bf[i], 0, c.len_l, nullptr, s, rf.a, rf.m));
         x = w.bf[i].x2;
@@ -616,7 +651,7 @@ static int encoder_backward(const Ctx& c, const hsimae_io* io, float* grads, hip
     const Geo& g = c.g; const float* P = io->params; const Ws& w = c.w; const PLayout& L = c.L;
     const BlockPlan enc = enc_plan(c, sc);
     for (int i = g.nfus - 1; i >= 0; --i) {
-        BlkP bp = resolve(L.bf[i], c.W.bf[i], P, io->wpk, c.W);
+        BlkP bp = resolve(L.bf[i], c.W.bf[i], P, io->wpk, c.W, g.h);
         const float* xin = (i > 0) ? w.bf[i - 1].x2 : (g.has_axis ? w.b2[g.sdepth - 1].x2 : w.x0);
         const DropRs rf = drop_rs(io, (g.has_axis ? 2 * g.sdepth : 0) + i, c.Me);
         CK(block_bwd(bp, enc, L.bf[i], grads, xin, w.bf[i], 0, c.len_l, w.G0, w.sc, w.G0, 0, s, 1, rf.a, rf.m, io->det_acc));
@@ -637,7 +672,7 @@ static int encoder_backward(const Ctx& c, const hsimae_io* io, float* grads, hip
         // for the right stream through an event); without one the side stream's ranges wait for the join
         const bool per_block = emit.bucket != nullptr || !forked;
         for (int i = g.sdepth - 1; i >= 0; --i) {
-            BlkP b2 = resolve(L.b2[i], c.W.b2[i], P, io->wpk, c.W);
+            BlkP b2 = resolve(L.b2[i], c.W.b2[i], P, io->wpk, c.W, g.h);
             const DropRs r1 = drop_rs(io, i, c.Me), r2d = drop_rs(io, g.sdepth + i, c.Me);
             const float* xin2 = (i > 0) ? w.b2[i - 1].x2 : w.x0;
             CK(block_bwd(b2, enc, L.b2[i], grads, xin2, w.b2[i], 2, c.len_l, w.G0, scr2, w.G0, 0, s2, forked ? 2 : 1, r2d.a, r2d.m, io->det_acc));
@@ -646,7 +681,7 @@ static int encoder_backward(const Ctx& c, const hsimae_io* io, float* grads, hip
                 CK((int)hipEventRecord(sd.join, sd.s));
                 CK((int)hipStreamWaitEvent(s, sd.join, 0));
             }
-            BlkP b1 = resolve(L.b1[i], c.W.b1[i], P, io->wpk, c.W);
+            BlkP b1 = resolve(L.b1[i], c.W.b1[i], P, io->wpk, c.W, g.h);
             const float* xin1 = (i > 0) ? w.b1[i - 1].x2 : w.x0;
             float* out = (i == 0) ? w.G0 : w.G2;
             CK(block_bwd(b1, enc, L.b1[i], grads, xin1, w.b1[i], 1, c.len_l, w.G2, w.sc, out, i == 0, s, forked ? 2 : 1, r1.a, r1.m, io->det_acc));
@@ -657,14 +692,8 @@ static int encoder_backward(const Ctx& c, const hsimae_io* io, float* grads, hip
             for (int i = g.sdepth - 1; i >= 0; --i) CK(emit(L.b1[i].n1w, L.b1[i].end, s));
         }
     }
-    {   // patch_embed.proj: only the kept tokens carry gradient (Models.py:528); no input gradient
-        WgradParams wg; std::memset(&wg, 0, sizeof(wg));
-        WgradTask& t = wg.t[0]; t.dO = w.G0; t.dO_f32 = 1; t.ldo = g.Dp; t.A = w.a_pe; t.lda = 96; t.N = g.D; t.K = 72;
-        t.dW = grads + L.pew; t.ldw = 72; t.db = grads + L.peb;
-        wg.det_base = grads; wg.det_acc = io->det_acc;
-        wg.ntasks = 1; wg.M = (int)c.Me; wg.msplit = wgrad_msplit((g.D + 127) / 128, c.Me);
-        CK(hs_wgrad(wg, s));
-    }
+    // patch_embed.proj: only the kept tokens carry gradient (Models.py:528); no input gradient
+    CK(wgrad_one(w.G0, true, g.Dp, w.a_pe, 96, g.D, 72, c.Me, (g.D + 127) / 128, grads, L.pew, L.peb, io->det_acc, s));
     CK(emit(0, L.peb + g.D, s));
     return HSIMAE_OK;
 }
@@ -678,14 +707,7 @@ static int decoder_backward(const Ctx& c, const hsimae_io* io, float* grads, hip
     GemmParams p = gp();
     p.A = w.dpred; p.lda = 96; p.M = (int)c.Md; p.N = g.Ddp; p.K = 96; p.n_valid = g.Dd; p.W = io->wpk + c.W.dpT; p.out = w.du; p.ldo = g.Ddp;
     CK(hs_gemm(p, A_BF16, E_F32, s));
-    {
-        WgradParams wg; std::memset(&wg, 0, sizeof(wg));
-        WgradTask& t = wg.t[0]; t.dO = w.dpred; t.dO_f32 = 0; t.ldo = 96; t.A = w.zn; t.lda = g.Ddp; t.N = 72; t.K = g.Dd;
-        t.dW = grads + L.dpw; t.ldw = g.Dd; t.db = grads + L.dpb;
-        wg.det_base = grads; wg.det_acc = io->det_acc;
-        wg.ntasks = 1; wg.M = (int)c.Md; wg.msplit = wgrad_msplit(1, c.Md);
-        CK(hs_wgrad(wg, s));
-    }
+    CK(wgrad_one(w.dpred, false, 96, w.zn, g.Ddp, 72, g.Dd, c.Md, 1, grads, L.dpw, L.dpb, io->det_acc, s));
     LnBwdParams l; std::memset(&l, 0, sizeof(l));
     l.du = w.du; l.x = zlast; l.gamma = P + L.dnw; l.dres = nullptr; l.dx = w.G0; l.dgamma = grads + L.dnw; l.dbeta = grads + L.dnb;
     l.M = (int)c.Md; l.d = g.Dd; l.ld = g.Ddp; l.det_base = grads; l.det_acc = io->det_acc;
@@ -695,22 +717,16 @@ static int decoder_backward(const Ctx& c, const hsimae_io* io, float* grads, hip
     const DecPlan dec = plan_dec(c.g.Dd, c.g.Hd, c.g.hdec, c.g.TL, sc);
     const BlockPlan lay = dec_block_plan(c, sc);
     for (int i = g.ddepth - 1; i >= 0; --i) {
-        BlkP bp = resolve(L.bd[i], c.W.bd[i], P, io->wpk, c.W);
+        BlkP bp = resolve(L.bd[i], c.W.bd[i], P, io->wpk, c.W, g.hdec);
         const float* xin = (i == 0) ? w.yfull : w.bd[i - 1].x2;
         if (dec.fused) {
-            const BlkOff& o = L.bd[i];
-            DecBlockGrads dg;
-            dg.n1w = grads + o.n1w; dg.n1b = grads + o.n1b; dg.qw = grads + o.qw; dg.qb = grads + o.qb;
-            dg.kw = grads + o.kw; dg.kb = grads + o.kb; dg.vw = grads + o.vw; dg.vb = grads + o.vb;
-            dg.pw = grads + o.pw; dg.pb = grads + o.pb; dg.n2w = grads + o.n2w; dg.n2b = grads + o.n2b;
-            dg.w1w = grads + o.w1w; dg.w1b = grads + o.w1b; dg.w2w = grads + o.w2w; dg.w2b = grads + o.w2b;
-            dg.w3w = grads + o.w3w; dg.w3b = grads + o.w3b;
-            dg.det = HsDet{grads, reinterpret_cast<long long*>(io->det_acc)};
             // MLP half then attention half, both persistent with the block's weight gradients held in registers
             // (measured equal to "row-tile kernel + wgrad operands through HBM" at d = 64, with 0.7 GB less traffic)
             // slab NULL: commit the in-register weight gradients with float atomics (rounds 1-2) instead of slab + reduce
-            CK(hs_dec_block_bwd(xin, w.bd[i].x1, w.G0, w.G1, w.G0, w.bd[i].o, w.bd[i].lse, c.N, g.TL, dec_ptrs(bp, g.hdec), dg, s,
-                                dec.slab ? w.slab : nullptr));
+            DecBlockBwd d;
+            d.x = xin; d.x1 = w.bd[i].x1; d.dy = w.G0; d.dx1_tmp = w.G1; d.dx = w.G0; d.o = w.bd[i].o; d.lse = w.bd[i].lse;
+            d.nsamples = c.N; d.Ts = g.TL; d.slab = dec.slab ? w.slab : nullptr;
+            CK(hs_dec_block_bwd(bp, dec_grads(grads, L.bd[i], HsDet{grads, reinterpret_cast<long long*>(io->det_acc)}), d, s));
         } else {
             CK(block_bwd(bp, lay, L.bd[i], grads, xin, w.bd[i], 0, 9, w.G0, w.sc, w.G0, 0, s, 1, nullptr, nullptr, io->det_acc));
         }
@@ -723,15 +739,8 @@ static int decoder_backward(const Ctx& c, const hsimae_io* io, float* grads, hip
     p = gp();
     p.A = w.dyb; p.lda = g.Ddp; p.M = (int)c.Me; p.N = g.Dp; p.K = g.Ddp; p.n_valid = g.D; p.W = io->wpk + c.W.deT; p.out = w.du; p.ldo = g.Dp;
     CK(hs_gemm(p, A_BF16, E_F32, s));
-    {
-        WgradParams wg; std::memset(&wg, 0, sizeof(wg));
-        WgradTask& t = wg.t[0]; t.dO = w.dyb; t.dO_f32 = 0; t.ldo = g.Ddp; t.A = w.lat; t.lda = g.Dp; t.N = g.Dd; t.K = g.D;
-        t.dW = grads + L.dew; t.ldw = g.D; t.db = grads + L.deb;
-        wg.det_base = grads; wg.det_acc = io->det_acc;
-        wg.ntasks = 1; wg.M = (int)c.Me; wg.msplit = wgrad_msplit(((g.Dd + 127) / 128) * ((g.D + 127) / 128), c.Me);
-        CK(hs_wgrad(wg, s));
-    }
-    return HSIMAE_OK;
+    return wgrad_one(w.dyb, false, g.Ddp, w.lat, g.Dp, g.Dd, g.D, c.Me, ((g.Dd + 127) / 128) * ((g.D + 127) / 128), grads, L.dew, L.deb,
+                     io->det_acc, s);
 }
 
 // Backward of `norm` (Models.py:570 / 892): du [Me][Dp] -> d(x of the last encoder block) in w.G0
@@ -744,56 +753,54 @@ static int norm_backward(const Ctx& c, const hsimae_io* io, const float* du, flo
     return hs_ln_bwd(l, s);
 }
 
+// What the backward entry points share: the context, the schedule that the forward recorded for this arena (never the environment's
+// word now), the zeroed fixed-point shadow sums of deterministic mode and the range reporter.  stacks: which of the forward's records
+// the pass needs; have_args: the entry point's own required pointers are all there.
+enum Stacks { ENCODER = 1, DECODER = 2 };
+struct BwdPass { Ctx c; uint32_t sc_enc = 0, sc_dec = 0; hipStream_t s = nullptr; Emitter emit{}; };
+static int begin_backward(BwdPass& b, const hsimae_config* cfg, const hsimae_io* io, int stacks, bool have_args, float* grads,
+                          hsimae_bucket_cb cb, void* user, void* stream) {
+    CK(make_ctx(cfg, io, b.c, true));
+    if (!grads || !have_args || ((stacks & DECODER) && !io->ids_restore)) return HSIMAE_ENULL;
+    CK(lookup_sched(io->workspace, (stacks & ENCODER) != 0, (stacks & DECODER) != 0, b.sc_enc, b.sc_dec));
+    b.s = S(stream);
+    if (io->det_acc) CK((int)hipMemsetAsync(io->det_acc, 0, (size_t)b.c.L.total * 8, b.s));
+    b.emit = Emitter{cb, user, cb ? S(io->bucket_stream) : nullptr, 0, grads, io->det_acc};
+    return HSIMAE_OK;
+}
+
 int hsimae_backward(const hsimae_config* cfg, const hsimae_io* io, float* grads, hsimae_bucket_cb cb, void* user,
                     void* stream) {
-    Ctx c; CK(make_ctx(cfg, io, c, true));
-    if (!grads || !io->ids_restore) return HSIMAE_ENULL;
-    uint32_t sc_enc = 0, sc_dec = 0;                  // what the forward that filled this arena ran (never the environment's word now)
-    CK(lookup_sched(io->workspace, true, true, sc_enc, sc_dec));
-    hipStream_t s = S(stream);
-    if (io->det_acc) CK((int)hipMemsetAsync(io->det_acc, 0, (size_t)c.L.total * 8, s));     // deterministic mode: fixed-point shadow sums
-    const Geo& g = c.g; const Ws& w = c.w; const PLayout& L = c.L;
-    Emitter emit{cb, user, cb ? S(io->bucket_stream) : nullptr, 0, grads, io->det_acc};
-    CK(decoder_backward(c, io, grads, s, emit, sc_dec));
-    CK(norm_backward(c, io, w.du, grads, s));
-    CK(emit(L.nw, L.deb + g.Dd, s));
-    return encoder_backward(c, io, grads, s, emit, sc_enc);
+    BwdPass b; CK(begin_backward(b, cfg, io, ENCODER | DECODER, true, grads, cb, user, stream));
+    const Ctx& c = b.c; const Geo& g = c.g; const PLayout& L = c.L;
+    CK(decoder_backward(c, io, grads, b.s, b.emit, b.sc_dec));
+    CK(norm_backward(c, io, c.w.du, grads, b.s));
+    CK(b.emit(L.nw, L.deb + g.Dd, b.s));
+    return encoder_backward(c, io, grads, b.s, b.emit, b.sc_enc);
 }
 
 int hsimae_decode_backward(const hsimae_config* cfg, const hsimae_io* io, const float* dpred, float* dlatent, float* grads,
                            hsimae_bucket_cb cb, void* user, void* stream) {
-    Ctx c; CK(make_ctx(cfg, io, c, true));
-    if (!grads || !dpred || !dlatent || !io->ids_restore) return HSIMAE_ENULL;
-    uint32_t sc_enc = 0, sc_dec = 0;
-    CK(lookup_sched(io->workspace, false, true, sc_enc, sc_dec));
-    hipStream_t s = S(stream);
-    if (io->det_acc) CK((int)hipMemsetAsync(io->det_acc, 0, (size_t)c.L.total * 8, s));     // deterministic mode: fixed-point shadow sums
-    const Geo& g = c.g; const Ws& w = c.w; const PLayout& L = c.L;
+    BwdPass b; CK(begin_backward(b, cfg, io, DECODER, dpred && dlatent, grads, cb, user, stream));
+    const Ctx& c = b.c; const Geo& g = c.g; const Ws& w = c.w; const PLayout& L = c.L; hipStream_t s = b.s;
     CK(hs_rows_pad_bf16(dpred, w.dpred, c.Md, 72, 96, s));
-    Emitter emit{cb, user, cb ? S(io->bucket_stream) : nullptr, 0, grads, io->det_acc};
-    CK(decoder_backward(c, io, grads, s, emit, sc_dec));
-    CK(emit(L.dew, L.deb + g.Dd, s));
+    CK(decoder_backward(c, io, grads, s, b.emit, b.sc_dec));
+    CK(b.emit(L.dew, L.deb + g.Dd, s));
     return (int)hipMemcpy2DAsync(dlatent, (size_t)g.D * 4, w.du, (size_t)g.Dp * 4, (size_t)g.D * 4, (size_t)c.Me, hipMemcpyDeviceToDevice, s);
 }
 
 int hsimae_encode_backward(const hsimae_config* cfg, const hsimae_io* io, const float* dlatent, float* grads,
                            hsimae_bucket_cb cb, void* user, void* stream) {
-    Ctx c; CK(make_ctx(cfg, io, c, true));
-    if (!grads || !dlatent) return HSIMAE_ENULL;
-    uint32_t sc_enc = 0, sc_dec = 0;
-    CK(lookup_sched(io->workspace, true, false, sc_enc, sc_dec));
-    hipStream_t s = S(stream);
-    if (io->det_acc) CK((int)hipMemsetAsync(io->det_acc, 0, (size_t)c.L.total * 8, s));     // deterministic mode: fixed-point shadow sums
-    const Geo& g = c.g; const Ws& w = c.w; const PLayout& L = c.L;
+    BwdPass b; CK(begin_backward(b, cfg, io, ENCODER, dlatent != nullptr, grads, cb, user, stream));
+    const Ctx& c = b.c; const Geo& g = c.g; const Ws& w = c.w; const PLayout& L = c.L; hipStream_t s = b.s;
     const float* dlat = dlatent;
     if (g.Dp != g.D) {          // rows stored wider than the model: the caller's [Me][D] gradient into a padded buffer
         CK((int)hipMemcpy2DAsync(w.du, (size_t)g.Dp * 4, dlatent, (size_t)g.D * 4, (size_t)g.D * 4, (size_t)c.Me, hipMemcpyDeviceToDevice, s));
         dlat = w.du;
     }
     CK(norm_backward(c, io, dlat, grads, s));
-    Emitter emit{cb, user, cb ? S(io->bucket_stream) : nullptr, 0, grads, io->det_acc};
-    CK(emit(L.nw, L.nb + g.D, s));
-    return encoder_backward(c, io, grads, s, emit, sc_enc);
+    CK(b.emit(L.nw, L.nb + g.D, s));
+    return encoder_backward(c, io, grads, s, b.emit, b.sc_enc);
 }
 
 // ---------------------------------------------------------------------- per-kernel entry points
@@ -813,7 +820,7 @@ int hsimae_enc_mlp_fwd(const float* x1, const float* res2, float* x2, int32_t M,
     if (M <= 0) return HSIMAE_OK;
     if (!x1 || !x2 || !w) return HSIMAE_ENULL;
     if (!mlp_fusable(d, w->hidden)) return HSIMAE_EUNSUPPORTED;
-    return hs_enc_mlp_fwd(x1, res2, x2, M, d, mlp_ptrs(*w, w->hidden), S(stream), rowscale);
+    return hs_enc_mlp_fwd(x1, res2, x2, M, d, block_w(*w), S(stream), rowscale);
 }
 int hsimae_enc_mlp_bwd(const float* x1, const float* dy, float* dx1, hs_bf16* u2, hs_bf16* dh13, hs_bf16* g, hs_bf16* dyb,
                        hs_bf16* dx1b, int32_t M, int32_t d, const hsimae_mlp_weights* w, float* g_n2w, float* g_n2b,
@@ -824,26 +831,20 @@ int hsimae_enc_mlp_bwd(const float* x1, const float* dy, float* dx1, hs_bf16* u2
     // operand outputs are optional as groups: {u2, dyb} and {dh13, g} (NULL = not written: the data path alone), dx1b on its own
     if ((!u2) != (!dyb) || (!dh13) != (!g)) return HSIMAE_ENULL;
     if (!mlp_fusable(d, w->hidden)) return HSIMAE_EUNSUPPORTED;
-    return hs_enc_mlp_bwd(x1, dy, dx1, u2, dh13, g, dyb, dx1b, M, d, mlp_ptrs(*w, w->hidden), g_n2w, g_n2b, S(stream), rs_mlp, rs_attn,
-                          HsDet{nullptr, nullptr}, plane_rows);
-}
-static DecBlockPtrs dec_from_abi(const hsimae_dec_block_weights* w) {
-    DecBlockPtrs d; std::memset(&d, 0, sizeof(d));
-    d.n1w = w->n1w; d.n1b = w->n1b; d.bqkv = w->bqkv; d.pb = w->pb; d.n2w = w->n2w; d.n2b = w->n2b;
-    d.w1b = w->w1b; d.w3b = w->w3b; d.w2b = w->w2b;
-    d.qkv = w->qkv; d.p = w->p; d.w1 = w->w1; d.w3 = w->w3; d.w2 = w->w2; d.w2T = w->w2T;
-    d.qf = w->qf; d.kf = w->kf; d.vf = w->vf; d.pf = w->pf; d.w1f = w->w1f; d.w3f = w->w3f; d.h = w->hidden;
-    return d;
+    EncMlpBwd m;
+    m.x1 = x1; m.dy = dy; m.dx1 = dx1; m.u2 = u2; m.dh13 = dh13; m.g = g; m.dyb = dyb; m.dx1b = dx1b; m.g_n2w = g_n2w; m.g_n2b = g_n2b;
+    m.rs_mlp = rs_mlp; m.rs_attn = rs_attn; m.det = HsDet{nullptr, nullptr}; m.M = M; m.d = d; m.plane_rows = plane_rows;
+    return hs_enc_mlp_bwd(block_w(*w), m, S(stream));
 }
 int hsimae_dec_block_fwd(const hsimae_dec_block_weights* w, const float* x, float* x1, float* x2, hs_bf16* o, float* lse,
                          int32_t nsamples, int32_t Ts, int32_t split, void* stream) {
     if (nsamples <= 0) return HSIMAE_OK;
     if (!w || !x || !x1 || !x2 || !o || !lse) return HSIMAE_ENULL;
     if (!dec_fusable(kDecD, kDecHeads, w->hidden, Ts)) return HSIMAE_EUNSUPPORTED;
-    const DecBlockPtrs d = dec_from_abi(w);
+    const BlockW d = block_w(*w);
     if (split) {
         CK(hs_dec_attn_fwd(x, x1, o, lse, nsamples, Ts, d, S(stream)));
-        return hs_enc_mlp_fwd(x1, nullptr, x2, nsamples * Ts, kDecD, mlp_ptrs(d, d.h), S(stream));      // (d.w13T is NULL: forward only)
+        return hs_enc_mlp_fwd(x1, nullptr, x2, nsamples * Ts, kDecD, d, S(stream));      // (d.w13T is NULL: forward only)
     }
     return hs_dec_block_fwd(x, x1, x2, o, lse, nsamples, Ts, d, S(stream));
 }
@@ -855,11 +856,10 @@ int hsimae_dec_block_bwd(const hsimae_dec_block_weights* w, const hsimae_dec_blo
     if (nsamples <= 0) return HSIMAE_OK;
     if (!w || !g || !x || !x1 || !dy || !dx1_tmp || !dx || !o || !lse) return HSIMAE_ENULL;
     if (!dec_fusable(kDecD, kDecHeads, w->hidden, Ts)) return HSIMAE_EUNSUPPORTED;
-    DecBlockGrads dg;
-    dg.n1w = g->n1w; dg.n1b = g->n1b; dg.qw = g->qw; dg.qb = g->qb; dg.kw = g->kw; dg.kb = g->kb; dg.vw = g->vw; dg.vb = g->vb;
-    dg.pw = g->pw; dg.pb = g->pb; dg.n2w = g->n2w; dg.n2b = g->n2b; dg.w1w = g->w1w; dg.w1b = g->w1b; dg.w2w = g->w2w;
-    dg.w2b = g->w2b; dg.w3w = g->w3w; dg.w3b = g->w3b; dg.det = HsDet{nullptr, nullptr};
-    return hs_dec_block_bwd(x, x1, dy, dx1_tmp, dx, o, lse, nsamples, Ts, dec_from_abi(w), dg, S(stream), slab);
+    DecBlockBwd d;
+    d.x = x; d.x1 = x1; d.dy = dy; d.dx1_tmp = dx1_tmp; d.dx = dx; d.o = o; d.lse = lse; d.nsamples = nsamples; d.Ts = Ts; d.slab = slab;
+    // (DecBlockGrads is the ABI's gradient struct + the deterministic-commit pair: none through this entry point)
+    return hs_dec_block_bwd(block_w(*w), DecBlockGrads{*g, HsDet{nullptr, nullptr}}, d, S(stream));
 }
 int hsimae_attn_fwd(const hsimae_attn_params* p, void* stream) { return p ? hs_attn_fwd(*p, S(stream)) : HSIMAE_ENULL; }
 int hsimae_attn_bwd(const hsimae_attn_params* p, void* stream) { return p ? hs_attn_bwd(*p, S(stream)) : HSIMAE_ENULL; }
@@ -885,12 +885,12 @@ int hsimae_attn_block_fwd(const hsimae_attn_block_weights* w, const float* x, hs
     if (nsamples == 0) return HSIMAE_OK;
     CK(attn_block_check(w, d, heads, Ts, nsamples, mode, len_l, {x, u, o, lse, x1}));
     if (qkv && (reinterpret_cast<uintptr_t>(qkv) & 15)) return HSIMAE_EALIGN;
-    if (d == 128)
-        return hs_attn_block_fwd(x, w->n1w, w->n1b, w->qkv, w->bqkv, w->p, w->pb, u, qkv, o, lse, x1, rowscale, Ts, nsamples, mode, len_l,
-                                 S(stream));
+    AttnBlockFwd f;
+    f.x = x; f.u = u; f.qkv = qkv; f.o = o; f.lse = lse; f.x1 = x1; f.rowscale = rowscale;
+    f.Ts = Ts; f.nsamples = nsamples; f.mode = mode; f.len_l = len_l;
+    if (d == 128) return hs_attn_block_fwd(block_w(*w), f, S(stream));
     if (!qkv) return HSIMAE_EUNSUPPORTED;                // blk256_fwd always saves q|k|v (its backward reads them)
-    return hs_attn_block256_fwd(x, w->n1w, w->n1b, w->qkv, w->bqkv, w->p, w->pb, u, qkv, o, lse, x1, rowscale, Ts, nsamples, mode, len_l,
-                                S(stream));
+    return hs_attn_block256_fwd(block_w(*w), f, S(stream));
 }
 int hsimae_attn_block_bwd(const hsimae_attn_block_weights* w, const hs_bf16* qkv, const hs_bf16* u, const hs_bf16* o, const float* lse,
                           const hs_bf16* dx1b, const float* dx1, const float* x, hs_bf16* dqkv, float* dx, float* dgamma, float* dbeta,
@@ -906,13 +906,11 @@ int hsimae_attn_block_bwd(const hsimae_attn_block_weights* w, const hs_bf16* qkv
     hipStream_t s = S(stream);
     // deterministic: the kernel commits dgamma | dbeta into det_acc[0, 2 d) (offsets from dgamma), converted and added below
     if (det_acc) CK((int)hipMemsetAsync(det_acc, 0, sizeof(int64_t) * 2 * d, s));
-    long long* acc = reinterpret_cast<long long*>(det_acc);
-    if (d == 128)
-        CK(hs_attn_block_bwd(qkv, u, w->qkv, w->bqkv, o, lse, dx1b, dx1, x, w->n1w, w->pT, w->qkvT, dqkv, dx, dgamma, dbeta, dgamma, acc,
-                             Ts, nsamples, mode, len_l, accumulate, s));
-    else
-        CK(hs_attn_block256_bwd(qkv, lse, dx1b, dx1, x, w->n1w, w->pT, w->qkvT, dqkv, dx, dgamma, dbeta, dgamma, acc, Ts, nsamples, mode,
-                                len_l, accumulate, s));
+    AttnBlockBwd r;
+    r.qkv = qkv; r.u = u; r.o = o; r.lse = lse; r.dx1b = dx1b; r.dx1 = dx1; r.x = x; r.dqkv = dqkv; r.dx = dx;
+    r.dgamma = dgamma; r.dbeta = dbeta; r.det = HsDet{dgamma, reinterpret_cast<long long*>(det_acc)};
+    r.Ts = Ts; r.nsamples = nsamples; r.mode = mode; r.len_l = len_l; r.accumulate = accumulate;
+    CK(d == 128 ? hs_attn_block_bwd(block_w(*w), r, s) : hs_attn_block256_bwd(block_w(*w), r, s));
     return det_acc ? hs_det_convert(det_acc, dgamma, 2 * d, s) : HSIMAE_OK;
 }
 int hsimae_wgrad(const hsimae_wgrad_params* p, void* stream) { return p ? hs_wgrad(*p, S(stream)) : HSIMAE_ENULL; }

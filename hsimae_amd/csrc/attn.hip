@@ -696,8 +696,7 @@ int launch_blk128(const Blk128Args& a, hipStream_t s) {
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)L::TOTAL); attr_set = true; }
     // persistent, one 8-wave workgroup per CU: the weights (64 registers) + the attention state need ~156 registers;
     // forced to 128 (two workgroups per CU) the kernel spills 24-68 of them and is 20 % slower.  At most 256 workgroups.
-    static int wgs = 0;
-    if (!wgs) wgs = 256;
+    constexpr int wgs = 256;
     const int groups = (a.nsamples + SPW - 1) / SPW;
     hipLaunchKernelGGL((blk128_fwd_kernel<NT, SPW>), dim3(groups < wgs ? groups : wgs), dim3(512), (size_t)L::TOTAL, s, a);
     return (int)hipGetLastError();
@@ -1190,8 +1189,7 @@ int launch_blk128_bwd(const Blk128BwdArgs& a, hipStream_t s) {
     static bool attr_set = false;
     if (!attr_set) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(blk128_bwd_kernel<NT, SPW, RC>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)L::TOTAL); attr_set = true; }
-    static int wgs = 0;
-    if (!wgs) wgs = 256;
+    constexpr int wgs = 256;                  // persistent, one 8-wave workgroup per CU, as the forward
     const int groups = (a.nsamples + SPW - 1) / SPW;
     hipLaunchKernelGGL((blk128_bwd_kernel<NT, SPW, RC>), dim3(groups < wgs ? groups : wgs), dim3(512), (size_t)L::TOTAL, s, a);
     return (int)hipGetLastError();
@@ -1271,33 +1269,29 @@ int hs_attn_bwd(const AttnParams& p, hipStream_t s) { return dispatch<true>(p, s
 // the shape it selects the kernel for is the one instantiated here (NT <= 2 tiles of 16 tokens, 8 waves = 8 heads of 16).
 static_assert(hsplan::kAttn128D == BIR && hsplan::kAttn128D == 16 * hsplan::kAttn128Heads,
               "plan.h attn128_fusable must select exactly the shape blk128_fwd / blk128_bwd are instantiated for");
-int hs_attn_block_fwd(const float* x, const float* n1w, const float* n1b, const hs_bf16* wqkv, const float* bqkv, const hs_bf16* wp,
-                      const float* pb, hs_bf16* u, hs_bf16* qkv, hs_bf16* o, float* lse, float* x1, const float* rowscale, int Ts,
-                      int nsamples, int mode, int len_l, hipStream_t s) {
-    if (nsamples <= 0) return HS_OK;
-    if (Ts < 1 || Ts > hsplan::kAttnMaxTs) return HS_EUNSUPPORTED;
+int hs_attn_block_fwd(const BlockW& w, const AttnBlockFwd& p, hipStream_t s) {
+    if (p.nsamples <= 0) return HS_OK;
+    if (p.Ts < 1 || p.Ts > hsplan::kAttnMaxTs) return HS_EUNSUPPORTED;
     Blk128Args a;
-    a.x = x; a.n1w = n1w; a.n1b = n1b; a.wqkv = wqkv; a.bqkv = bqkv; a.wp = wp; a.pb = pb; a.u = u; a.qkv = qkv; a.o = o;
-    a.lse = lse; a.x1 = x1; a.rowscale = rowscale; a.Ts = Ts; a.nsamples = nsamples; a.mode = mode; a.len_l = len_l;
+    a.x = p.x; a.n1w = w.n1w; a.n1b = w.n1b; a.wqkv = w.qkv; a.bqkv = w.bqkv; a.wp = w.p; a.pb = w.pb; a.u = p.u; a.qkv = p.qkv; a.o = p.o;
+    a.lse = p.lse; a.x1 = p.x1; a.rowscale = p.rowscale; a.Ts = p.Ts; a.nsamples = p.nsamples; a.mode = p.mode; a.len_l = p.len_l;
     // two samples in hand per iteration (one: 84 instead of 74 us in round 3; three measured 0.5 % slower than two)
-    return Ts <= hsplan::kAttnTile ? launch_blk128<1, 2>(a, s) : launch_blk128<2, 2>(a, s);
+    return p.Ts <= hsplan::kAttnTile ? launch_blk128<1, 2>(a, s) : launch_blk128<2, 2>(a, s);
 }
 
 // dO + attention backward + du + LayerNorm-1 backward in one launch (see blk128_bwd_kernel)
-int hs_attn_block_bwd(const hs_bf16* qkv, const hs_bf16* u, const hs_bf16* wqkv, const float* bqkv, const hs_bf16* o, const float* lse,
-                      const hs_bf16* dx1b, const float* dx1, const float* x, const float* gamma, const hs_bf16* wpT, const hs_bf16* wqkvT,
-                      hs_bf16* dqkv, float* dx, float* dgamma, float* dbeta, const float* det_base, long long* det_acc, int Ts,
-                      int nsamples, int mode, int len_l, int accumulate, hipStream_t s) {
-    if (nsamples <= 0) return HS_OK;
-    if (Ts < 1 || Ts > hsplan::kAttnMaxTs) return HS_EUNSUPPORTED;
-    const bool rc = qkv == nullptr;                  // no saved q|k|v: recompute them from u
-    if (rc && !(u && wqkv && bqkv)) return HS_EUNSUPPORTED;
+int hs_attn_block_bwd(const BlockW& w, const AttnBlockBwd& p, hipStream_t s) {
+    if (p.nsamples <= 0) return HS_OK;
+    if (p.Ts < 1 || p.Ts > hsplan::kAttnMaxTs) return HS_EUNSUPPORTED;
+    const bool rc = p.qkv == nullptr;                // no saved q|k|v: recompute them from u
+    if (rc && !(p.u && w.qkv && w.bqkv)) return HS_EUNSUPPORTED;
     Blk128BwdArgs a;
-    a.qkv = qkv; a.u = u; a.wqkv = wqkv; a.bqkv = bqkv; a.o = o; a.lse = lse; a.dx1b = dx1b; a.dx1 = dx1; a.x = x; a.gamma = gamma;
-    a.wpT = wpT; a.wqkvT = wqkvT; a.dqkv = dqkv; a.dx = dx; a.dgamma = dgamma; a.dbeta = dbeta; a.det_base = det_base; a.det_acc = det_acc;
-    a.Ts = Ts; a.nsamples = nsamples; a.mode = mode; a.len_l = len_l; a.accumulate = accumulate;
-    if (rc) return Ts <= hsplan::kAttnTile ? launch_blk128_bwd<1, 2, true>(a, s) : launch_blk128_bwd<2, 2, true>(a, s);
-    return Ts <= hsplan::kAttnTile ? launch_blk128_bwd<1, 2, false>(a, s) : launch_blk128_bwd<2, 2, false>(a, s);
+    a.qkv = p.qkv; a.u = p.u; a.wqkv = w.qkv; a.bqkv = w.bqkv; a.o = p.o; a.lse = p.lse; a.dx1b = p.dx1b; a.dx1 = p.dx1; a.x = p.x;
+    a.gamma = w.n1w; a.wpT = w.pT; a.wqkvT = w.qkvT; a.dqkv = p.dqkv; a.dx = p.dx; a.dgamma = p.dgamma; a.dbeta = p.dbeta;
+    a.det_base = p.det.base; a.det_acc = p.det.acc;
+    a.Ts = p.Ts; a.nsamples = p.nsamples; a.mode = p.mode; a.len_l = p.len_l; a.accumulate = p.accumulate;
+    if (rc) return p.Ts <= hsplan::kAttnTile ? launch_blk128_bwd<1, 2, true>(a, s) : launch_blk128_bwd<2, 2, true>(a, s);
+    return p.Ts <= hsplan::kAttnTile ? launch_blk128_bwd<1, 2, false>(a, s) : launch_blk128_bwd<2, 2, false>(a, s);
 }
 
 HS_UNIT_VARIANT_BITS(attn)

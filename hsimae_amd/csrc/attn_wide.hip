@@ -724,8 +724,7 @@ int launch_blk256_bwd(const Blk256BwdArgs& a, hipStream_t s) {
     static bool attr_set = false;
     if (!attr_set) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(blk256_bwd_kernel<NT, SPW>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)L::TOTAL); attr_set = true; }
-    static int wgs = 0;                       // persistent, one 16-wave workgroup per CU, at most 256 of them
-    if (!wgs) wgs = 256;
+    constexpr int wgs = 256;                  // persistent, one 16-wave workgroup per CU, at most 256 of them
     const int groups = (a.nsamples + SPW - 1) / SPW;
     hipLaunchKernelGGL((blk256_bwd_kernel<NT, SPW>), dim3(groups < wgs ? groups : wgs), dim3(NTHW), (size_t)L::TOTAL, s, a);
     return (int)hipGetLastError();
@@ -737,8 +736,7 @@ int launch_blk256(const Blk256Args& a, hipStream_t s) {
     static bool attr_set = false;
     if (!attr_set) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(blk256_fwd_kernel<NT, SPW>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)L::TOTAL); attr_set = true; }
-    static int wgs = 0;                       // persistent, one 16-wave workgroup per CU, at most 256 of them
-    if (!wgs) wgs = 256;
+    constexpr int wgs = 256;                  // persistent, one 16-wave workgroup per CU, at most 256 of them
     const int groups = (a.nsamples + SPW - 1) / SPW;
     hipLaunchKernelGGL((blk256_fwd_kernel<NT, SPW>), dim3(groups < wgs ? groups : wgs), dim3(NTHW), (size_t)L::TOTAL, s, a);
     return (int)hipGetLastError();
@@ -752,30 +750,25 @@ static_assert(hsplan::kAttn256D == DW && hsplan::kAttn256Heads == HW,
               "plan.h attn256_fusable must select exactly the shape blk256_fwd / blk256_bwd are instantiated for");
 
 // dO + attention backward + du + LayerNorm-1 backward at D = 256 in one launch (blk256_bwd_kernel)
-int hs_attn_block256_bwd(const hs_bf16* qkv, const float* lse, const hs_bf16* dx1b, const float* dx1, const float* x, const float* gamma,
-                         const hs_bf16* wpT, const hs_bf16* wqkvT, hs_bf16* dqkv, float* dx, float* dgamma, float* dbeta,
-                         const float* det_base, long long* det_acc, int Ts, int nsamples, int mode, int len_l, int accumulate,
-                         hipStream_t s) {
-    if (nsamples <= 0) return HS_OK;
-    if (Ts < 1 || Ts > hsplan::kAttnMaxTs) return HS_EUNSUPPORTED;
-    if ((int64_t)nsamples * Ts * 3 * DW >= (1ll << 31)) return HS_EUNSUPPORTED;      // 32-bit element offsets inside the kernel
+int hs_attn_block256_bwd(const BlockW& w, const AttnBlockBwd& p, hipStream_t s) {
+    if (p.nsamples <= 0) return HS_OK;
+    if (p.Ts < 1 || p.Ts > hsplan::kAttnMaxTs) return HS_EUNSUPPORTED;
+    if ((int64_t)p.nsamples * p.Ts * 3 * DW >= (1ll << 31)) return HS_EUNSUPPORTED;      // 32-bit element offsets inside the kernel
     Blk256BwdArgs a;
-    a.qkv = qkv; a.lse = lse; a.dx1b = dx1b; a.dx1 = dx1; a.x = x; a.gamma = gamma; a.wpT = wpT; a.wqkvT = wqkvT; a.dqkv = dqkv; a.dx = dx;
-    a.dgamma = dgamma; a.dbeta = dbeta; a.det_base = det_base; a.det_acc = det_acc;
-    a.Ts = Ts; a.nsamples = nsamples; a.mode = mode; a.len_l = len_l; a.accumulate = accumulate;
-    return Ts <= hsplan::kAttnTile ? launch_blk256_bwd<1, 2>(a, s) : launch_blk256_bwd<2, 2>(a, s);
+    a.qkv = p.qkv; a.lse = p.lse; a.dx1b = p.dx1b; a.dx1 = p.dx1; a.x = p.x; a.gamma = w.n1w; a.wpT = w.pT; a.wqkvT = w.qkvT;
+    a.dqkv = p.dqkv; a.dx = p.dx; a.dgamma = p.dgamma; a.dbeta = p.dbeta; a.det_base = p.det.base; a.det_acc = p.det.acc;
+    a.Ts = p.Ts; a.nsamples = p.nsamples; a.mode = p.mode; a.len_l = p.len_l; a.accumulate = p.accumulate;
+    return p.Ts <= hsplan::kAttnTile ? launch_blk256_bwd<1, 2>(a, s) : launch_blk256_bwd<2, 2>(a, s);
 }
 
-int hs_attn_block256_fwd(const float* x, const float* n1w, const float* n1b, const hs_bf16* wqkv, const float* bqkv, const hs_bf16* wp,
-                         const float* pb, hs_bf16* u, hs_bf16* qkv, hs_bf16* o, float* lse, float* x1, const float* rowscale, int Ts,
-                         int nsamples, int mode, int len_l, hipStream_t s) {
-    if (nsamples <= 0) return HS_OK;
-    if (Ts < 1 || Ts > hsplan::kAttnMaxTs) return HS_EUNSUPPORTED;
-    if ((int64_t)nsamples * Ts * 3 * DW >= (1ll << 31)) return HS_EUNSUPPORTED;      // 32-bit element offsets inside the kernel
+int hs_attn_block256_fwd(const BlockW& w, const AttnBlockFwd& p, hipStream_t s) {
+    if (p.nsamples <= 0) return HS_OK;
+    if (p.Ts < 1 || p.Ts > hsplan::kAttnMaxTs) return HS_EUNSUPPORTED;
+    if ((int64_t)p.nsamples * p.Ts * 3 * DW >= (1ll << 31)) return HS_EUNSUPPORTED;      // 32-bit element offsets inside the kernel
     Blk256Args a;
-    a.x = x; a.n1w = n1w; a.n1b = n1b; a.wqkv = wqkv; a.bqkv = bqkv; a.wp = wp; a.pb = pb; a.u = u; a.qkv = qkv; a.o = o;
-    a.lse = lse; a.x1 = x1; a.rowscale = rowscale; a.Ts = Ts; a.nsamples = nsamples; a.mode = mode; a.len_l = len_l;
-    return Ts <= hsplan::kAttnTile ? launch_blk256<1, 2>(a, s) : launch_blk256<2, 2>(a, s);
+    a.x = p.x; a.n1w = w.n1w; a.n1b = w.n1b; a.wqkv = w.qkv; a.bqkv = w.bqkv; a.wp = w.p; a.pb = w.pb; a.u = p.u; a.qkv = p.qkv; a.o = p.o;
+    a.lse = p.lse; a.x1 = p.x1; a.rowscale = p.rowscale; a.Ts = p.Ts; a.nsamples = p.nsamples; a.mode = p.mode; a.len_l = p.len_l;
+    return p.Ts <= hsplan::kAttnTile ? launch_blk256<1, 2>(a, s) : launch_blk256<2, 2>(a, s);
 }
 
 HS_UNIT_VARIANT_BITS(attn_wide)

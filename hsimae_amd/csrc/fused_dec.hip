@@ -2029,8 +2029,7 @@ int launch_fwd(const DecFwdArgs& a, hipStream_t s) {
                                   hipFuncAttributeMaxDynamicSharedMemorySize, L::FWD_TOTAL);
         attr_set = true;
     }
-    static int wgs = 0;                       // workgroups: 2 per CU walking the samples
-    if (!wgs) wgs = 512;
+    constexpr int wgs = 512;                  // workgroups: 2 per CU walking the samples
     hipLaunchKernelGGL((dec_block_fwd_kernel<MT>), dim3(a.nsamples < wgs ? a.nsamples : wgs), dim3(256), L::FWD_TOTAL, s, a);
     return (int)hipGetLastError();
 }
@@ -2086,49 +2085,45 @@ int launch_bwd(const DecBwdMlpArgs& a, const DecBwdAttnArgs& b, hipStream_t s) {
 static_assert(hsplan::kDecD == D && hsplan::kDecHeads * HD == D && hsplan::kDecHeads * 64 == NT_ && hsplan::kDecHp == HPD &&
               hsplan::kDecMaxTs == 7 * 16, "plan.h dec_fusable must select exactly the shape these kernels are compiled for");
 
-int hs_dec_block_bwd(const float* x, const float* x1, const float* dy, float* dx1_tmp, float* dx, const hs_bf16* o,
-                     const float* lse, int nsamples, int Ts, const DecBlockPtrs& bp, const DecBlockGrads& g, hipStream_t s,
-                     float* slab) {
+// the kernel-argument subset of a block's parameters
+static DecW dec_w(const BlockW& b) {
     DecW w;
-    w.n1w = bp.n1w; w.n1b = bp.n1b; w.bqkv = bp.bqkv; w.pb = bp.pb; w.n2w = bp.n2w; w.n2b = bp.n2b;
-    w.w1b = bp.w1b; w.w3b = bp.w3b; w.w2b = bp.w2b;
-    w.qkv = bp.qkv; w.p = bp.p; w.w1 = bp.w1; w.w3 = bp.w3; w.w2 = bp.w2; w.h = bp.h;
+    w.n1w = b.n1w; w.n1b = b.n1b; w.bqkv = b.bqkv; w.pb = b.pb; w.n2w = b.n2w; w.n2b = b.n2b;
+    w.w1b = b.w1b; w.w3b = b.w3b; w.w2b = b.w2b;
+    w.qkv = b.qkv; w.p = b.p; w.w1 = b.w1; w.w3 = b.w3; w.w2 = b.w2; w.h = b.h;
+    return w;
+}
+
+int hs_dec_block_bwd(const BlockW& bp, const DecBlockGrads& g, const DecBlockBwd& p, hipStream_t s) {
     DecBwdMlpArgs a;
-    a.x1 = x1; a.dy = dy; a.dx1 = dx1_tmp; a.nsamples = nsamples; a.Ts = Ts; a.w = w; a.w2T = bp.w2T; a.w13T = bp.w13T;
+    a.x1 = p.x1; a.dy = p.dy; a.dx1 = p.dx1_tmp; a.nsamples = p.nsamples; a.Ts = p.Ts; a.w = dec_w(bp); a.w2T = bp.w2T; a.w13T = bp.w13T;
     a.w1f = bp.w1f; a.w3f = bp.w3f;
     a.g_n2w = g.n2w; a.g_n2b = g.n2b; a.g_w1w = g.w1w; a.g_w1b = g.w1b; a.g_w3w = g.w3w; a.g_w3b = g.w3b;
-    a.g_w2w = g.w2w; a.g_w2b = g.w2b; a.det = g.det; a.slab = slab;
+    a.g_w2w = g.w2w; a.g_w2b = g.w2b; a.det = g.det; a.slab = p.slab;
     DecBwdAttnArgs b;
-    b.x = x; b.dx1 = dx1_tmp; b.dx = dx; b.o = o; b.lse_g = lse; b.nsamples = nsamples; b.Ts = Ts; b.w = w; b.qkvT = bp.qkvT; b.pT = bp.pT;
-    b.qf = bp.qf; b.kf = bp.kf; b.vf = bp.vf; b.pf = bp.pf;
+    b.x = p.x; b.dx1 = p.dx1_tmp; b.dx = p.dx; b.o = p.o; b.lse_g = p.lse; b.nsamples = p.nsamples; b.Ts = p.Ts; b.w = a.w;
+    b.qkvT = bp.qkvT; b.pT = bp.pT; b.qf = bp.qf; b.kf = bp.kf; b.vf = bp.vf; b.pf = bp.pf;
     b.g_n1w = g.n1w; b.g_n1b = g.n1b; b.g_qw = g.qw; b.g_qb = g.qb; b.g_kw = g.kw; b.g_kb = g.kb; b.g_vw = g.vw;
-    b.g_vb = g.vb; b.g_pw = g.pw; b.g_pb = g.pb; b.det = g.det; b.slab = slab;
-    const int mt = (Ts + 15) / 16;
+    b.g_vb = g.vb; b.g_pw = g.pw; b.g_pb = g.pb; b.det = g.det; b.slab = p.slab;
+    const int mt = (p.Ts + 15) / 16;
     if (mt <= 4) return launch_bwd<4>(a, b, s);
     if (mt <= 7) return launch_bwd<7>(a, b, s);
     return HS_EUNSUPPORTED;
 }
 
 // attention half of the block only (x1 = x + proj(attention(LN1 x)); O and logsumexp kept for the backward)
-int hs_dec_attn_fwd(const float* x, float* x1, hs_bf16* o, float* lse, int nsamples, int Ts, const DecBlockPtrs& bp, hipStream_t s) {
+int hs_dec_attn_fwd(const float* x, float* x1, hs_bf16* o, float* lse, int nsamples, int Ts, const BlockW& bp, hipStream_t s) {
     DecAttnFwdArgs a;
-    a.x = x; a.x1 = x1; a.o = o; a.lse = lse; a.nsamples = nsamples; a.Ts = Ts;
-    a.w.n1w = bp.n1w; a.w.n1b = bp.n1b; a.w.bqkv = bp.bqkv; a.w.pb = bp.pb; a.w.n2w = bp.n2w; a.w.n2b = bp.n2b;
-    a.w.w1b = bp.w1b; a.w.w3b = bp.w3b; a.w.w2b = bp.w2b;
-    a.w.qkv = bp.qkv; a.w.p = bp.p; a.w.w1 = bp.w1; a.w.w3 = bp.w3; a.w.w2 = bp.w2; a.w.h = bp.h;
+    a.x = x; a.x1 = x1; a.o = o; a.lse = lse; a.nsamples = nsamples; a.Ts = Ts; a.w = dec_w(bp);
     const int mt = (Ts + 15) / 16;
     if (mt <= 4) return launch_attn_fwd<4>(a, s);
     if (mt <= 7) return launch_attn_fwd<7>(a, s);
     return HS_EUNSUPPORTED;
 }
 
-int hs_dec_block_fwd(const float* x, float* x1, float* x2, hs_bf16* o, float* lse, int nsamples, int Ts,
-                     const DecBlockPtrs& bp, hipStream_t s) {
+int hs_dec_block_fwd(const float* x, float* x1, float* x2, hs_bf16* o, float* lse, int nsamples, int Ts, const BlockW& bp, hipStream_t s) {
     DecFwdArgs a;
-    a.x = x; a.x1 = x1; a.x2 = x2; a.o = o; a.lse = lse; a.nsamples = nsamples; a.Ts = Ts;
-    a.w.n1w = bp.n1w; a.w.n1b = bp.n1b; a.w.bqkv = bp.bqkv; a.w.pb = bp.pb; a.w.n2w = bp.n2w; a.w.n2b = bp.n2b;
-    a.w.w1b = bp.w1b; a.w.w3b = bp.w3b; a.w.w2b = bp.w2b;
-    a.w.qkv = bp.qkv; a.w.p = bp.p; a.w.w1 = bp.w1; a.w.w3 = bp.w3; a.w.w2 = bp.w2; a.w.h = bp.h;
+    a.x = x; a.x1 = x1; a.x2 = x2; a.o = o; a.lse = lse; a.nsamples = nsamples; a.Ts = Ts; a.w = dec_w(bp);
     const int mt = (Ts + 15) / 16;
     if (mt <= 4) return launch_fwd<4>(a, s);
     if (mt <= 7) return launch_fwd<7>(a, s);

@@ -802,7 +802,7 @@ __global__ __launch_bounds__(NTH, (MG<D, HPE>::WPC)) void enc_mlp_bwd_kernel(Enc
 // the kernels are templates on <D, HP>: Base (128, 344 -> 352), Large (256, 684 -> 704) and the decoder width (64, 172 -> 192)
 // are instantiated by launch_fwd / launch_bwd below; every launch goes through set_attrs<D, HP>
 
-static EncMlpW mkw(const EncMlpPtrs& b) {
+static EncMlpW mkw(const BlockW& b) {
     EncMlpW w;
     w.n2w = b.n2w; w.n2b = b.n2b; w.w1b = b.w1b; w.w3b = b.w3b; w.w2b = b.w2b;
     w.w1 = b.w1; w.w3 = b.w3; w.w2 = b.w2; w.w2T = b.w2T; w.w13T = b.w13T; w.h = b.h;
@@ -824,8 +824,7 @@ template <int D, int HP>
 static int fwd_grid(int M) {
     const int panels = (M + MG<D, HP>::R - 1) / MG<D, HP>::R;
     if (!MG<D, HP>::PERSIST) return panels;
-    static int slots = 0;                     // resident workgroups: WPCF per CU
-    if (!slots) slots = 256 * MG<D, HP>::WPCF;
+    constexpr int slots = 256 * MG<D, HP>::WPCF;      // resident workgroups: WPCF per CU
     return panels < slots ? panels : slots;
 }
 
@@ -845,7 +844,7 @@ static int launch_fwd(const EncMlpFwdArgs& a, int M, int d, hipStream_t s) {
     return (int)hipGetLastError();
 }
 
-int hs_enc_mlp_fwd(const float* x1, const float* res2, float* x2, int M, int d, const EncMlpPtrs& b, hipStream_t s,
+int hs_enc_mlp_fwd(const float* x1, const float* res2, float* x2, int M, int d, const BlockW& b, hipStream_t s,
                    const float* rowscale) {
     if (M <= 0) return HS_OK;
     EncMlpFwdArgs a;
@@ -873,20 +872,12 @@ static int launch_bwd(const EncMlpBwdArgs& a, int M, int d, hipStream_t s) {
     return (int)hipGetLastError();
 }
 
-static EncMlpBwdArgs mk_bwd(const float* x1, const float* dy, float* dx1, hs_bf16* u2, hs_bf16* dh13, hs_bf16* g, hs_bf16* dyb,
-                            hs_bf16* dx1b, int M, const EncMlpPtrs& b, float* g_n2w, float* g_n2b, const float* rs_mlp,
-                            const float* rs_attn, HsDet det, int plane_rows) {
-    EncMlpBwdArgs a; a.x1 = x1; a.dy = dy; a.dx1 = dx1; a.u2 = u2; a.dh13 = dh13; a.g = g; a.M = M; a.w = mkw(b);
-    a.g_n2w = g_n2w; a.g_n2b = g_n2b; a.dyb = dyb; a.dx1b = dx1b; a.rs_mlp = rs_mlp; a.rs_attn = rs_attn; a.det = det;
-    a.plane_rows = plane_rows;
-    return a;
-}
-
-int hs_enc_mlp_bwd(const float* x1, const float* dy, float* dx1, hs_bf16* u2, hs_bf16* dh13, hs_bf16* g, hs_bf16* dyb,
-                   hs_bf16* dx1b, int M, int d, const EncMlpPtrs& b, float* g_n2w, float* g_n2b, hipStream_t s,
-                   const float* rs_mlp, const float* rs_attn, HsDet det, int plane_rows) {
-    if (M <= 0) return HS_OK;
-    return launch_bwd(mk_bwd(x1, dy, dx1, u2, dh13, g, dyb, dx1b, M, b, g_n2w, g_n2b, rs_mlp, rs_attn, det, plane_rows), M, d, s);
+int hs_enc_mlp_bwd(const BlockW& b, const EncMlpBwd& p, hipStream_t s) {
+    if (p.M <= 0) return HS_OK;
+    EncMlpBwdArgs a; a.x1 = p.x1; a.dy = p.dy; a.dx1 = p.dx1; a.u2 = p.u2; a.dh13 = p.dh13; a.g = p.g; a.M = p.M; a.w = mkw(b);
+    a.g_n2w = p.g_n2w; a.g_n2b = p.g_n2b; a.dyb = p.dyb; a.dx1b = p.dx1b; a.rs_mlp = p.rs_mlp; a.rs_attn = p.rs_attn; a.det = p.det;
+    a.plane_rows = p.plane_rows;
+    return launch_bwd(a, p.M, p.d, s);
 }
 
 HS_UNIT_VARIANT_BITS(fused_enc)

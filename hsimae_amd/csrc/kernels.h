@@ -58,55 +58,60 @@ int hs_rows_pad_bf16(const float* src, hs_bf16* dst, int64_t rows, int cols, int
 int hs_det_convert(const int64_t* acc, float* g, int64_t n, hipStream_t s);
 int hs_add2(const float* a, const float* b, float* out, int64_t n, hipStream_t s);
 
-// ------------------------------------------------------------------ fused_dec.hip (decoder Block, one workgroup per sample)
-struct DecBlockPtrs {
+// ------------------------------------------------------------------ one transformer Block's parameters
+// What every block launcher below takes: api.hip fills one per block of a pass (resolve()) and one from each weights struct of
+// the C ABI.  A member its source does not have stays NULL; each unit copies the subset its kernels read (DecW, EncMlpW, Blk*Args).
+struct BlockW {
     const float *n1w, *n1b, *bqkv, *pb, *n2w, *n2b, *w1b, *w3b, *w2b;
     const bf16_t *qkv, *p, *w1, *w3, *w2, *qkvT, *pT, *w13T, *w2T;
-    const float *qf, *kf, *vf, *pf, *w1f, *w3f;    // fp32 row-major weights [out][in] (the backward stages them in LDS as bf16)
-    int h;
+    const float *qf, *kf, *vf, *pf, *w1f, *w3f;    // fp32 row-major weights [out][in] (the fused decoder backward stages them in LDS as bf16)
+    int h;                                         // hidden width of the MLP
 };
-struct DecBlockGrads {
-    float *n1w, *n1b, *qw, *qb, *kw, *kb, *vw, *vb, *pw, *pb, *n2w, *n2b, *w1w, *w1b, *w2w, *w2b, *w3w, *w3b;
+
+// ------------------------------------------------------------------ fused_dec.hip (decoder Block, one workgroup per sample)
+// The 18 gradient pointers are the C ABI's struct itself (hsimae_dec_block_bwd's caller hands one over as it is): a member added to
+// hsimae_dec_block_grads reaches hs_dec_block_bwd, which must then commit it (the assert below stops the build until someone looks).
+struct DecBlockGrads : hsimae_dec_block_grads {
     HsDet det;                    // deterministic commits (common.h); {nullptr, nullptr} = fp32 atomics
 };
-int hs_dec_block_fwd(const float* x, float* x1, float* x2, hs_bf16* o, float* lse, int nsamples, int Ts,
-                     const DecBlockPtrs& bp, hipStream_t s);
-int hs_dec_attn_fwd(const float* x, float* x1, hs_bf16* o, float* lse, int nsamples, int Ts, const DecBlockPtrs& bp, hipStream_t s);
+static_assert(sizeof(hsimae_dec_block_grads) == 18 * sizeof(float*), "hsimae_dec_block_grads changed: fused_dec.hip commits exactly 18 gradients");
+int hs_dec_block_fwd(const float* x, float* x1, float* x2, hs_bf16* o, float* lse, int nsamples, int Ts, const BlockW& w, hipStream_t s);
+int hs_dec_attn_fwd(const float* x, float* x1, hs_bf16* o, float* lse, int nsamples, int Ts, const BlockW& w, hipStream_t s);
 // slab: NULL = the block's gradients are committed with float atomics; else >= kDecSlabFloats floats of scratch
 // (plan.h slab_bytes(); C ABI: hsimae_dec_block_slab_floats()): per-workgroup partials, summed into the gradients by one
 // reduce launch per block.  256 workgroups x (104 in-register dW values x 512 threads + 2112 bias / LayerNorm sums).
 constexpr long long kDecSlabFloats = HSIMAE_DEC_BLOCK_SLAB_FLOATS;
-int hs_dec_block_bwd(const float* x, const float* x1, const float* dy, float* dx1_tmp, float* dx, const hs_bf16* o,
-                     const float* lse, int nsamples, int Ts, const DecBlockPtrs& bp, const DecBlockGrads& g, hipStream_t s,
-                     float* slab = nullptr);
-
-// ------------------------------------------------------------------ fused_enc.hip (MLP half of an encoder Block, D = 128)
-struct EncMlpPtrs {
-    const float *n2w, *n2b, *w1b, *w3b, *w2b;
-    const bf16_t *w1, *w3, *w2, *w2T, *w13T;
-    int h;
+struct DecBlockBwd {
+    const float *x, *x1, *dy; float *dx1_tmp, *dx; const hs_bf16* o; const float* lse;
+    int nsamples, Ts; float* slab = nullptr;
 };
-int hs_attn_block_bwd(const hs_bf16* qkv, const hs_bf16* u, const hs_bf16* wqkv, const float* bqkv, const hs_bf16* o, const float* lse,
-                      const hs_bf16* dx1b, const float* dx1, const float* x, const float* gamma, const hs_bf16* wpT, const hs_bf16* wqkvT,
-                      hs_bf16* dqkv, float* dx, float* dgamma, float* dbeta, const float* det_base, long long* det_acc, int Ts,
-                      int nsamples, int mode, int len_l, int accumulate, hipStream_t s);
-int hs_attn_block_fwd(const float* x, const float* n1w, const float* n1b, const hs_bf16* wqkv, const float* bqkv, const hs_bf16* wp,
-                      const float* pb, hs_bf16* u, hs_bf16* qkv, hs_bf16* o, float* lse, float* x1, const float* rowscale, int Ts,
-                      int nsamples, int mode, int len_l, hipStream_t s);
-// the same half at D = 256 (16 heads of 16, <= 32 tokens): attn_wide.hip
-int hs_attn_block256_fwd(const float* x, const float* n1w, const float* n1b, const hs_bf16* wqkv, const float* bqkv, const hs_bf16* wp,
-                         const float* pb, hs_bf16* u, hs_bf16* qkv, hs_bf16* o, float* lse, float* x1, const float* rowscale, int Ts,
-                         int nsamples, int mode, int len_l, hipStream_t s);
-// ... and its backward (dO + attention backward + du + LayerNorm-1 backward, round 5)
-int hs_attn_block256_bwd(const hs_bf16* qkv, const float* lse, const hs_bf16* dx1b, const float* dx1, const float* x, const float* gamma,
-                         const hs_bf16* wpT, const hs_bf16* wqkvT, hs_bf16* dqkv, float* dx, float* dgamma, float* dbeta,
-                         const float* det_base, long long* det_acc, int Ts, int nsamples, int mode, int len_l, int accumulate,
-                         hipStream_t s);
-int hs_enc_mlp_fwd(const float* x1, const float* res2, float* x2, int M, int d, const EncMlpPtrs& b, hipStream_t s,
+int hs_dec_block_bwd(const BlockW& w, const DecBlockGrads& g, const DecBlockBwd& p, hipStream_t s);
+
+// ------------------------------------------------------------------ attn.hip / attn_wide.hip (attention half of an encoder Block)
+// blk128_* at D = 128 (8 heads of 16), blk256_* at D = 256 (16 heads of 16), <= 32 tokens: LN1 + q|k|v + attention + projection +
+// residual forward; dO + attention backward + du + LayerNorm-1 backward.  Members as in hsimae_attn_block_fwd / _bwd.
+struct AttnBlockFwd {
+    const float* x; hs_bf16 *u, *qkv, *o; float *lse, *x1; const float* rowscale = nullptr;      // qkv NULL (D = 128): not saved; rowscale NULL: 1
+    int Ts, nsamples, mode, len_l;
+};
+struct AttnBlockBwd {
+    const hs_bf16 *qkv, *u, *o; const float* lse; const hs_bf16* dx1b; const float *dx1, *x;      // qkv NULL (D = 128): recomputed from u
+    hs_bf16* dqkv; float *dx, *dgamma, *dbeta; HsDet det{nullptr, nullptr};
+    int Ts, nsamples, mode, len_l, accumulate;
+};
+int hs_attn_block_fwd(const BlockW& w, const AttnBlockFwd& p, hipStream_t s);
+int hs_attn_block_bwd(const BlockW& w, const AttnBlockBwd& p, hipStream_t s);
+int hs_attn_block256_fwd(const BlockW& w, const AttnBlockFwd& p, hipStream_t s);
+int hs_attn_block256_bwd(const BlockW& w, const AttnBlockBwd& p, hipStream_t s);      // (reads neither u nor o)
+
+// ------------------------------------------------------------------ fused_enc.hip (MLP half of a Block, D = 128 / 256 / 64)
+int hs_enc_mlp_fwd(const float* x1, const float* res2, float* x2, int M, int d, const BlockW& w, hipStream_t s,
                    const float* rowscale = nullptr);
-int hs_enc_mlp_bwd(const float* x1, const float* dy, float* dx1, hs_bf16* u2, hs_bf16* dh13, hs_bf16* g, hs_bf16* dyb,
-                   hs_bf16* dx1b, int M, int d, const EncMlpPtrs& b, float* g_n2w, float* g_n2b, hipStream_t s,
-                   const float* rs_mlp = nullptr, const float* rs_attn = nullptr, HsDet det = HsDet{nullptr, nullptr}, int plane_rows = 0);
+struct EncMlpBwd {
+    const float *x1, *dy; float* dx1; hs_bf16 *u2, *dh13, *g, *dyb, *dx1b; float *g_n2w, *g_n2b;
+    const float *rs_mlp = nullptr, *rs_attn = nullptr; HsDet det{nullptr, nullptr}; int M, d, plane_rows = 0;      // the optional ones: NULL / 0 = none
+};
+int hs_enc_mlp_bwd(const BlockW& w, const EncMlpBwd& p, hipStream_t s);
 
 int hs_adamw(float* p, const float* g, float* m, float* v, const unsigned char* group, int64_t n, float lr, float b1, float b2,
              float eps, float wd, int step, hipStream_t s);

@@ -509,8 +509,7 @@ int hs_wgrad(const WgradParams& p, hipStream_t s) {
         // 256 x 256 tiles, one workgroup per CU: the row split that fills the chip once (p.msplit is sized for 128-tiles)
         WgradParams q = p;
         const int t256 = wg_tiles(p, 256), nchunks = (p.M + DC - 1) / DC;
-        static int wgs = 0;
-        if (!wgs) wgs = 256;
+        constexpr int wgs = 256;
         q.msplit = std::max(1, std::min(wgs / std::max(1, t256), nchunks));
         const int total = t256 * q.msplit;
         const dim3 grid(8 * ((total + 7) / 8));
