@@ -23,5 +23,6 @@ from .finetune_train import dual_branch_finetuning, dual_branch_finetuning_scene
 from .scene_data import SceneCubes, get_scene_set_dual, split_labeled, tile_origins, unlabeled_pixels  # noqa: F401
 from .gwpca import GWPCA, apply_gwpca  # noqa: F401
 from .classify import ClassLoss, ScoreMeter  # noqa: F401
+from .colormap import label_to_colormap, save_label_png  # noqa: F401
 
 __version__ = "0.1.0"

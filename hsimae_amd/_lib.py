@@ -139,6 +139,12 @@ class ClsParams(C.Structure):
                 ("loss", vp), ("n_valid", vp), ("dlogits", vp), ("ldd", i32), ("pred", vp), ("bad", vp), ("workspace", vp)]
 
 
+class ClassProbParams(C.Structure):
+    _fields_ = [("logits", vp), ("ld", i32), ("N", i32), ("C", i32), ("first", i32), ("view", i32), ("n_views", i32),
+                ("acc", vp), ("lda", i32), ("H", i32), ("W", i32), ("p0", i64), ("pixels", vp),
+                ("label_map", vp), ("conf_map", vp), ("margin_map", vp), ("probs", vp), ("ldp", i32)]
+
+
 class GradSeg(C.Structure):
     _fields_ = [("g", vp), ("group", vp), ("n", i64)]
 
@@ -234,6 +240,7 @@ SYMBOLS = {
     "hsimae_confusion": (C.c_int, [vp, vp, i64, i32, vp, vp, vp]),
     "hsimae_confusion_map": (C.c_int, [vp, vp, vp, vp, i64, i32, vp, vp, vp]),
     "hsimae_scores": (C.c_int, [vp, i32, vp, vp]),
+    "hsimae_class_prob": (C.c_int, [C.POINTER(ClassProbParams), vp]),
     "hsimae_encode": (C.c_int, [C.POINTER(Config), C.POINTER(IO), vp]),
     "hsimae_encode_backward": (C.c_int, [C.POINTER(Config), C.POINTER(IO), vp, vp, BUCKET_CB, vp, vp]),
     "hsimae_agg_pool": (C.c_int, [vp, vp, i32, i32, i32, i32, vp]),

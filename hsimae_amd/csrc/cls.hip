@@ -28,14 +28,7 @@ __host__ __device__ inline ClsPartials cls_carve(void* ws) {
     return ClsPartials{static_cast<double*>(ws), reinterpret_cast<long long*>(static_cast<double*>(ws) + CLS_MAXNB)};
 }
 
-// (value, index) of the better of two argmax candidates: a NaN beats every number, a larger value a smaller one, and of two
-// equals (or two NaNs) the lower index wins -- torch.argmax, and hsimae_class_argmax's serial scan
-__device__ __forceinline__ void arg_better(float& v, int& i, float v2, int i2) {
-    const bool n1 = __builtin_isnan(v), n2 = __builtin_isnan(v2);
-    const bool take = n2 ? (!n1 || i2 < i) : (!n1 && (v2 > v || (v2 == v && i2 < i)));
-    if (take) { v = v2; i = i2; }
-}
-
+// (arg_better, the argmax rule of the predictions: common.h)
 __global__ __launch_bounds__(256) void cls_rows_kernel(hsimae_cls_params p, ClsPartials part) {
     __shared__ double wsum[4];
     __shared__ long long wcnt[4];

@@ -58,6 +58,14 @@ static inline unsigned hs_variant_bits() {
 #define HS_EALIGN (-3)
 #define HS_ENULL (-4)
 
+// (value, index) of the better of two argmax candidates: a NaN beats every number, a larger value a smaller one, and of two
+// equals (or two NaNs) the lower index wins -- torch.argmax, and hsimae_class_argmax's serial scan (cls.hip, prob.hip)
+__device__ __forceinline__ void arg_better(float& v, int& i, float v2, int i2) {
+    const bool n1 = __builtin_isnan(v), n2 = __builtin_isnan(v2);
+    const bool take = n2 ? (!n1 || i2 < i) : (!n1 && (v2 > v || (v2 == v && i2 < i)));
+    if (take) { v = v2; i = i2; }
+}
+
 __device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
     // D[16x16] += A[16x32] * B[32x16].  lane l: A[row l&15][k 8(l>>4)+j], B[k 8(l>>4)+j][col l&15];
     // D: col = l&15, row = 4*(l>>4)+r.

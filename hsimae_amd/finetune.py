@@ -17,6 +17,7 @@ pass, then grid / masking noise, then reconstruction pass); `drop_factors=` repl
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 
 import numpy as np
@@ -25,6 +26,26 @@ import torch.nn as nn
 
 from . import _lib
 from .model import HSIMAE
+
+# what DualViT.classify_scene returns
+SceneClassification = collections.namedtuple("SceneClassification", ["labels", "confidence", "margin", "probs"])
+
+
+def scene_views(views):
+    """classify_scene's `views` as a tuple of distinct flip codes in 0 .. 3 (bit 0: along w, bit 1: along h); "flips" is all four."""
+    if isinstance(views, str):
+        if views != "flips":
+            raise ValueError(f'views must be "flips" or a tuple of flip codes 0 .. 3, got {views!r}')
+        return (0, 1, 2, 3)
+    try:
+        out = tuple(views)
+    except TypeError:
+        raise ValueError(f'views must be "flips" or a tuple of flip codes 0 .. 3, got {views!r}') from None
+    if not out or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= 3 for v in out):
+        raise ValueError(f"views must be a non-empty tuple of flip codes 0 .. 3, got {views!r}")
+    if len(set(out)) != len(out):
+        raise ValueError(f"views repeats a flip code: {views!r}")
+    return tuple(int(v) for v in out)
 
 
 class _FineTuneStep(torch.autograd.Function):
@@ -147,6 +168,38 @@ class DualViT(HSIMAE):
         for the encoder's workspace to fit SCENE_WORKSPACE_BUDGET bytes.
         -> int64 [H, W] map (CPU), and with return_logits=True also fp32 [n, num_class] logits (CPU) in pixel order.
         on_device=True: both stay on the model's device and nothing waits for the host."""
+        s, H, W, Cb, pix, dev, n_total, chunk = self._scene_args(scene, pixels, batch_size)
+        lib = _lib.load()
+        T, L = self.input_size[0], self.input_size[1] ** 2
+        with torch.no_grad(), torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            s = s.to(dev).contiguous()
+            pix_d = None if pix is None else pix.to(dev)
+            labels = torch.zeros(H * W, dtype=torch.int64, device=dev)
+            logits_all = torch.empty(n_total, self.num_class, dtype=torch.float32, device=dev) if return_logits else None
+            win, n1, n2 = self._scene_buffers(chunk, Cb, dev)
+            for k0 in range(0, n_total, chunk):
+                n = min(chunk, n_total - k0)
+                sp = _lib.SceneParams(scene=s.data_ptr(), scene_f64=int(s.dtype == torch.float64), H=H, W=W, C=Cb,
+                                      p0=k0 if pix_d is None else 0, pixels=None if pix_d is None else pix_d.data_ptr() + 8 * k0,
+                                      N=n, out=win.data_ptr(), sn=win.stride(0), sb=win.stride(2), sh=win.stride(3),
+                                      sw=win.stride(4))
+                _lib.check(lib.hsimae_scene_windows(C.byref(sp), stream), "hsimae_scene_windows")
+                _, _, _, st = self._run_forward(win[:n], 0.0, (n1[:n], n2[:n]), (T, L), want_latent=True, encoder_only=True)
+                logits, _ = self.head(st["latent"])
+                st.release()
+                _lib.check(lib.hsimae_class_argmax(C.byref(sp), logits.data_ptr(), logits.stride(0), self.num_class, 1,
+                                                   labels.data_ptr(), stream), "hsimae_class_argmax")
+                if logits_all is not None:
+                    logits_all[k0:k0 + n].copy_(logits)
+            out = labels.view(H, W) if on_device else labels.view(H, W).cpu()
+        if return_logits:
+            return out, (logits_all if on_device else logits_all.cpu())
+        return out
+
+    def _scene_args(self, scene, pixels, batch_size):
+        """The argument checks and the chunk size predict_scene and classify_scene share
+        -> (scene tensor, H, W, bands, pixel indices (CPU int64) or None, the model's device, pixel count, pixels per chunk)."""
         if isinstance(scene, torch.Tensor):
             s = scene
         else:
@@ -176,37 +229,71 @@ class DualViT(HSIMAE):
         if dev.type != "cuda":
             raise RuntimeError("hsimae_amd runs on MI355X only (no CPU fallback): move the model to a GPU")
         n_total = H * W if pix is None else pix.numel()
-        lib = _lib.load()
-        T, L = self.input_size[0], self.input_size[1] ** 2
         chunk = max(1, min(self._scene_chunk(batch_size), n_total))
+        return s, H, W, Cb, pix, dev, n_total, chunk
+
+    def _scene_buffers(self, chunk, Cb, dev):
+        """The encoder's input of one chunk, band-fastest as the reference's HSIdataset yields it ([chunk, 9, 9, C] viewed
+        [chunk, 1, C, 9, 9]), and the increasing noise that keeps every token in its place."""
+        T, L = self.input_size[0], self.input_size[1] ** 2
+        win = torch.empty(chunk, 9, 9, Cb, dtype=torch.float32, device=dev).permute(0, 3, 1, 2).unsqueeze(1)
+        n1 = torch.arange(T, dtype=torch.float32, device=dev).expand(chunk, T).contiguous()
+        n2 = torch.arange(L, dtype=torch.float32, device=dev).expand(chunk, L).contiguous()
+        return win, n1, n2
+
+    def classify_scene(self, scene, pixels=None, batch_size=8192, views=(0,), return_probs=False, on_device=False):
+        """predict_scene with what a classifier's user asks for next: the class probabilities behind every label, averaged over
+        `views` of the pixel's window, and per pixel the winning probability and its margin over the runner-up.
+        `views`: distinct flip codes 0 .. 3 (bit 0 flips the window along w, bit 1 along h: hsimae_scene_batch's, the flips
+        fine-tuning draws); "flips" = (0, 1, 2, 3).  Per chunk and view, on the current stream: the flipped windows
+        (hsimae_scene_batch), the unmasked encoder, the AGG head, and hsimae_class_prob: softmax over the real classes 1 ..
+        num_class - 1 (class 0 is "unlabelled": probability 0), summed over the views in a chunk-local buffer; the last view
+        writes mean, label = argmax of the mean (of the logits with one view: predict_scene's label bit for bit), confidence =
+        mean[label] and margin = mean[label] - the largest other mean into device-resident maps.
+        `scene`, `pixels`, `batch_size`, eval / no-grad behaviour: as predict_scene.  Pixels not asked for get label 0,
+        confidence 0 and margin 0.
+        -> SceneClassification(labels int64 [H, W], confidence fp32 [H, W], margin fp32 [H, W], probs fp32 [n, num_class] in pixel
+        order with return_probs=True, else None), on the CPU after one wait for the copies; on_device=True: all stay on the
+        model's device and nothing waits for the host."""
+        views = scene_views(views)
+        s, H, W, Cb, pix, dev, n_total, chunk = self._scene_args(scene, pixels, batch_size)
+        lib = _lib.load()
+        T, L, nc = self.input_size[0], self.input_size[1] ** 2, self.num_class
         with torch.no_grad(), torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
             s = s.to(dev).contiguous()
-            pix_d = None if pix is None else pix.to(dev)
+            items = torch.arange(H * W, dtype=torch.int64, device=dev) if pix is None else pix.to(dev)
             labels = torch.zeros(H * W, dtype=torch.int64, device=dev)
-            logits_all = torch.empty(n_total, self.num_class, dtype=torch.float32, device=dev) if return_logits else None
-            # the encoder's input, band-fastest as the reference's HSIdataset yields it: [chunk, 9, 9, C] viewed [chunk, 1, C, 9, 9]
-            win = torch.empty(chunk, 9, 9, Cb, dtype=torch.float32, device=dev).permute(0, 3, 1, 2).unsqueeze(1)
-            n1 = torch.arange(T, dtype=torch.float32, device=dev).expand(chunk, T).contiguous()   # increasing noise: identity order
-            n2 = torch.arange(L, dtype=torch.float32, device=dev).expand(chunk, L).contiguous()
+            conf = torch.zeros(H * W, dtype=torch.float32, device=dev)
+            margin = torch.zeros(H * W, dtype=torch.float32, device=dev)
+            probs = torch.empty(n_total, nc, dtype=torch.float32, device=dev) if return_probs else None
+            acc = torch.empty(chunk, nc, dtype=torch.float32, device=dev)      # the views' sum of one chunk (view 0 overwrites it)
+            flips = [torch.full((chunk,), v, dtype=torch.uint8, device=dev) for v in views]
+            bad = torch.zeros(1, dtype=torch.int32, device=dev)
+            win, n1, n2 = self._scene_buffers(chunk, Cb, dev)
             for k0 in range(0, n_total, chunk):
                 n = min(chunk, n_total - k0)
-                sp = _lib.SceneParams(scene=s.data_ptr(), scene_f64=int(s.dtype == torch.float64), H=H, W=W, C=Cb,
-                                      p0=k0 if pix_d is None else 0, pixels=None if pix_d is None else pix_d.data_ptr() + 8 * k0,
-                                      N=n, out=win.data_ptr(), sn=win.stride(0), sb=win.stride(2), sh=win.stride(3),
-                                      sw=win.stride(4))
-                _lib.check(lib.hsimae_scene_windows(C.byref(sp), stream), "hsimae_scene_windows")
-                _, _, _, st = self._run_forward(win[:n], 0.0, (n1[:n], n2[:n]), (T, L), want_latent=True, encoder_only=True)
-                logits, _ = self.head(st["latent"])
-                st.release()
-                _lib.check(lib.hsimae_class_argmax(C.byref(sp), logits.data_ptr(), logits.stride(0), self.num_class, 1,
-                                                   labels.data_ptr(), stream), "hsimae_class_argmax")
-                if logits_all is not None:
-                    logits_all[k0:k0 + n].copy_(logits)
-            out = labels.view(H, W) if on_device else labels.view(H, W).cpu()
-        if return_logits:
-            return out, (logits_all if on_device else logits_all.cpu())
-        return out
+                for vi, fl in enumerate(flips):
+                    bp = _lib.SceneBatchParams(scene=s.data_ptr(), scene_f64=int(s.dtype == torch.float64), H=H, W=W, C=Cb,
+                                               items=items.data_ptr() + 8 * k0, N=n, n_items=H * W, flips=fl.data_ptr(),
+                                               out=win.data_ptr(), sn=win.stride(0), sb=win.stride(2), sh=win.stride(3),
+                                               sw=win.stride(4), bad=bad.data_ptr())
+                    _lib.check(lib.hsimae_scene_batch(C.byref(bp), stream), "hsimae_scene_batch")
+                    _, _, _, st = self._run_forward(win[:n], 0.0, (n1[:n], n2[:n]), (T, L), want_latent=True, encoder_only=True)
+                    logits, _ = self.head(st["latent"])
+                    st.release()
+                    cp = _lib.ClassProbParams(logits=logits.data_ptr(), ld=logits.stride(0), N=n, C=nc, first=1, view=vi,
+                                              n_views=len(views), acc=acc.data_ptr(), lda=nc, H=H, W=W,
+                                              pixels=items.data_ptr() + 8 * k0, label_map=labels.data_ptr(),
+                                              conf_map=conf.data_ptr(), margin_map=margin.data_ptr(),
+                                              probs=None if probs is None else probs.data_ptr() + 4 * nc * k0, ldp=nc)
+                    _lib.check(lib.hsimae_class_prob(C.byref(cp), stream), "hsimae_class_prob")
+            out = [labels.view(H, W), conf.view(H, W), margin.view(H, W), probs]
+            if not on_device:
+                out = [None if t is None else t.cpu() for t in out]
+                if int(bad.item()):                       # (the indices were checked on the host: this cannot happen)
+                    raise RuntimeError("classify_scene: a pixel index was outside the scene")
+        return SceneClassification(*out)
 
     # ------------------------------------------------------------------ stochastic depth (Models.py:235-263, 687-731)
     def drop_rates(self):

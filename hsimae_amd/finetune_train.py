@@ -26,8 +26,9 @@ import torch
 
 from . import _lib
 from .classify import ClassLoss, ScoreMeter
+from .colormap import save_label_png
 from .data import DeviceLoader
-from .finetune import DualViT, HSIViT
+from .finetune import DualViT, HSIViT, scene_views
 from .optim import FusedAdamW, FusedLAMB, weights_state_dict
 from .pretrain import seed_everything
 from .scene_data import SceneCubes, device_scene, unlabeled_pixels
@@ -296,10 +297,11 @@ def _finetune(datasets, h, c, gt, save_dir, model_name, pretrained, lr, wd, dept
     return val_value, epoch_loss_list, val_loss_list
 
 
-def test_model(data_cubes, test_gt, gt, save_dir, model_name, depth=12, dim=96, s_depth=6, device="cuda:0"):
+def test_model(data_cubes, test_gt, gt, save_dir, model_name, depth=12, dim=96, s_depth=6, device="cuda:0", save_images=False):
     """Model_Finetuning.test_model (:243-300): every cube of the scene through HSIViT loaded key-filtered from the
     fine-tuned checkpoint, class = 1 + argmax over logits[:, 1:], scores on the labeled test pixels.
-    -> (oa, aa, kappa, per-class recall, prediction map shaped like `gt`).  The colour-map PNGs (:296-298) are not written."""
+    -> (oa, aa, kappa, per-class recall, prediction map shaped like `gt`).  save_images=True also writes the reference's two
+    colour-map PNGs (:282-285, 299-300; `_save_maps`)."""
     device = torch.device(device)
     h, w, c = data_cubes[0].shape
     n_class = int(np.max(gt) + 1)
@@ -324,23 +326,46 @@ def test_model(data_cubes, test_gt, gt, save_dir, model_name, depth=12, dim=96, 
             _lib.check(lib.hsimae_class_argmax(C.byref(sp), logits.data_ptr(), logits.stride(0), n_class, 1, pred.data_ptr(), stream),
                        "hsimae_class_argmax")
             k0 += int(logits.shape[0])
-    oa, aa, kappa, ca = _scene_scores(pred.view(np.asarray(gt).shape), test_gt, gt, n_class, device)
-    return oa, aa, kappa, ca, pred.cpu().numpy().reshape(np.asarray(gt).shape)
+    return _score_and_save(pred.view(np.asarray(gt).shape), test_gt, gt, n_class, device, save_dir, model_name, save_images)
 
 
-def _scene_scores(pred, test_gt, gt, n_class, device):
-    """Model_Finetuning.py:285-290 on the device: the prediction map zeroed where `gt` is 0, counted against `test_gt`."""
+def _scene_scores(pred, test_gt, gt, n_class, device, want_masked=False):
+    """Model_Finetuning.py:285-290 on the device: the prediction map zeroed where `gt` is 0, counted against `test_gt`.
+    want_masked=True: -> (scores, that zeroed map)."""
     meter = ScoreMeter(n_class, device)
-    meter.update_map(np.asarray(test_gt).reshape(-1), pred.reshape(-1), mask_map=np.asarray(gt).reshape(-1))
-    return meter.compute()
+    masked = meter.update_map(np.asarray(test_gt).reshape(-1), pred.reshape(-1), mask_map=np.asarray(gt).reshape(-1))
+    return (meter.compute(), masked) if want_masked else meter.compute()
 
 
-def test_model_scene(scene, test_gt, gt, save_dir, model_name, depth=12, dim=96, s_depth=6, device="cuda:0", batch_size=8192):
+def _save_maps(save_dir, model_name, oa, pred, masked):
+    """The reference's two pictures (:267-269, 282-285, 299-300) in <save_dir>/<stem>/: <stem>_all_oa_<OA %>.png from the whole
+    prediction map and <stem>_oa_<OA %>.png from the map zeroed where the scene has no label."""
+    save_path = os.path.join(save_dir, model_name.replace(".pkl", ""))
+    os.makedirs(save_path, exist_ok=True)
+    tag = str(np.around(oa * 100, 2))
+    save_label_png(os.path.join(save_path, model_name.replace(".pkl", "_all_oa_" + tag + ".png")), pred)
+    save_label_png(os.path.join(save_path, model_name.replace(".pkl", "_oa_" + tag + ".png")), masked)
+
+
+def _score_and_save(pred, test_gt, gt, n_class, device, save_dir, model_name, save_images):
+    """What test_model and test_model_scene end with: the scores of the device-resident map `pred`, the pictures if asked for."""
+    shape = np.asarray(gt).shape
+    (oa, aa, kappa, ca), masked = _scene_scores(pred, test_gt, gt, n_class, device, want_masked=True)
+    if save_images:
+        _save_maps(save_dir, model_name, oa, pred.view(shape), masked.view(shape))
+    return oa, aa, kappa, ca, pred.cpu().numpy().reshape(shape)
+
+
+def test_model_scene(scene, test_gt, gt, save_dir, model_name, depth=12, dim=96, s_depth=6, device="cuda:0", batch_size=8192,
+                     views=(0,), save_images=False):
     """`test_model` from the scene itself: `scene` is the [H, W, C] `HSI_data` the reference cuts `data_cubes` from
     (Utils/Preprocessing.py:189-213, after GWPCA / norm), fp32 or fp64.  The same model, loaded the same way; the windows are
     cut on the device (HSIViT.predict_scene, at most `batch_size` pixels per chunk) instead of being built on the host.
+    `views` other than (0,): the label of the class probabilities averaged over these flips of every window
+    (HSIViT.classify_scene; "flips" = all four).  save_images=True also writes the reference's two colour-map PNGs.
     -> (oa, aa, kappa, per-class recall, prediction map shaped like `gt`), as test_model returns them."""
     device = torch.device(device)
+    views = scene_views(views)
     if len(scene.shape) != 3:
         raise ValueError(f"scene must be [H, W, C], got shape {tuple(scene.shape)}")
     c = int(scene.shape[2])
@@ -352,6 +377,8 @@ def test_model_scene(scene, test_gt, gt, save_dir, model_name, depth=12, dim=96,
     model_dict.update({k: v for k, v in loaded.items() if k in model_dict})
     model.load_state_dict(model_dict)
     model.eval()
-    pred = model.predict_scene(scene, batch_size=batch_size, on_device=True)
-    oa, aa, kappa, ca = _scene_scores(pred, test_gt, gt, n_class, device)
-    return oa, aa, kappa, ca, pred.cpu().numpy().reshape(np.asarray(gt).shape)
+    if views != (0,) or save_images:
+        pred = model.classify_scene(scene, batch_size=batch_size, views=views, on_device=True).labels
+    else:
+        pred = model.predict_scene(scene, batch_size=batch_size, on_device=True)
+    return _score_and_save(pred, test_gt, gt, n_class, device, save_dir, model_name, save_images)

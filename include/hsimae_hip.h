@@ -633,6 +633,47 @@ int hsimae_confusion_map(const int64_t* gt_map, const int64_t* mask_map, const i
                          int64_t* cm, int32_t* bad, void* stream);
 int hsimae_scores(const int64_t* cm, int32_t C, double* out, void* stream);
 
+/* ------------------------------------------------------------------ scene products: probabilities, flip views, confidence
+ * ADDED under HSIMAE_VERSION 108 like the entry points above: nothing that 108 already had changes; hsimae_class_argmax is as it
+ * was.  What hsimae_class_argmax throws away: the class probabilities of a chunk of pixels, averaged over the views (flips of
+ * the window, hsimae_scene_batch's) the caller ran the model on, and per pixel the label, its probability and the top-1 / top-2
+ * margin.  ONE CALL PER VIEW of a chunk, on one stream, view = 0 .. n_views - 1 in order; `logits` may be another buffer in
+ * every call, everything else stays.
+ *   logits   fp32 [N][ld] of this view; only the columns [first, C) are ever read (neither the classes below `first` nor
+ *            the pad [C, ld));
+ *   p_c      = softmax(logits[k, first:C])_c for first <= c < C and exactly 0 for c < first: the row maximum m over
+ *            [first, C), e_c = exp2((z_c - m) log2 e), s = their sum (per lane in ascending order, then a fixed shuffle tree),
+ *            p_c = e_c * (1 / s).  A NaN logit in [first, C) makes every p_c of the row with c >= first NaN;
+ *   acc      fp32 [N][lda], required, the caller's scratch for this chunk: acc[k, c] = p_c at view 0 (acc is NOT read: what
+ *            it held before cannot leak), acc[k, c] += p_c at a later view, for c < C; columns [C, lda) are never touched;
+ *   at view n_views - 1, with mean_c = acc[k, c] * fl(1 / n_views) (exact for 1, 2, 4 and 8 views):
+ *   probs    fp32 [N][ldp] or NULL: probs[k, c] = mean_c for c < C, rows in chunk order; columns [C, ldp) are never touched;
+ *   label_map int64 [H * W], required: at the row's pixel (`pixels[k]`, or `p0 + k` when `pixels` is NULL: the meaning of
+ *            hsimae_scene_params) the label: with n_views = 1, first + argmax(logits[k, first:C]), bit-identical to
+ *            hsimae_class_argmax; with more views first + argmax_c mean_c.  Ties go to the lowest index and NaN counts as
+ *            the maximum (torch.argmax);
+ *   conf_map fp32 [H * W] or NULL: mean_label;
+ *   margin_map fp32 [H * W] or NULL: mean_label - max of mean_c over c != label, c >= first; mean_label itself when
+ *            C - first = 1.  Not clamped: with one view, two logits one ulp apart may give a margin of -1 ulp.
+ *   A pixel index outside [0, H * W) writes none of the three maps (its `acc` and `probs` rows are written: they are in chunk
+ *   order).  A pixel that occurs twice in `pixels` is written once per occurrence: which one stays is unspecified unless
+ *   their logits are the same.
+ * One wave per row, one launch, no host wait, no atomics: two runs are bit-identical.
+ * Refusals: params NULL -> HSIMAE_ENULL; N < 0, C < 2, first outside [0, C), n_views outside [1, 8], view outside
+ * [0, n_views), ld or lda < C, probs given with ldp < C, H or W <= 0 -> HSIMAE_EDIMS; C > 1024 -> HSIMAE_EUNSUPPORTED; with
+ * N > 0 logits, acc or label_map NULL -> HSIMAE_ENULL; a pointer not aligned to its element -> HSIMAE_EALIGN.
+ * N = 0 -> HSIMAE_OK, nothing written. */
+typedef struct {
+    const float* logits; int32_t ld;
+    int32_t N, C, first;
+    int32_t view, n_views;
+    float* acc; int32_t lda;
+    int32_t H, W; int64_t p0; const int64_t* pixels;
+    int64_t* label_map; float* conf_map; float* margin_map;
+    float* probs; int32_t ldp;
+} hsimae_class_prob_params;
+int hsimae_class_prob(const hsimae_class_prob_params* p, void* stream);
+
 /* ------------------------------------------------------------------ gradient norm, clipping and the non-finite step skip
  * (what torch.nn.utils.clip_grad_norm_ and an `isfinite(...).item()` test do on the host, kept in device memory: no host wait).
  * ADDED under HSIMAE_VERSION 108 like the entry points above: nothing that 108 already had changes; hsimae_adamw_step is as it was.

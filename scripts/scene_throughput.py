@@ -8,6 +8,8 @@ leg, the host windowing time, and the number of pixels whose labels differ betwe
 
     python scripts/scene_throughput.py [--models base,large] [--reps 3] [--out FILE]
     python scripts/scene_throughput.py --profile     # predict_scene only (Base): run under rocprofv3 --kernel-trace --stats
+    python scripts/scene_throughput.py --views flips # predict_scene against classify_scene with one view and with these views
+                                                     # (a comma list of flip codes, or "flips"); with --profile: classify_scene
 """
 import argparse
 import contextlib
@@ -61,6 +63,44 @@ def new_flow(model, scene):
     return model.predict_scene(scene).numpy()
 
 
+def parse_views(text):
+    return "flips" if text == "flips" else tuple(int(v) for v in text.split(","))
+
+
+def views_flow(models, scene, views, reps, out):
+    """predict_scene, classify_scene(views=(0,)) and classify_scene(views) in one process, alternating, each warmed up first."""
+    rows = []
+    for name in models:
+        m = make_model(name)
+        legs = {"predict_scene": lambda: m.predict_scene(scene).numpy(),
+                "classify_one_view": lambda: m.classify_scene(scene).labels.numpy(),
+                "classify_views": lambda: m.classify_scene(scene, views=views).labels.numpy()}
+        secs = {k: [] for k in legs}
+        first = {}
+        for k, fn in legs.items():
+            release(m)
+            first[k] = fn()
+        for _ in range(reps):
+            for k, fn in legs.items():
+                release(m)
+                pred, s, _ = timed(fn)
+                secs[k].append(s)
+                assert np.array_equal(pred, first[k]), f"{k}: labels changed between runs"
+        row = {"model": name, "scene": [H, W, BANDS], "pixels": H * W, "reps": reps, "views": views, "chunk": m._scene_chunk(8192),
+               "one_view_labels_differ": int((first["predict_scene"] != first["classify_one_view"]).sum()),
+               "views_labels_differ": int((first["predict_scene"] != first["classify_views"]).sum())}
+        for k in legs:
+            row[k + "_s"] = [round(v, 4) for v in secs[k]]
+            row[k + "_px_per_s"] = round(H * W / float(np.median(secs[k])))
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+        del m
+        torch.cuda.empty_cache()
+    if out:
+        with open(out, "w") as fh:
+            json.dump(rows, fh, indent=1)
+
+
 def timed(fn):
     torch.cuda.synchronize()
     torch.cuda.reset_peak_memory_stats()
@@ -81,15 +121,19 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--out", default=None)
     ap.add_argument("--profile", action="store_true")
+    ap.add_argument("--views", default=None)
     a = ap.parse_args()
     scene = np.random.default_rng(0).standard_normal((H, W, BANDS))
     if a.profile:
         m = make_model("base")
-        new_flow(m, scene)
-        torch.cuda.synchronize()
-        new_flow(m, scene)
-        torch.cuda.synchronize()
-        print("profiled predict_scene (base) x2")
+        views = None if a.views is None else parse_views(a.views)
+        for _ in range(2):
+            new_flow(m, scene) if views is None else m.classify_scene(scene, views=views)
+            torch.cuda.synchronize()
+        print(f"profiled {'predict_scene' if views is None else f'classify_scene(views={views})'} (base) x2")
+        return
+    if a.views is not None:
+        views_flow(a.models.split(","), scene, parse_views(a.views), a.reps, a.out)
         return
     t0 = time.perf_counter()
     data_cubes = host_windows(scene)
