@@ -479,6 +479,8 @@ int hs_wgrad(const WgradParams& p, hipStream_t s) {
     bool any_planar = false;
     for (int i = 0; i < p.ntasks; ++i) {
         if (p.t[i].ldo % 8 || p.t[i].lda % 8) return HS_EDIMS;
+        // the row factor is applied where an fp32 dO is rounded to bf16 (load_rows); no kernel scales a bf16 dO
+        if (p.t[i].dO_rowscale && !p.t[i].dO_f32) return HS_EUNSUPPORTED;
         // planar operands: padded width a multiple of 64, whole 32-row DMA chunks (a row past M would be the next plane's row 0)
         if (p.t[i].dO_plane_rows && (p.t[i].ldo % 64 || p.t[i].dO_f32 || p.M % DC || p.t[i].dO_plane_rows < p.M)) return HS_EDIMS;
         if (p.t[i].A_plane_rows && (p.t[i].lda % 64 || p.M % DC || p.t[i].A_plane_rows < p.M)) return HS_EDIMS;

@@ -386,7 +386,9 @@ typedef struct {
     int32_t N, K;
     float* dW; int32_t ldw;
     float* db;
-    const float* dO_rowscale;     /* optional per-row factor [M] on an fp32 dO (DropPath); NULL = 1 */
+    const float* dO_rowscale;     /* optional per-row factor [M] on an fp32 dO (DropPath), applied in fp32 before the bf16 rounding;
+                                     NULL = 1.  With a bf16 dO (dO_f32 == 0) it must be NULL: HSIMAE_EUNSUPPORTED, nothing is launched
+                                     (fold the factor into the bf16 copy instead, as hsimae_backward does) */
     /* Operand layout (round 5).  0 = row-major [M][ldo] / [M][lda].  R > 0 = 64-column PLANES of R >= M rows each: the operand
        is [ldo / 64][R][64] (lda likewise), i.e. column c of row r lives at (c / 64) * R * 64 + r * 64 + c % 64 and ldo / lda is
        the padded width, a multiple of 64.  A producer that emits its operand 64 columns at a time (hsimae_enc_mlp_bwd: one
