@@ -326,9 +326,7 @@ int block_bwd(const BlkP& P, const BlockPlan& pl, const BlkOff& o, float* grads,
         { task(6, w.g0b, dp, b.g, pl.planar ? hp64 : hp, d, h, o.w2w, o.w2b); g.t[g.ntasks - 1].A_plane_rows = prow; }
         g.M = (int)M; g.det_base = grads; g.det_acc = det_acc;
         g.slab = pl.wgrad_slab ? w.slab : nullptr;               // this stream's slab (NULL: float atomics on dW also in the 256 x 256-tile launches)
-        int tiles = 0;
-        for (int i = 0; i < g.ntasks; ++i) tiles += ((g.t[i].N + 127) / 128) * ((g.t[i].K + 127) / 128);
-        g.msplit = wgrad_msplit(tiles, M, concurrent);
+        g.msplit = wgrad_msplit(wg_tiles(g, 128), M, concurrent);
         return hs_wgrad(g, s);
     };
     AttnParams a; std::memset(&a, 0, sizeof(a));

@@ -14,6 +14,7 @@
 // access; the first version's per-element 2-byte stores made every GEMM store-issue bound (profiles/).
 #include "common.h"
 #include "kernels.h"
+#include "plan.h"
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
@@ -804,137 +805,44 @@ int launch(const GemmParams& p, hipStream_t s) {
     return (int)hipGetLastError();
 }
 
-// Tiling of the wide layers, from scripts/gemm_sweep.py at the Large / Huge shapes (profiles/r02_gemm_sweep.txt):
-// 64-row panels (two to three workgroups per CU: one panel's staging / epilogue overlaps another's MFMA loop) win
-// wherever the weight image is small enough that streaming it once per 64 rows instead of once per 128 costs less than
-// the overlap gains: q|k|v at d = 256 235 -> 175 us, gate backward 461 -> 216 us; they lose at d = 512 when K is deep
-// (w2 303 -> 355 us).  256-deep A chunks pay only together with 64-row panels (alone: 1.3-1.7x slower).
-// (The A/B switches of this family — HSIMAE_GEMM_WIDE, _GEMM_KO_BM, _GEMM_KOUTER, _GEMM_F8_BM — went in round 6; hsimae_gemm_tiled
-//  still forces a tile shape for sweeps.)
-static int wide_mode() { return 1; }
-static thread_local int g_force_bm = 0, g_force_kc = 0;       // hsimae_gemm_tiled (tile sweeps): 0 = the shape rule below
-static int ko_bm() { return 0; }          // panel height of the k-outer products: the shape rule below
-static bool k_outer() { return true; }
-static bool small_weights(const GemmParams& p, bool dual) {
-    const int64_t nk = (int64_t)p.N * p.K;
-    if (p.K < 256) return false;
-    if (dual) return nk <= 400 * 1024;
-    return p.K <= 512 ? nk <= 800 * 1024 : nk <= 400 * 1024;
+// Which instantiation a call launches is decided in plan.h: plan_gemm() picks (KC, BM, F8, NCH) from the A kind, the epilogue, the
+// precision, N, K and the tile override, with the measurements behind its thresholds next to them, and HS_GEMM_INSTANCES lists
+// every tuple it can answer.  This expansion of the list is the only place that names gemm_kernel's template arguments, so the
+// library holds exactly those kernels; the rule and the list are compared without a GPU (tests/test_launch_plan_cpu.py).
+int launch_inst(int akind, int epi, const hsplan::GemmInst& g, const GemmParams& p, hipStream_t s) {
+#define HS_GEMM_LAUNCH(AK, EPI, KC, BM, F8, NCH) \
+    if (akind == AK && epi == EPI && g.kc == KC && g.bm == BM && g.f8 == F8 && g.nch == NCH) return launch<AK, EPI, KC, BM, F8, NCH>(p, s);
+    HS_GEMM_INSTANCES(HS_GEMM_LAUNCH)
+#undef HS_GEMM_LAUNCH
+    return HS_EUNSUPPORTED;
 }
 
-// fp8 (MX) form: 512-deep e4m3 chunks; 64-row panels by the same weight-size rule (any K)
-template <int AK, int EPI>
-int launch_f8(const GemmParams& p, hipStream_t s) {
-    if constexpr (EPI == E_LN_BWD || EPI == E_POS_F32) {
-        return HS_EUNSUPPORTED;
-    } else {
-        if (!p.W8 || !p.S8 || (EPI == E_SWIGLU && (!p.W8b || !p.S8b))) return HSIMAE_ENULL;
-        if (AK == A_F32_LN && p.K > 512) return HS_EUNSUPPORTED;
-        const int64_t nk = (int64_t)p.N * p.K * (EPI == E_SWIGLU ? 2 : 1);
-        // 64-row panels for every fp8 product: the e4m3 weight stream per panel is half the bf16 one, and two to three resident
-        // workgroups hide the fragment fetches that one 128-row workgroup exposes (Huge step 57.7 -> 55.6 ms; 128 rows everywhere:
-        // 76.8 ms, and a deeper fragment prefetch there does not help: 87.8 ms)
-        bool bm64 = true;
-        (void)nk;
-        if (g_force_bm) bm64 = g_force_bm == 64;
-        if constexpr (AK != A_F32_LN && EPI != E_SWIGLU) {
-            // deep K (several 512-chunks) and at most 4 n-chunks: k outer on 64-row panels, every chunk quantised once
-            if (k_outer() && p.K > 512 && p.N > 128 && p.N <= 512 && g_force_bm != 128) {
-                if constexpr (AK == A_BF16) {         // register-prefetched A chunks: 32-row panels keep them at 32 registers
-                    if (ko_bm() != 64) return p.N <= 256 ? launch<AK, EPI, 512, 32, 1, 2>(p, s) : launch<AK, EPI, 512, 32, 1, 4>(p, s);
-                }
-                return p.N <= 256 ? launch<AK, EPI, 512, 64, 1, 2>(p, s) : launch<AK, EPI, 512, 64, 1, 4>(p, s);
-            }
-        }
-        return bm64 ? launch<AK, EPI, 512, 64, 1>(p, s) : launch<AK, EPI, 512, 128, 1>(p, s);
-    }
-}
-
-template <int AK, int EPI>
-int launch_kc(const GemmParams& p, hipStream_t s) {
-    if (p.prec == HSIMAE_PREC_FP8) return launch_f8<AK, EPI>(p, s);
-    bool bm64 = wide_mode() && small_weights(p, EPI == E_SWIGLU);
-    if (g_force_bm) bm64 = g_force_bm == 64;
-    if constexpr (AK == A_F32_LN) {
-        if (p.K <= 128) return launch<AK, EPI, 128, 128>(p, s);
-        if (p.K <= 256) return bm64 ? launch<AK, EPI, 256, 64>(p, s) : launch<AK, EPI, 256, 128>(p, s);
-        if (p.K <= 512) return bm64 ? launch<AK, EPI, 512, 64>(p, s) : launch<AK, EPI, 512, 128>(p, s);
-        return HS_EUNSUPPORTED;
-    } else if constexpr (EPI == E_LN_BWD) {
-        return launch<AK, EPI, 128, 128>(p, s);
-    } else {
-        const bool kc256 = g_force_kc ? g_force_kc == 256 : (bm64 && p.K >= 256 && p.K <= 1024);
-        if constexpr (EPI != E_SWIGLU && EPI != E_SWIGLU_BWD) {
-            if (k_outer() && !g_force_bm && p.K > 256 && p.N > 128 && p.N <= 512) {
-                if constexpr (AK == A_BF16) {
-                    if (ko_bm() == 32) return p.N <= 256 ? launch<AK, EPI, 256, 32, 0, 2>(p, s) : launch<AK, EPI, 256, 32, 0, 4>(p, s);
-                }
-                return p.N <= 256 ? launch<AK, EPI, 256, 64, 0, 2>(p, s) : launch<AK, EPI, 256, 64, 0, 4>(p, s);
-            }
-        }
-        if (kc256) return bm64 ? launch<AK, EPI, 256, 64>(p, s) : launch<AK, EPI, 256, 128>(p, s);
-        return bm64 ? launch<AK, EPI, 128, 64>(p, s) : launch<AK, EPI, 128, 128>(p, s);
-    }
-}
-
-}  // namespace
-
-int hs_gemm(const GemmParams& p, int akind, int epi, hipStream_t s);
-int hs_gemm_tiled(const GemmParams& p, int akind, int epi, int bm, int kc, hipStream_t s) {
-    if ((bm != 0 && bm != 64 && bm != 128) || (kc != 0 && kc != 128 && kc != 256)) return HS_EDIMS;
-    g_force_bm = bm; g_force_kc = kc;
-    const int rc = hs_gemm(p, akind, epi, s);
-    g_force_bm = 0; g_force_kc = 0;
-    return rc;
-}
-
-int hs_gemm(const GemmParams& p, int akind, int epi, hipStream_t s) {
+// bm / kc: the tile override of hsimae_gemm_tiled (tile sweeps), 0 = plan_gemm's shape rule
+int run_gemm(const GemmParams& p, int akind, int epi, int bm, int kc, hipStream_t s) {
     if (p.M <= 0) return HS_OK;
     if (p.K % 32 || p.N % 16 || p.lda % 8 || p.ldo % 8) return HS_EDIMS;
     if ((epi == E_F32 || epi == E_RES_F32 || epi == E_POS_F32) && p.n_valid % 8) return HS_EDIMS;
     // the LayerNorm prologue reads whole octets of columns [0, ln_width): a partial octet or a width past K would read pad columns as data
     if (akind == A_F32_LN && (p.ln_width < 0 || p.ln_width % 8 || p.ln_width > p.K)) return HS_EDIMS;
-#define CASE(AK, EP) \
-    if (akind == AK && epi == EP) return launch_kc<AK, EP>(p, s);
-    CASE(A_F32_LN, E_BF16)
-    CASE(A_F32_LN, E_SWIGLU)
-    CASE(A_F32_LN, E_F32)
-    CASE(A_BF16, E_RES_F32)
-    CASE(A_BF16, E_POS_F32)
-    CASE(A_BF16, E_F32)
-    CASE(A_BF16, E_BF16)
-    if (akind == A_BF16 && epi == E_LN_BWD && p.N == 512) {
-        // 512-wide rows: four accumulator sets on 32-row panels (on 64-row panels they spilled 100 registers)
+    hsplan::GemmInst g;
+    const int rc = hsplan::plan_gemm(akind, epi, p.prec, p.N, p.K, bm, kc, g);
+    // Which refusal wins is part of the interface: a combination without a kernel, or a width the LayerNorm backward has no form
+    // for, before anything else; the K <= 512 of the fp8 LayerNorm prologue only after the MX images have been asked for.
+    if (rc && (epi == E_LN_BWD || !hsplan::gemm_has_kernel(akind, epi, p.prec))) return rc;
+    if (epi == E_LN_BWD) {
         if (p.n_valid != p.N || !p.lnx || !p.res || !p.gamma || !p.dgamma || !p.dbeta || p.ldr % 4 || p.ldo % 4) return HS_EUNSUPPORTED;
-        if (p.prec == HSIMAE_PREC_FP8) {
-            if (!p.W8 || !p.S8) return HSIMAE_ENULL;
-            return launch<A_BF16, E_LN_BWD, 512, 32, 1, 4>(p, s);
-        }
-        return launch<A_BF16, E_LN_BWD, 256, 32, 0, 4>(p, s);
+        if (g.nch == 1 && p.u_out) return HS_EUNSUPPORTED;      // the one-chunk epilogue stores no bf16 copy (only the k-outer forms at 256 / 512 do)
     }
-    if (akind == A_BF16 && epi == E_LN_BWD && p.N == 256) {
-        // 256-wide rows: the k-outer form (both chunks' accumulators live), bf16 or MX fp8 operands.  (At N = 512 the four
-        // accumulator sets + the per-thread dgamma / dbeta sums spill 100 registers; an LDS table for those sums with
-        // ds_add was 9 ms slower per Huge step than the separate ln_bwd pass.)
-        if (p.n_valid != p.N || !p.lnx || !p.res || !p.gamma || !p.dgamma || !p.dbeta || p.ldr % 4 || p.ldo % 4) return HS_EUNSUPPORTED;
-        if (p.prec == HSIMAE_PREC_FP8) {
-            if (!p.W8 || !p.S8) return HSIMAE_ENULL;
-            return ko_bm() != 64 ? launch<A_BF16, E_LN_BWD, 512, 32, 1, 2>(p, s) : launch<A_BF16, E_LN_BWD, 512, 64, 1, 2>(p, s);
-        }
-        return ko_bm() == 32 ? launch<A_BF16, E_LN_BWD, 256, 32, 0, 2>(p, s) : launch<A_BF16, E_LN_BWD, 256, 64, 0, 2>(p, s);
-    }
-    if (akind == A_BF16 && epi == E_LN_BWD) {
-        if (p.prec == HSIMAE_PREC_FP8) return HS_EUNSUPPORTED;
-        if (p.N != 128 || p.n_valid != 128 || !p.lnx || !p.res || !p.gamma || !p.dgamma || !p.dbeta || p.ldr % 4 || p.ldo % 4)
-            return HS_EUNSUPPORTED;
-        if (p.u_out) return HS_EUNSUPPORTED;        // the one-chunk epilogue stores no bf16 copy (only the k-outer forms at 256 / 512 do)
-        return launch_kc<A_BF16, E_LN_BWD>(p, s);
-    }
-    CASE(A_F32, E_SWIGLU_BWD)
-    CASE(A_F32, E_BF16)
-    CASE(A_F32, E_F32)
-#undef CASE
-    return HS_EUNSUPPORTED;
+    if (p.prec == HSIMAE_PREC_FP8 && (!p.W8 || !p.S8 || (epi == E_SWIGLU && (!p.W8b || !p.S8b)))) return HSIMAE_ENULL;
+    return rc ? rc : launch_inst(akind, epi, g, p, s);
+}
+
+}  // namespace
+
+int hs_gemm(const GemmParams& p, int akind, int epi, hipStream_t s) { return run_gemm(p, akind, epi, 0, 0, s); }
+int hs_gemm_tiled(const GemmParams& p, int akind, int epi, int bm, int kc, hipStream_t s) {
+    if ((bm != 0 && bm != 64 && bm != 128) || (kc != 0 && kc != 128 && kc != 256)) return HS_EDIMS;
+    return run_gemm(p, akind, epi, bm, kc, s);
 }
 
 HS_UNIT_VARIANT_BITS(gemm)

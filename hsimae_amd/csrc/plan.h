@@ -1,7 +1,9 @@
 // Host-side planning of the HSIMAE kernel library: model geometry, the flat parameter layout, the packed-weight layout and
-// its descriptor table, the workspace carve and the launch-shape rule of the weight-gradient kernel.  Pure C++ (no HIP):
-// api.hip includes it for the real library; csrc/plan_host.cpp builds the same code with g++ -fsanitize=address,undefined
-// into libhsimae_plan_asan.so, which the CPU tests drive through the same C entry points (tests/test_plan_asan_cpu.py).
+// its descriptor table, the workspace carve, the schedule of a pass and the launch rules of the GEMM and weight-gradient kernels
+// (plan_gemm, plan_wgrad).  Pure C++ (no HIP): api.hip, gemm.hip and wgrad.hip include it for the real library;
+// csrc/plan_host.cpp builds the same code with g++ -fsanitize=address,undefined into libhsimae_plan_asan.so, which the CPU tests
+// drive through the same C entry points (tests/test_plan_asan_cpu.py), and csrc/plan_sched_main.cpp into a stand-alone program
+// that prints the planners' decisions (tests/test_sched_plan_cpu.py, tests/test_launch_plan_cpu.py).
 #pragma once
 #include "../../include/hsimae_hip.h"
 #include <algorithm>
@@ -296,6 +298,178 @@ inline int wgrad_msplit(int tiles, int64_t M, int concurrent = 1) {
     if (ms < 8) ms = std::max(1, budget / std::max(1, tiles));
     if (ms >= 8) ms &= ~7;              // whole XCD groups (wgrad.hip places row slice ms on XCD ms % 8)
     return std::max(1, std::min(ms, chunks));
+}
+
+// ------------------------------------------------------------------ which gemm_kernel a call launches (gemm.hip)
+// hs_gemm launches ONE gemm_kernel<AK, EPI, KC, BM, F8, NCH> per call.  plan_gemm() below picks (KC, BM, F8, NCH) from the A kind,
+// the epilogue, the precision, N, K and the tile override of hsimae_gemm_tiled (0 = this rule); HS_GEMM_INSTANCES lists every
+// tuple it can answer, and gemm.hip instantiates exactly that list.  csrc/plan_sched_main.cpp prints both without a GPU and
+// tests/test_launch_plan_cpu.py holds them against each other and against the tables of the GPU tests (tests/gemm_ref.py).
+//
+// Tiling of the wide layers, from scripts/gemm_sweep.py at the Large / Huge shapes (profiles/r02_gemm_sweep.txt):
+// 64-row panels (two to three workgroups per CU: one panel's staging / epilogue overlaps another's MFMA loop) win
+// wherever the weight image is small enough that streaming it once per 64 rows instead of once per 128 costs less than
+// the overlap gains: q|k|v at d = 256 235 -> 175 us, gate backward 461 -> 216 us; they lose at d = 512 when K is deep
+// (w2 303 -> 355 us).  256-deep A chunks pay only together with 64-row panels (alone: 1.3-1.7x slower).
+struct GemmInst { int kc, bm, f8, nch; };          // A chunk depth, rows per workgroup, MX e4m3 operands, accumulator sets (1 = n outer)
+
+inline bool small_weights(int N, int K, bool dual) {
+    const int64_t nk = (int64_t)N * K;
+    if (K < 256) return false;
+    if (dual) return nk <= 400 * 1024;
+    return K <= 512 ? nk <= 800 * 1024 : nk <= 400 * 1024;
+}
+
+// (A kind, epilogue, precision) combinations that have a kernel at some shape.  The MX form has no position-embedding epilogue.
+inline bool gemm_has_kernel(int akind, int epi, int prec) {
+    if (prec == HSIMAE_PREC_FP8 && epi == HSIMAE_E_POS_F32) return false;
+    switch (akind) {
+    case HSIMAE_A_F32_LN: return epi == HSIMAE_E_BF16 || epi == HSIMAE_E_SWIGLU || epi == HSIMAE_E_F32;
+    case HSIMAE_A_BF16: return epi == HSIMAE_E_RES_F32 || epi == HSIMAE_E_POS_F32 || epi == HSIMAE_E_F32 || epi == HSIMAE_E_BF16 || epi == HSIMAE_E_LN_BWD;
+    case HSIMAE_A_F32: return epi == HSIMAE_E_SWIGLU_BWD || epi == HSIMAE_E_BF16 || epi == HSIMAE_E_F32;
+    }
+    return false;
+}
+
+// HSIMAE_OK and the instantiation, or the refusal the shape alone decides (HSIMAE_EUNSUPPORTED; `out` is then all zeros).  What
+// depends on the other members of the parameter block — strides, pointers — stays with hs_gemm.  force_bm: 0 / 64 / 128,
+// force_kc: 0 / 128 / 256 (hsimae_gemm_tiled, tile sweeps); the LayerNorm-backward epilogue has one tile shape per N and ignores both.
+inline int plan_gemm(int akind, int epi, int prec, int N, int K, int force_bm, int force_kc, GemmInst& out) {
+    out = GemmInst{0, 0, 0, 0};
+    if (!gemm_has_kernel(akind, epi, prec)) return HSIMAE_EUNSUPPORTED;
+    const bool f8 = prec == HSIMAE_PREC_FP8, ln = akind == HSIMAE_A_F32_LN, dual = epi == HSIMAE_E_SWIGLU;
+    if (epi == HSIMAE_E_LN_BWD) {
+        // rows of one 128-column chunk: the one-chunk epilogue (bf16 only).  256- / 512-wide rows: k outer, all chunks' accumulators
+        // live, bf16 or MX fp8 operands; four accumulator sets sit on 32-row panels (on 64-row panels they and the per-thread
+        // dgamma / dbeta sums spilled 100 registers, and an LDS table for those sums with ds_add was 9 ms slower per Huge step than
+        // the separate ln_bwd pass), and so do the register-prefetched A chunks of the fp8 form
+        if (N == 128 && !f8) out = GemmInst{128, 128, 0, 1};
+        else if (N == 256) out = f8 ? GemmInst{512, 32, 1, 2} : GemmInst{256, 64, 0, 2};
+        else if (N == 512) out = f8 ? GemmInst{512, 32, 1, 4} : GemmInst{256, 32, 0, 4};
+        else return HSIMAE_EUNSUPPORTED;
+        return HSIMAE_OK;
+    }
+    if (ln && K > 512) return HSIMAE_EUNSUPPORTED;          // the LayerNorm prologue stages the whole row as one chunk
+    const bool deep = !ln && !dual && N > 128 && N <= 512;  // at most 4 n-chunks, no prologue, no gate pair: k outer where K is deep
+    if (f8) {
+        // fp8 (MX) form: 512-deep e4m3 chunks.  64-row panels for every fp8 product: the e4m3 weight stream per panel is half the
+        // bf16 one, and two to three resident workgroups hide the fragment fetches that one 128-row workgroup exposes (Huge step
+        // 57.7 -> 55.6 ms; 128 rows everywhere: 76.8 ms, and a deeper fragment prefetch there does not help: 87.8 ms).
+        // Deep K (several 512-chunks): k outer, every chunk quantised once; bf16 A chunks are prefetched into registers, and
+        // 32-row panels keep them at 32 registers.
+        if (deep && K > 512 && force_bm != 128) out = GemmInst{512, akind == HSIMAE_A_BF16 ? 32 : 64, 1, N <= 256 ? 2 : 4};
+        else out = GemmInst{512, force_bm == 128 ? 128 : 64, 1, 1};
+        return HSIMAE_OK;
+    }
+    const bool bm64 = force_bm ? force_bm == 64 : small_weights(N, K, dual);
+    if (ln) out = GemmInst{K <= 128 ? 128 : K <= 256 ? 256 : 512, (K > 128 && bm64) ? 64 : 128, 0, 1};
+    else if (deep && epi != HSIMAE_E_SWIGLU_BWD && !force_bm && K > 256) out = GemmInst{256, 64, 0, N <= 256 ? 2 : 4};
+    else {
+        const bool kc256 = force_kc ? force_kc == 256 : (bm64 && K >= 256 && K <= 1024);
+        out = GemmInst{kc256 ? 256 : 128, bm64 ? 64 : 128, 0, 1};
+    }
+    return HSIMAE_OK;
+}
+
+// Every (AK, EPI, KC, BM, F8, NCH) plan_gemm can answer: 90.  gemm.hip expands the list into its launch switch, the only place
+// that instantiates gemm_kernel; a tuple missing here is HSIMAE_EUNSUPPORTED at the launch, and the CPU test proves there is none.
+#define HS_GI_LN(X, EPI)            /* LayerNorm prologue: the whole row is one chunk (KC from K); fp8: 512 */ \
+    X(HSIMAE_A_F32_LN, EPI, 128, 128, 0, 1) X(HSIMAE_A_F32_LN, EPI, 256, 64, 0, 1) X(HSIMAE_A_F32_LN, EPI, 256, 128, 0, 1) \
+    X(HSIMAE_A_F32_LN, EPI, 512, 64, 0, 1) X(HSIMAE_A_F32_LN, EPI, 512, 128, 0, 1) X(HSIMAE_A_F32_LN, EPI, 512, 64, 1, 1) \
+    X(HSIMAE_A_F32_LN, EPI, 512, 128, 1, 1)
+#define HS_GI_BF(X, AK, EPI)        /* bf16: k outer with 2 / 4 accumulator sets, else n outer, 128- / 256-deep chunks, 64 / 128 rows */ \
+    X(AK, EPI, 256, 64, 0, 2) X(AK, EPI, 256, 64, 0, 4) X(AK, EPI, 256, 64, 0, 1) X(AK, EPI, 256, 128, 0, 1) \
+    X(AK, EPI, 128, 64, 0, 1) X(AK, EPI, 128, 128, 0, 1)
+#define HS_GI_F8(X, AK, EPI, KOBM)  /* fp8: k outer on KOBM-row panels, else n outer on 64 / 128 rows */ \
+    X(AK, EPI, 512, KOBM, 1, 2) X(AK, EPI, 512, KOBM, 1, 4) X(AK, EPI, 512, 64, 1, 1) X(AK, EPI, 512, 128, 1, 1)
+#define HS_GEMM_INSTANCES(X) \
+    HS_GI_LN(X, HSIMAE_E_BF16) HS_GI_LN(X, HSIMAE_E_SWIGLU) HS_GI_LN(X, HSIMAE_E_F32) \
+    HS_GI_BF(X, HSIMAE_A_BF16, HSIMAE_E_RES_F32) HS_GI_BF(X, HSIMAE_A_BF16, HSIMAE_E_POS_F32) HS_GI_BF(X, HSIMAE_A_BF16, HSIMAE_E_F32) \
+    HS_GI_BF(X, HSIMAE_A_BF16, HSIMAE_E_BF16) HS_GI_BF(X, HSIMAE_A_F32, HSIMAE_E_BF16) HS_GI_BF(X, HSIMAE_A_F32, HSIMAE_E_F32) \
+    X(HSIMAE_A_F32, HSIMAE_E_SWIGLU_BWD, 128, 64, 0, 1) X(HSIMAE_A_F32, HSIMAE_E_SWIGLU_BWD, 128, 128, 0, 1) \
+    X(HSIMAE_A_F32, HSIMAE_E_SWIGLU_BWD, 256, 64, 0, 1) X(HSIMAE_A_F32, HSIMAE_E_SWIGLU_BWD, 256, 128, 0, 1) \
+    HS_GI_F8(X, HSIMAE_A_BF16, HSIMAE_E_RES_F32, 32) HS_GI_F8(X, HSIMAE_A_BF16, HSIMAE_E_F32, 32) HS_GI_F8(X, HSIMAE_A_BF16, HSIMAE_E_BF16, 32) \
+    HS_GI_F8(X, HSIMAE_A_F32, HSIMAE_E_SWIGLU_BWD, 64) HS_GI_F8(X, HSIMAE_A_F32, HSIMAE_E_BF16, 64) HS_GI_F8(X, HSIMAE_A_F32, HSIMAE_E_F32, 64) \
+    X(HSIMAE_A_BF16, HSIMAE_E_LN_BWD, 128, 128, 0, 1) X(HSIMAE_A_BF16, HSIMAE_E_LN_BWD, 256, 64, 0, 2) X(HSIMAE_A_BF16, HSIMAE_E_LN_BWD, 256, 32, 0, 4) \
+    X(HSIMAE_A_BF16, HSIMAE_E_LN_BWD, 512, 32, 1, 2) X(HSIMAE_A_BF16, HSIMAE_E_LN_BWD, 512, 32, 1, 4)
+#define HS_GI_ONE(AK, EPI, KC, BM, F8, NCH) +1
+static_assert(0 HS_GEMM_INSTANCES(HS_GI_ONE) == 90, "HS_GEMM_INSTANCES: one more or fewer kernel is a decision (tests/gemm_ref.py TABLE)");
+#undef HS_GI_ONE
+
+// ------------------------------------------------------------------ which kernel a weight-gradient launch runs (wgrad.hip)
+constexpr int kWgradDmaRows = 32;          // rows per LDS stage of the LDS-DMA kernels (one MFMA k-step); planar operands come in whole ones
+// T x T dW tiles of a launch.  (constexpr: the kernels of wgrad.hip count their tiles with it too.)
+constexpr int wg_tiles(const hsimae_wgrad_params& p, int T) {
+    int tiles = 0;
+    for (int i = 0; i < p.ntasks; ++i) tiles += ((p.t[i].N + T - 1) / T) * ((p.t[i].K + T - 1) / T);
+    return tiles;
+}
+
+// WG_REG: wgrad_kernel, register-staged 128 x 128 tiles (fp32 dO, unaligned or >= 4 GB operands); WG_DMA6 / WG_DMA3:
+// wgrad_dma_kernel<6 / 3, false>, 128 x 128 tiles fed by LDS-DMA; WG_BIG: wgrad_dma_kernel<4, true>, 256 x 256 tiles committed with
+// float atomics; WG_BIG_SLAB: the same through the caller's slab + wgrad_slab_reduce_kernel.
+enum WgradPath { WG_REG, WG_DMA6, WG_DMA3, WG_BIG, WG_BIG_SLAB };
+struct WgradPlan {
+    WgradPath path;
+    int msplit;          // row slices the launch uses: p.msplit on 128-tiles, its own on 256-tiles
+    int grid;            // workgroups of the main launch; 0: nothing to launch
+    int reduce_grid;     // workgroups of the slab reduce launch (WG_BIG_SLAB), else 0
+};
+
+// Everything hs_wgrad decides before it launches: its refusals, in its order, then the path and the grids.  Pointers are looked at
+// (NULL or not, 16-byte alignment), never through.
+inline int plan_wgrad(const hsimae_wgrad_params& p, WgradPlan& out) {
+    constexpr int DC = kWgradDmaRows;
+    out = WgradPlan{WG_REG, 0, 0, 0};
+    if (p.ntasks <= 0 || p.M <= 0) return HSIMAE_OK;
+    if (p.ntasks > 16 || p.msplit < 1) return HSIMAE_EDIMS;
+    bool any_planar = false;
+    for (int i = 0; i < p.ntasks; ++i) {
+        const hsimae_wgrad_task& t = p.t[i];
+        if (t.ldo % 8 || t.lda % 8) return HSIMAE_EDIMS;
+        // the row factor is applied where an fp32 dO is rounded to bf16 (load_rows); no kernel scales a bf16 dO
+        if (t.dO_rowscale && !t.dO_f32) return HSIMAE_EUNSUPPORTED;
+        // planar operands: padded width a multiple of 64, whole 32-row DMA chunks (a row past M would be the next plane's row 0)
+        if (t.dO_plane_rows && (t.ldo % 64 || t.dO_f32 || p.M % DC || t.dO_plane_rows < p.M)) return HSIMAE_EDIMS;
+        if (t.A_plane_rows && (t.lda % 64 || p.M % DC || t.A_plane_rows < p.M)) return HSIMAE_EDIMS;
+        // 32-bit byte offsets: an edge tile's lanes address plane index (n0 + 255) / 64, i.e. up to 256 columns past ld, and rely on
+        // the buffer bounds check to return zeros there — which holds only while that offset does not wrap
+        if ((int64_t)std::max(t.dO_plane_rows, t.A_plane_rows) * (std::max(t.ldo, t.lda) + 256) * 2 >= (1ll << 32)) return HSIMAE_EDIMS;
+        any_planar = any_planar || t.dO_plane_rows || t.A_plane_rows;
+    }
+    // all operands bf16 and addressable with 32-bit buffer offsets -> LDS-DMA kernels; fp32 dO (the layer-at-a-time schedule) or larger
+    // extents -> the register-staged wgrad_kernel.  (The switches that forced the older choice — HSIMAE_WGRAD_DMA, _WGRAD_BIG, _WGRAD_DS —
+    // and the ring depths nobody ran went in round 6.)
+    bool dma = true, big = true;
+    for (int i = 0; i < p.ntasks; ++i) {
+        const hsimae_wgrad_task& t = p.t[i];
+        if (t.dO_f32 || (int64_t)(p.M + DC) * t.ldo * 2 >= (1ll << 32) || (int64_t)(p.M + DC) * t.lda * 2 >= (1ll << 32)) dma = false;
+        if ((reinterpret_cast<uintptr_t>(t.dO) | reinterpret_cast<uintptr_t>(t.A)) & 15) dma = false;
+        if (t.N < 256 || t.K < 256) big = false;            // wide layers only: a 256-tile of a 128-wide matrix is half padding
+    }
+    if (any_planar && !dma) return HSIMAE_EUNSUPPORTED;     // only the LDS-DMA kernels address planes
+    if (dma && big) {
+        // 256 x 256 tiles, one workgroup per CU: the row split that fills the chip once (p.msplit is sized for 128-tiles)
+        const int t256 = wg_tiles(p, 256), nchunks = (p.M + DC - 1) / DC;
+        constexpr int wgs = 256;
+        out.msplit = std::max(1, std::min(wgs / std::max(1, t256), nchunks));
+        const int total = t256 * out.msplit;
+        out.grid = 8 * ((total + 7) / 8);
+        // slab + reduce pays where many row slices meet in one tile (Large: 13 tiles x 19 slices, 264 -> 196 us of atomics out,
+        // 35.70 -> 35.27 ms per step); with few slices per tile (Huge: 52 tiles x 4) the atomics are uncontended and the extra
+        // 64 MB pass costs more than it saves (48.86 -> 49.06 ms): atomics there, whether a slab is given or not
+        const bool slab = p.slab && !(total > 256 || out.msplit < 8);
+        out.path = slab ? WG_BIG_SLAB : WG_BIG;
+        out.reduce_grid = slab ? t256 * 128 : 0;
+        return HSIMAE_OK;
+    }
+    const int tiles = wg_tiles(p, 128);
+    out.msplit = p.msplit;
+    out.grid = (p.msplit & 7) == 0 ? 8 * tiles * (p.msplit / 8) : 8 * ((tiles + 7) / 8) * p.msplit;      // wgrad.hip decode_wg
+    // ring depth: a launch of at most one workgroup per CU has the LDS to itself (6 stages = 96 KB); larger launches keep 3
+    // stages so that three workgroups fit a CU
+    out.path = !dma ? WG_REG : out.grid > 256 ? WG_DMA3 : WG_DMA6;
+    return HSIMAE_OK;
 }
 
 // ------------------------------------------------------------------ the schedule of a pass, decided ONCE, by its forward

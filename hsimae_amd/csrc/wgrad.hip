@@ -9,6 +9,7 @@
 // Launches whose matrices are all at least 256 wide (d = 256 / 512) use 256x256 tiles instead (WT<true> below).
 #include "common.h"
 #include "kernels.h"
+#include "plan.h"
 #include <cstdlib>
 #include <algorithm>
 
@@ -197,6 +198,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradParams p) {
 // wave instruction, lane i -> bytes [16 i, 16 i + 16)).  Bank conflicts of the transpose reads are avoided by
 // permuting which 16-byte column chunk each lane FETCHES: slot s of row r holds column chunk s ^ swz(r).
 constexpr int DC = 32;                     // rows per stage (one MFMA k-step)
+static_assert(DC == hsplan::kWgradDmaRows, "plan_wgrad sizes chunks, row splits and planar operands by the stage height");
 
 typedef __attribute__((address_space(3))) void* lds_vptr;
 
@@ -262,11 +264,7 @@ __device__ __forceinline__ void wait_lds(Frag2 (&y)[4]) {
 template <int N>
 __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
-__host__ __device__ inline int wg_tiles(const WgradParams& p, int T) {
-    int tiles = 0;
-    for (int i = 0; i < p.ntasks; ++i) tiles += ((p.t[i].N + T - 1) / T) * ((p.t[i].K + T - 1) / T);
-    return tiles;
-}
+using hsplan::wg_tiles;          // T x T dW tiles of a launch: the planner's count (plan.h)
 
 template <int DS, bool BIG>                        // ring stages, tile geometry
 __global__ __launch_bounds__(WT<BIG>::NTHR) void wgrad_dma_kernel(WgradParams p) {
@@ -473,65 +471,32 @@ __global__ __launch_bounds__(512) void wgrad_slab_reduce_kernel(WgradParams p) {
 
 }  // namespace
 
+// Which kernel a launch runs, its row split and its grids are plan.h plan_wgrad()'s answer, with the refusals in front of them;
+// tests/test_launch_plan_cpu.py checks that rule without a GPU.
 int hs_wgrad(const WgradParams& p, hipStream_t s) {
-    if (p.ntasks <= 0 || p.M <= 0) return HS_OK;
-    if (p.ntasks > 16 || p.msplit < 1) return HS_EDIMS;
-    bool any_planar = false;
-    for (int i = 0; i < p.ntasks; ++i) {
-        if (p.t[i].ldo % 8 || p.t[i].lda % 8) return HS_EDIMS;
-        // the row factor is applied where an fp32 dO is rounded to bf16 (load_rows); no kernel scales a bf16 dO
-        if (p.t[i].dO_rowscale && !p.t[i].dO_f32) return HS_EUNSUPPORTED;
-        // planar operands: padded width a multiple of 64, whole 32-row DMA chunks (a row past M would be the next plane's row 0)
-        if (p.t[i].dO_plane_rows && (p.t[i].ldo % 64 || p.t[i].dO_f32 || p.M % DC || p.t[i].dO_plane_rows < p.M)) return HS_EDIMS;
-        if (p.t[i].A_plane_rows && (p.t[i].lda % 64 || p.M % DC || p.t[i].A_plane_rows < p.M)) return HS_EDIMS;
-        // 32-bit byte offsets: an edge tile's lanes address plane index (n0 + 255) / 64, i.e. up to 256 columns past ld, and rely on
-        // the buffer bounds check to return zeros there — which holds only while that offset does not wrap
-        if ((int64_t)std::max(p.t[i].dO_plane_rows, p.t[i].A_plane_rows) * (std::max(p.t[i].ldo, p.t[i].lda) + 256) * 2 >= (1ll << 32)) return HS_EDIMS;
-        any_planar = any_planar || p.t[i].dO_plane_rows || p.t[i].A_plane_rows;
-    }
-    const int tiles = wg_tiles(p, 128);
-    // all operands bf16 and addressable with 32-bit buffer offsets -> LDS-DMA kernels; fp32 dO (the layer-at-a-time schedule) or larger
-    // extents -> the register-staged wgrad_kernel.  (The switches that forced the older choice — HSIMAE_WGRAD_DMA, _WGRAD_BIG, _WGRAD_DS —
-    // and the ring depths nobody ran went in round 6.)
+    hsplan::WgradPlan pl;
+    if (const int rc = hsplan::plan_wgrad(p, pl)) return rc;
+    if (!pl.grid) return HS_OK;
+    constexpr int SB = WT<false>::STAGE_ELEMS * 2, SBB = WT<true>::STAGE_ELEMS * 2;      // bytes per ring stage
     static bool attrs = false;
     if (!attrs) {
         attrs = true;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_dma_kernel<6, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 6 * WT<false>::STAGE_ELEMS * 2);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_dma_kernel<4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * WT<true>::STAGE_ELEMS * 2);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_dma_kernel<6, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 6 * SB);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_dma_kernel<4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * SBB);
     }
-    bool dma = true, big = true;
-    for (int i = 0; i < p.ntasks; ++i) {
-        const WgradTask& t = p.t[i];
-        if (t.dO_f32 || (int64_t)(p.M + DC) * t.ldo * 2 >= (1ll << 32) || (int64_t)(p.M + DC) * t.lda * 2 >= (1ll << 32)) dma = false;
-        if ((reinterpret_cast<uintptr_t>(t.dO) | reinterpret_cast<uintptr_t>(t.A)) & 15) dma = false;
-        if (t.N < 256 || t.K < 256) big = false;            // wide layers only: a 256-tile of a 128-wide matrix is half padding
-    }
-    if (any_planar && !dma) return HS_EUNSUPPORTED;     // only the LDS-DMA kernels address planes
-    if (dma && big) {
-        // 256 x 256 tiles, one workgroup per CU: the row split that fills the chip once (p.msplit is sized for 128-tiles)
+    switch (pl.path) {
+    case hsplan::WG_REG: hipLaunchKernelGGL(wgrad_kernel, dim3(pl.grid), dim3(256), 0, s, p); break;
+    case hsplan::WG_DMA6: hipLaunchKernelGGL((wgrad_dma_kernel<6, false>), dim3(pl.grid), dim3(256), 6 * SB, s, p); break;
+    case hsplan::WG_DMA3: hipLaunchKernelGGL((wgrad_dma_kernel<3, false>), dim3(pl.grid), dim3(256), 3 * SB, s, p); break;
+    case hsplan::WG_BIG:
+    case hsplan::WG_BIG_SLAB: {
         WgradParams q = p;
-        const int t256 = wg_tiles(p, 256), nchunks = (p.M + DC - 1) / DC;
-        constexpr int wgs = 256;
-        q.msplit = std::max(1, std::min(wgs / std::max(1, t256), nchunks));
-        const int total = t256 * q.msplit;
-        const dim3 grid(8 * ((total + 7) / 8));
-        // slab + reduce pays where many row slices meet in one tile (Large: 13 tiles x 19 slices, 264 -> 196 us of atomics out,
-        // 35.70 -> 35.27 ms per step); with few slices per tile (Huge: 52 tiles x 4) the atomics are uncontended and the extra
-        // 64 MB pass costs more than it saves (48.86 -> 49.06 ms): atomics there
-        if (total > 256 || q.msplit < 8) q.slab = nullptr;
-        hipLaunchKernelGGL((wgrad_dma_kernel<4, true>), grid, dim3(512), 4 * WT<true>::STAGE_ELEMS * 2, s, q);
-        if (q.slab) hipLaunchKernelGGL(wgrad_slab_reduce_kernel, dim3(t256 * 128), dim3(512), 0, s, q);
-        return (int)hipGetLastError();
+        q.msplit = pl.msplit;
+        if (pl.path == hsplan::WG_BIG) q.slab = nullptr;      // (a given slab the plan does not use: atomics)
+        hipLaunchKernelGGL((wgrad_dma_kernel<4, true>), dim3(pl.grid), dim3(512), 4 * SBB, s, q);
+        if (pl.reduce_grid) hipLaunchKernelGGL(wgrad_slab_reduce_kernel, dim3(pl.reduce_grid), dim3(512), 0, s, q);
+        break;
     }
-    const dim3 grid((p.msplit & 7) == 0 ? 8 * tiles * (p.msplit / 8) : 8 * ((tiles + 7) / 8) * p.msplit);      // decode_wg
-    if (dma) {
-        // ring depth: a launch of at most one workgroup per CU has the LDS to itself (6 stages = 96 KB); larger
-        // launches keep 3 stages so that three workgroups fit a CU
-        constexpr int SB = WT<false>::STAGE_ELEMS * 2;
-        if (grid.x > 256) hipLaunchKernelGGL((wgrad_dma_kernel<3, false>), grid, dim3(256), 3 * SB, s, p);
-        else hipLaunchKernelGGL((wgrad_dma_kernel<6, false>), grid, dim3(256), 6 * SB, s, p);
-    } else {
-        hipLaunchKernelGGL(wgrad_kernel, grid, dim3(256), 0, s, p);
     }
     return (int)hipGetLastError();
 }

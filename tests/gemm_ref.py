@@ -1,4 +1,5 @@
-"""fp64 reference and element-wise error bound for hsimae_gemm (tests/test_gpu_gemm.py, tests/test_gemm_bound_cpu.py).
+"""fp64 reference, element-wise error bound and dispatch rule of hsimae_gemm (tests/test_gpu_gemm.py, tests/test_gemm_bound_cpu.py,
+tests/test_launch_plan_cpu.py).
 
 A plain module, not a conftest: the GPU tests and the CPU test of the bound import the same functions.
 
@@ -31,6 +32,74 @@ C1_F8 = 2048.0
 C2 = 4.0
 # LayerNorm statistics in fp32 (a tree sum over the row, x - mean, rsqrt): relative to (1 + kappa), kappa = rstd * mean|x|.
 C_LN = 16.0
+
+
+# ------------------------------------------------------------------------------------------------ the dispatch rule
+# hs_gemm launches one gemm_kernel<AK, EPI, KC, BM, F8, NCH> per call; csrc/plan.h plan_gemm picks it from the A kind, the epilogue,
+# the precision, N, K and the tiling.  TABLE lists every instantiation that rule can launch and `expected()` restates the rule.
+# tests/test_launch_plan_cpu.py compares both with the library's own rule and list (no GPU); tests/test_gpu_gemm.py proves that
+# its cases reach every row.  The constants are those of include/hsimae_hip.h (HSIMAE_A_*, HSIMAE_E_*, HSIMAE_PREC_*).
+AB, AF, LN = 0, 1, 2
+EB, EF, ER, EP, ES, ESB, ELB = 0, 1, 2, 3, 4, 5, 6
+BF16, FP8 = 0, 1
+PLAIN = [(AB, ER), (AB, EP), (AB, EF), (AB, EB), (AF, EB), (AF, EF)]          # bf16: no prologue, no gate pair
+F8_PLAIN = [(AB, ER), (AB, EF), (AB, EB), (AF, ESB), (AF, EB), (AF, EF)]      # fp8: no prologue, no gate pair
+
+
+def _table():
+    t = set()
+    for epi in (EB, ES, EF):
+        # LayerNorm prologue: the whole row is one chunk (KC from K), 64-row panels when the weights are small; fp8: 512
+        t |= {(LN, epi, 128, 128, 0, 1), (LN, epi, 256, 64, 0, 1), (LN, epi, 256, 128, 0, 1), (LN, epi, 512, 64, 0, 1),
+              (LN, epi, 512, 128, 0, 1), (LN, epi, 512, 64, 1, 1), (LN, epi, 512, 128, 1, 1)}
+    for ak, epi in PLAIN:
+        # k-outer with 2 / 4 accumulator sets, else n-outer with 128 / 256-deep chunks on 64 / 128-row panels
+        t |= {(ak, epi, 256, 64, 0, 2), (ak, epi, 256, 64, 0, 4), (ak, epi, 256, 64, 0, 1), (ak, epi, 256, 128, 0, 1),
+              (ak, epi, 128, 64, 0, 1), (ak, epi, 128, 128, 0, 1)}
+    t |= {(AF, ESB, kc, bm, 0, 1) for kc in (128, 256) for bm in (64, 128)}
+    for ak, epi in F8_PLAIN:
+        t |= {(ak, epi, 512, 32 if ak == AB else 64, 1, 2), (ak, epi, 512, 32 if ak == AB else 64, 1, 4),
+              (ak, epi, 512, 64, 1, 1), (ak, epi, 512, 128, 1, 1)}
+    t |= {(AB, ELB, 128, 128, 0, 1), (AB, ELB, 256, 64, 0, 2), (AB, ELB, 256, 32, 0, 4), (AB, ELB, 512, 32, 1, 2),
+          (AB, ELB, 512, 32, 1, 4)}
+    return t
+
+
+TABLE = _table()
+
+
+def small_weights(N, K, dual):
+    if K < 256:
+        return False
+    if dual:
+        return N * K <= 400 * 1024
+    return N * K <= (800 if K <= 512 else 400) * 1024
+
+
+def expected(ak, epi, prec, N, K, bm=0, kc=0):
+    """(AK, EPI, KC, BM, F8, NCH) of the kernel hs_gemm (hs_gemm_tiled with bm / kc) launches: a restatement of the rule."""
+    if epi == ELB:
+        if N == 512:
+            return (AB, ELB, 512, 32, 1, 4) if prec == FP8 else (AB, ELB, 256, 32, 0, 4)
+        if N == 256:
+            return (AB, ELB, 512, 32, 1, 2) if prec == FP8 else (AB, ELB, 256, 64, 0, 2)
+        return (AB, ELB, 128, 128, 0, 1)
+    if prec == FP8:
+        if ak != LN and epi != ES and K > 512 and 128 < N <= 512 and bm != 128:
+            return (ak, epi, 512, 32 if ak == AB else 64, 1, 2 if N <= 256 else 4)
+        return (ak, epi, 512, 128 if bm == 128 else 64, 1, 1)
+    bm64 = bm == 64 if bm else small_weights(N, K, epi == ES)
+    if ak == LN:
+        kcx = 128 if K <= 128 else 256 if K <= 256 else 512
+        return (ak, epi, kcx, 128 if kcx == 128 or not bm64 else 64, 0, 1)
+    if epi != ESB and not bm and K > 256 and 128 < N <= 512:
+        return (ak, epi, 256, 64, 0, 2 if N <= 256 else 4)
+    kc256 = kc == 256 if kc else (bm64 and 256 <= K <= 1024)
+    return (ak, epi, 256 if kc256 else 128, 64 if bm64 else 128, 0, 1)
+
+
+def inst_name(t):
+    return "gemm_kernel<%d, %d, %d, %d, %d, %d>" % t
 
 
 def bf(x):

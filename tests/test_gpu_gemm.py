@@ -1,10 +1,10 @@
 """hsimae_gemm, branch by branch, against a float64 reference (tests/gemm_ref.py) on a real MI355X.
 
-hs_gemm / launch_kc / launch_f8 (csrc/gemm.hip) choose one gemm_kernel<AK, EPI, KC, BM, F8, NCH> per call from the A kind,
-the epilogue, the precision, N, K and the tiling.  TABLE lists every instantiation that rule can launch and `expected()`
-restates the rule; the first test proves that the cases below reach every row of TABLE, so a branch added later without
-a case fails here.  Every case compares element by element under the bound of gemm_ref (never max-over-max), surrounds
-every output with canaries (NaN / sentinel fill, guard rows after M, guard columns between N and ld), and checks the
+hs_gemm (csrc/gemm.hip) launches one gemm_kernel<AK, EPI, KC, BM, F8, NCH> per call, chosen by plan_gemm (csrc/plan.h) from the
+A kind, the epilogue, the precision, N, K and the tiling.  gemm_ref.TABLE lists every instantiation that rule can launch and
+gemm_ref.expected() restates the rule (tests/test_launch_plan_cpu.py holds both against the library's own); the first test
+proves that the cases below reach every row of TABLE, so a branch added later without a case fails here.  Every case
+compares element by element under the bound of gemm_ref (never max-over-max), surrounds every output with canaries (NaN / sentinel fill, guard rows after M, guard columns between N and ld), and checks the
 [n_valid, N) column contract of the header.  The worst err / bound per case is printed ("RATIO ...", run with -s).
 """
 import ctypes as C
@@ -29,65 +29,7 @@ OK, EDIMS, EUNSUP, ENULL = 0, -1, -2, -4
 GUARD_ROWS = 3
 EPS_FN = 2.0 ** -18        # __expf / rcp in the SiLU epilogues (relative, on top of the bf16 rounding of the result)
 
-# ------------------------------------------------------------------------------------------------ the dispatch rule
-PLAIN = [(AB, ER), (AB, EP), (AB, EF), (AB, EB), (AF, EB), (AF, EF)]          # bf16: no prologue, no gate pair
-F8_PLAIN = [(AB, ER), (AB, EF), (AB, EB), (AF, ESB), (AF, EB), (AF, EF)]      # fp8: no prologue, no gate pair
-
-
-def _table():
-    t = set()
-    for epi in (EB, ES, EF):
-        # LayerNorm prologue: the whole row is one chunk (KC from K), 64-row panels when the weights are small; fp8: 512
-        t |= {(LN, epi, 128, 128, 0, 1), (LN, epi, 256, 64, 0, 1), (LN, epi, 256, 128, 0, 1), (LN, epi, 512, 64, 0, 1),
-              (LN, epi, 512, 128, 0, 1), (LN, epi, 512, 64, 1, 1), (LN, epi, 512, 128, 1, 1)}
-    for ak, epi in PLAIN:
-        # k-outer with 2 / 4 accumulator sets, else n-outer with 128 / 256-deep chunks on 64 / 128-row panels
-        t |= {(ak, epi, 256, 64, 0, 2), (ak, epi, 256, 64, 0, 4), (ak, epi, 256, 64, 0, 1), (ak, epi, 256, 128, 0, 1),
-              (ak, epi, 128, 64, 0, 1), (ak, epi, 128, 128, 0, 1)}
-    t |= {(AF, ESB, kc, bm, 0, 1) for kc in (128, 256) for bm in (64, 128)}
-    for ak, epi in F8_PLAIN:
-        t |= {(ak, epi, 512, 32 if ak == AB else 64, 1, 2), (ak, epi, 512, 32 if ak == AB else 64, 1, 4),
-              (ak, epi, 512, 64, 1, 1), (ak, epi, 512, 128, 1, 1)}
-    t |= {(AB, ELB, 128, 128, 0, 1), (AB, ELB, 256, 64, 0, 2), (AB, ELB, 256, 32, 0, 4), (AB, ELB, 512, 32, 1, 2),
-          (AB, ELB, 512, 32, 1, 4)}
-    return t
-
-
-TABLE = _table()
-
-
-def small_weights(N, K, dual):
-    if K < 256:
-        return False
-    if dual:
-        return N * K <= 400 * 1024
-    return N * K <= (800 if K <= 512 else 400) * 1024
-
-
-def expected(ak, epi, prec, N, K, bm=0, kc=0):
-    """(AK, EPI, KC, BM, F8, NCH) of the kernel hs_gemm (hs_gemm_tiled with bm / kc) launches: a restatement of the rule."""
-    if epi == ELB:
-        if N == 512:
-            return (AB, ELB, 512, 32, 1, 4) if prec == FP8 else (AB, ELB, 256, 32, 0, 4)
-        if N == 256:
-            return (AB, ELB, 512, 32, 1, 2) if prec == FP8 else (AB, ELB, 256, 64, 0, 2)
-        return (AB, ELB, 128, 128, 0, 1)
-    if prec == FP8:
-        if ak != LN and epi != ES and K > 512 and 128 < N <= 512 and bm != 128:
-            return (ak, epi, 512, 32 if ak == AB else 64, 1, 2 if N <= 256 else 4)
-        return (ak, epi, 512, 128 if bm == 128 else 64, 1, 1)
-    bm64 = bm == 64 if bm else small_weights(N, K, epi == ES)
-    if ak == LN:
-        kcx = 128 if K <= 128 else 256 if K <= 256 else 512
-        return (ak, epi, kcx, 128 if kcx == 128 or not bm64 else 64, 0, 1)
-    if epi != ESB and not bm and K > 256 and 128 < N <= 512:
-        return (ak, epi, 256, 64, 0, 2 if N <= 256 else 4)
-    kc256 = kc == 256 if kc else (bm64 and 256 <= K <= 1024)
-    return (ak, epi, 256 if kc256 else 128, 64 if bm64 else 128, 0, 1)
-
-
-def inst_name(t):
-    return "gemm_kernel<%d, %d, %d, %d, %d, %d>" % t
+from gemm_ref import F8_PLAIN, PLAIN, TABLE, expected, inst_name  # noqa: E402  (the dispatch rule: shared with the CPU test of plan_gemm)
 
 
 # ------------------------------------------------------------------------------------------------ the cases

@@ -19,9 +19,10 @@ any-order bound (M + 2 P + 2) * 2^-24 * (colsum|dOb| + |db0|) there.  Determinis
 addend to a multiple of 2^-44: P * 2^-45 more per element (on the register-staged bias the two extra addends per slice
 disappear in the slack of the any-order term, thousands of times larger at any magnitude a gradient has).
 
-`expected` restates the rule by which hs_wgrad (csrc/wgrad.hip) picks one of its five launch paths.  The rule has one more
-branch: operands of 4 GB or more ((M + 32) * ld * 2 >= 2^32) fall back to the register-staged kernel whatever their type.  No
-test that runs in seconds reaches it, so it has no case here and `expected` does not model it.
+`expected` restates the rule by which plan_wgrad (csrc/plan.h) picks one of hs_wgrad's five launch paths, and
+tests/test_launch_plan_cpu.py holds it against that function.  The rule has one more branch: operands of 4 GB or more
+((M + 32) * ld * 2 >= 2^32) fall back to the register-staged kernel whatever their type.  No GPU test that runs in seconds
+reaches it, so it has no case here and `expected` does not model it.
 """
 import torch
 
