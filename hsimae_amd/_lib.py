@@ -145,6 +145,21 @@ class ClassProbParams(C.Structure):
                 ("label_map", vp), ("conf_map", vp), ("margin_map", vp), ("probs", vp), ("ldp", i32)]
 
 
+class RowNormalizeParams(C.Structure):
+    _fields_ = [("x", vp), ("ld", i32), ("N", i32), ("D", i32), ("out", vp), ("ldo", i32), ("norms", vp)]
+
+
+class KnnTopkParams(C.Structure):
+    _fields_ = [("q", vp), ("ldq", i32), ("bank", vp), ("ldb", i32), ("Q", i32), ("M", i32), ("D", i32), ("k", i32),
+                ("idx", vp), ("sim", vp)]
+
+
+class KnnVoteParams(C.Structure):
+    _fields_ = [("idx", vp), ("sim", vp), ("Q", i32), ("k", i32), ("M", i32), ("bank_labels", vp), ("C", i32), ("first", i32),
+                ("inv_temperature", f32), ("H", i32), ("W", i32), ("p0", i64), ("pixels", vp),
+                ("label_map", vp), ("conf_map", vp), ("margin_map", vp), ("probs", vp), ("ldp", i32), ("bad", vp)]
+
+
 class GradSeg(C.Structure):
     _fields_ = [("g", vp), ("group", vp), ("n", i64)]
 
@@ -241,6 +256,9 @@ SYMBOLS = {
     "hsimae_confusion_map": (C.c_int, [vp, vp, vp, vp, i64, i32, vp, vp, vp]),
     "hsimae_scores": (C.c_int, [vp, i32, vp, vp]),
     "hsimae_class_prob": (C.c_int, [C.POINTER(ClassProbParams), vp]),
+    "hsimae_row_normalize": (C.c_int, [C.POINTER(RowNormalizeParams), vp]),
+    "hsimae_knn_topk": (C.c_int, [C.POINTER(KnnTopkParams), vp]),
+    "hsimae_knn_vote": (C.c_int, [C.POINTER(KnnVoteParams), vp]),
     "hsimae_encode": (C.c_int, [C.POINTER(Config), C.POINTER(IO), vp]),
     "hsimae_encode_backward": (C.c_int, [C.POINTER(Config), C.POINTER(IO), vp, vp, BUCKET_CB, vp, vp]),
     "hsimae_agg_pool": (C.c_int, [vp, vp, i32, i32, i32, i32, vp]),

@@ -295,6 +295,101 @@ class DualViT(HSIMAE):
                     raise RuntimeError("classify_scene: a pixel index was outside the scene")
         return SceneClassification(*out)
 
+    # ------------------------------------------------------------------ features of a scene, and their k-NN evaluation
+    def _scene_feature_rows(self, s, H, W, Cb, items, flips, bufs, out, bad):
+        """One chunk: the windows of the pixels `items` (device int64 [n]) flipped by `flips`, the unmasked encoder, and the
+        AGG pooling written into `out` (fp32 [n, T * D], contiguous rows of the caller's result).  The head GEMM is not run."""
+        lib = _lib.load()
+        T, L, D = self.input_size[0], self.input_size[1] ** 2, self.dim
+        n = int(items.shape[0])
+        win, n1, n2 = bufs
+        stream = torch.cuda.current_stream(s.device).cuda_stream
+        bp = _lib.SceneBatchParams(scene=s.data_ptr(), scene_f64=int(s.dtype == torch.float64), H=H, W=W, C=Cb,
+                                   items=items.data_ptr(), N=n, n_items=H * W, flips=flips.data_ptr(),
+                                   out=win.data_ptr(), sn=win.stride(0), sb=win.stride(2), sh=win.stride(3),
+                                   sw=win.stride(4), bad=bad.data_ptr())
+        _lib.check(lib.hsimae_scene_batch(C.byref(bp), stream), "hsimae_scene_batch")
+        _, _, _, st = self._run_forward(win[:n], 0.0, (n1[:n], n2[:n]), (T, L), want_latent=True, encoder_only=True)
+        lat = st["latent"].contiguous()
+        _lib.check(lib.hsimae_agg_pool(lat.data_ptr(), out.data_ptr(), n, T, L, D, stream), "hsimae_agg_pool")
+        st.release()
+
+    def scene_features(self, scene, pixels=None, batch_size=8192, flip=0, on_device=True):
+        """The pooled encoder features of a scene's pixels: what `head()` feeds the classification layer, fp32 [n, T * D], rows in
+        pixel order (row-major over the scene, or the order of `pixels`).  Per chunk, on the current stream: the windows flipped
+        by the constant code `flip` in 0 .. 3 (hsimae_scene_batch, classify_scene's path), the unmasked encoder, and
+        hsimae_agg_pool written straight into the chunk's rows of the result.  The head GEMM is not run: a checkpoint from
+        pretraining has no trained `cls_head`.  `scene`, `pixels`, `batch_size`, eval / no-grad behaviour: as predict_scene.
+        on_device=True (the default): the result stays on the model's device and nothing waits for the host."""
+        (flip,) = scene_views((flip,))
+        s, H, W, Cb, pix, dev, n_total, chunk = self._scene_args(scene, pixels, batch_size)
+        T, D = self.input_size[0], self.dim
+        with torch.no_grad(), torch.cuda.device(dev):
+            s = s.to(dev).contiguous()
+            items = torch.arange(H * W, dtype=torch.int64, device=dev) if pix is None else pix.to(dev)
+            feats = torch.empty(n_total, T * D, dtype=torch.float32, device=dev)
+            flips = torch.full((chunk,), flip, dtype=torch.uint8, device=dev)
+            bad = torch.zeros(1, dtype=torch.int32, device=dev)
+            bufs = self._scene_buffers(chunk, Cb, dev)
+            for k0 in range(0, n_total, chunk):
+                n = min(chunk, n_total - k0)
+                self._scene_feature_rows(s, H, W, Cb, items[k0:k0 + n], flips, bufs, feats[k0:k0 + n], bad)
+        return feats if on_device else feats.cpu()
+
+    KNN_GROUP_ROWS = 32768
+
+    def knn_scene(self, scene, bank_pixels, bank_labels, pixels=None, k=20, temperature=0.07, bank_flips=(0,), batch_size=8192,
+                  return_probs=False, on_device=False):
+        """classify_scene without a trained head: every pixel gets the weighted vote of the `k` labelled pixels whose pooled
+        encoder features are most similar to its own (knn.KNNClassifier; cosine similarity, weights exp(sim / temperature), DINO's
+        defaults).  The bank is `scene_features` of `bank_pixels` under each flip code of `bank_flips` ("flips" = all four),
+        concatenated as rows, with `bank_labels` (one per bank pixel, in [1, num_class)) repeated per code.  Per chunk of query
+        pixels: the features (as scene_features, flip 0, in the same chunks); per group of whole chunks (up to KNN_GROUP_ROWS
+        rows): hsimae_row_normalize, hsimae_knn_topk, and hsimae_knn_vote into device-resident maps.  `scene`, `pixels`, `batch_size`, eval / no-grad behaviour: as predict_scene.
+        -> SceneClassification like classify_scene's (probs fp32 [n, num_class] with return_probs=True), on the CPU after one
+        wait for the copies; on_device=True: all stay on the model's device and nothing waits for the host after the bank's
+        labels were checked.  The fitted classifier of the last call stays reachable as `self.last_knn` (its bank: `.bank`)."""
+        from .knn import KNNClassifier
+        bank_flips = scene_views(bank_flips)
+        s, H, W, Cb, pix, dev, n_total, chunk = self._scene_args(scene, pixels, batch_size)
+        nc = self.num_class
+        with torch.no_grad(), torch.cuda.device(dev):
+            s = s.to(dev).contiguous()
+            y = torch.as_tensor(np.asarray(bank_labels) if not isinstance(bank_labels, torch.Tensor) else bank_labels)
+            if y.dim() != 1 or y.dtype.is_floating_point or y.dtype == torch.bool:
+                raise ValueError("bank_labels must be a 1-D array of integer labels")
+            bank = [self.scene_features(s, bank_pixels, batch_size, flip=f, on_device=True) for f in bank_flips]
+            if bank[0].shape[0] != y.numel():
+                raise ValueError(f"{y.numel()} labels for {bank[0].shape[0]} bank pixels")
+            knn = KNNClassifier(k=k, temperature=temperature, num_class=nc, first=1)
+            knn.fit(bank[0] if len(bank) == 1 else torch.cat(bank), y.to(dev).repeat(len(bank_flips)))
+            del bank
+            self.last_knn = knn                            # the fitted classifier of the last call (its bank: knn.bank)
+            T, D = self.input_size[0], self.dim
+            items = torch.arange(H * W, dtype=torch.int64, device=dev) if pix is None else pix.to(dev)
+            labels = torch.zeros(H * W, dtype=torch.int64, device=dev)
+            conf = torch.zeros(H * W, dtype=torch.float32, device=dev)
+            margin = torch.zeros(H * W, dtype=torch.float32, device=dev)
+            probs = torch.empty(n_total, nc, dtype=torch.float32, device=dev) if return_probs else None
+            # the k-NN launches want more rows than one encoder chunk has (2,095 at Base: 33 workgroups of hsimae_knn_topk on 256
+            # CUs): the features of whole chunks are collected up to KNN_GROUP_ROWS rows, then searched and voted on together
+            group = max(1, self.KNN_GROUP_ROWS // chunk) * chunk
+            feats = torch.empty(min(group, n_total), T * D, dtype=torch.float32, device=dev)
+            flips = torch.zeros(chunk, dtype=torch.uint8, device=dev)
+            bad = torch.zeros(1, dtype=torch.int32, device=dev)
+            bufs = self._scene_buffers(chunk, Cb, dev)
+            for g0 in range(0, n_total, group):
+                gn = min(group, n_total - g0)
+                for k0 in range(g0, g0 + gn, chunk):
+                    n = min(chunk, g0 + gn - k0)
+                    self._scene_feature_rows(s, H, W, Cb, items[k0:k0 + n], flips, bufs, feats[k0 - g0:k0 - g0 + n], bad)
+                knn.predict_into(feats[:gn], H, W, items[g0:g0 + gn], labels, conf, margin, None if probs is None else probs[g0:g0 + gn])
+            out = [labels.view(H, W), conf.view(H, W), margin.view(H, W), probs]
+            if not on_device:
+                out = [None if t is None else t.cpu() for t in out]
+                knn.check()
+        return SceneClassification(*out)
+
     # ------------------------------------------------------------------ stochastic depth (Models.py:235-263, 687-731)
     def drop_rates(self):
         """DropPath probability of every encoder block in execution order (blocks_1, blocks_2, blocks)."""

@@ -382,3 +382,34 @@ def test_model_scene(scene, test_gt, gt, save_dir, model_name, depth=12, dim=96,
     else:
         pred = model.predict_scene(scene, batch_size=batch_size, on_device=True)
     return _score_and_save(pred, test_gt, gt, n_class, device, save_dir, model_name, save_images)
+
+
+def knn_eval_scene(scene, train_index, train_labels, test_gt, gt, pretrained, depth=12, dim=96, s_depth=6, k=20, temperature=0.07,
+                   bank_flips=(0,), device="cuda:0", batch_size=8192, save_dir=None, model_name=None, save_images=False):
+    """The evaluation of a checkpoint that needs no fine-tuning: a weighted k-NN classifier on the frozen encoder's pooled features
+    (Wu et al. 2018; DINO's knn_classifier), over the whole scene.  Inputs are what get_scene_set_dual returns: `scene` the
+    processed [H, W, C] `HSI_data`, `train_index` / `train_labels` the labelled pixels that form the bank, `test_gt` / `gt` as in
+    test_model_scene.  `pretrained`: the path of a state dict, loaded key-filtered as dual_branch_finetuning loads it: a
+    pretraining checkpoint (HSIMAE) and a fine-tuned one (DualViT) both work, the classification head is never used.
+    `k`, `temperature`, `bank_flips`: HSIViT.knn_scene's.  save_images=True writes test_model_scene's two pictures into
+    <save_dir>/<stem of model_name>/ (model_name defaults to the checkpoint's file name).
+    -> (oa, aa, kappa, per-class recall, prediction map shaped like `gt`), scored as test_model_scene scores."""
+    device = torch.device(device)
+    bank_flips = scene_views(bank_flips)
+    if len(scene.shape) != 3:
+        raise ValueError(f"scene must be [H, W, C], got shape {tuple(scene.shape)}")
+    if save_images and save_dir is None:
+        raise ValueError("save_images=True needs save_dir")
+    c = int(scene.shape[2])
+    n_class = int(np.max(gt) + 1)
+    model = HSIViT(img_size=9, patch_size=3, in_chans=1, bands=c, b_patch_size=8, num_class=n_class, embed_dim=dim, depth=depth,
+                   num_heads=dim // 16, s_depth=s_depth, sep_pos_embed=True, use_learnable_pos_emb=False).to(device)
+    model_dict = model.state_dict()
+    loaded = torch.load(pretrained, map_location=device)
+    model_dict.update({k_: v for k_, v in loaded.items() if k_ in model_dict and v.shape == model_dict[k_].shape})
+    model.load_state_dict(model_dict)
+    model.eval()
+    pred = model.knn_scene(scene, train_index, train_labels, k=k, temperature=temperature, bank_flips=bank_flips,
+                           batch_size=batch_size, on_device=True).labels
+    name = os.path.basename(str(pretrained)) if model_name is None else model_name
+    return _score_and_save(pred, test_gt, gt, n_class, device, save_dir, name, save_images)

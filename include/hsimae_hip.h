@@ -676,6 +676,72 @@ typedef struct {
 } hsimae_class_prob_params;
 int hsimae_class_prob(const hsimae_class_prob_params* p, void* stream);
 
+/* ------------------------------------------------------------------ k-NN evaluation of frozen features (csrc/knn.hip)
+ * ADDED under HSIMAE_VERSION 108 like the entry points above: nothing that 108 already had changes.  The weighted k-NN classifier a
+ * pretrained encoder is judged by without fine-tuning (Wu et al. 2018; DINO's knn_classifier): L2-normalised features, the k
+ * most similar rows of a labelled bank, a vote weighted by exp(similarity / T).  Three launches, no host wait, no atomics: two
+ * runs are bit-identical.  Common refusals: params NULL -> HSIMAE_ENULL; a negative count, or a leading dimension below the
+ * width -> HSIMAE_EDIMS; with work to do, a required pointer NULL -> HSIMAE_ENULL; a pointer not aligned to its element ->
+ * HSIMAE_EALIGN; N or Q = 0 -> HSIMAE_OK and no launch (the dimension checks come first).
+ *
+ * hsimae_row_normalize: out[r, c] = x[r, c] / max(||x[r]||_2, 1e-12) (torch.nn.functional.normalize: a zero row gives zeros)
+ *   for x fp32 [N][ld], out fp32 [N][ldo], columns c < D; `norms` fp32 [N] or NULL receives ||x[r]||_2.  out == x is allowed.
+ *   One wave per row, in this order: lane l forms ss = fmaf(x_c, x_c, ss) over c = l, l + 64, .. from 0; the 64 sums are added by
+ *   the xor tree (partner lane ^ 1, ^ 2, .. ^ 32); n = sqrtf(ss); r = 1 / fmaxf(n, 1e-12f) (IEEE division); out_c = x_c * r.
+ *   A row whose sum of squares overflows fp32 (||x|| above 1.8e19) comes out as zeros.  D = 0 -> HSIMAE_OK, no launch.
+ *
+ * hsimae_knn_topk: for every row of q fp32 [Q][ldq] the k largest dot products with the rows of bank fp32 [M][ldb] over D
+ *   columns: idx int32 [Q][k] and sim fp32 [Q][k], descending by similarity, equal similarities by ascending bank index, a NaN
+ *   similarity below every number (NaNs among themselves by ascending index).  Every dot product is an exact-fp32 fmaf chain
+ *   from +0 over the columns 0, 1, .., D - 1 in this order (v_mfma_f32_32x32x2_f32), one rounding per product, the same for
+ *   every bank row: duplicated bank rows give bit-equal similarities.  q and bank are read as given (normalise them first for
+ *   cosine similarity).  Rows must be 16-byte aligned: the two base pointers, and ldq % 4 = ldb % 4 = 0, else HSIMAE_EALIGN.
+ *   D <= 0, D % 4 != 0, k < 1 or k > M -> HSIMAE_EDIMS; k > 64, M > 2^20 or D > 4096 -> HSIMAE_EUNSUPPORTED.
+ *   The [Q][M] matrix is never written to memory: a workgroup keeps the lists of 64 query rows in LDS while it walks the bank.
+ *
+ * hsimae_knn_vote: idx / sim [Q][k] as hsimae_knn_topk wrote them (sim[r][0] is the row's largest), bank_labels int64 [M],
+ *   classes [first, C) (class 0 is "unlabelled" with first = 1, as in hsimae_class_prob).  Per row, with neighbour j in lane j:
+ *     w_j     = exp2(((sim_j - sim_0) * inv_temperature) * log2 e)     (inv_temperature: the host's fp64 1 / T rounded once;
+ *               the shift by sim_0 cancels in p and keeps T = 0.01 inside fp32)
+ *     score_c = the w_j with bank_labels[idx_j] = c added in rank order j = 0 .. k - 1 from 0
+ *     total   = sum of score_c: lane l adds its classes first + l, first + l + 64, .. in order, then the xor tree
+ *     p_c     = score_c * (1 / total), exactly 0 for c < first
+ *   probs fp32 [Q][ldp] or NULL: p_c for c < C in row order (columns [C, ldp) untouched); at the row's pixel (`pixels[r]`, or
+ *   p0 + r when `pixels` is NULL; nothing is written for a pixel outside [0, H * W)): label_map int64 = argmax_c p_c (ties to
+ *   the lower class), conf_map fp32 or NULL = p_label, margin_map fp32 or NULL = p_label - the largest other p_c (p_label
+ *   itself when C - first = 1).  A neighbour index outside [0, M) or a bank label outside [first, C) sets *bad (int32, required)
+ *   to 1 and gives the row label 0, confidence 0, margin 0 and probabilities 0.
+ *   M < 1, k < 1, C < 2, first outside [0, C), probs given with ldp < C, H or W <= 0, inv_temperature not a positive finite
+ *   number -> HSIMAE_EDIMS; k > 64 or C > 1024 -> HSIMAE_EUNSUPPORTED. */
+typedef struct {
+    const float* x; int32_t ld;
+    int32_t N, D;
+    float* out; int32_t ldo;
+    float* norms;
+} hsimae_row_normalize_params;
+int hsimae_row_normalize(const hsimae_row_normalize_params* p, void* stream);
+
+typedef struct {
+    const float* q; int32_t ldq;
+    const float* bank; int32_t ldb;
+    int32_t Q, M, D, k;
+    int32_t* idx; float* sim;
+} hsimae_knn_topk_params;
+int hsimae_knn_topk(const hsimae_knn_topk_params* p, void* stream);
+
+typedef struct {
+    const int32_t* idx; const float* sim;
+    int32_t Q, k, M;
+    const int64_t* bank_labels;
+    int32_t C, first;
+    float inv_temperature;
+    int32_t H, W; int64_t p0; const int64_t* pixels;
+    int64_t* label_map; float* conf_map; float* margin_map;
+    float* probs; int32_t ldp;
+    int32_t* bad;
+} hsimae_knn_vote_params;
+int hsimae_knn_vote(const hsimae_knn_vote_params* p, void* stream);
+
 /* ------------------------------------------------------------------ gradient norm, clipping and the non-finite step skip
  * (what torch.nn.utils.clip_grad_norm_ and an `isfinite(...).item()` test do on the host, kept in device memory: no host wait).
  * ADDED under HSIMAE_VERSION 108 like the entry points above: nothing that 108 already had changes; hsimae_adamw_step is as it was.
