@@ -13,6 +13,7 @@
 // recomputes the scores in both orientations instead of transposing dS through LDS.
 #include "common.h"
 #include "kernels.h"
+#include "phase.h"
 #include "plan.h"
 #ifndef HS_BLK_PRIO
 #define HS_BLK_PRIO 0      /* s_setprio level of waves 4-7 in blk128_fwd / blk128_bwd (round 6) */
@@ -55,20 +56,6 @@ namespace {
 //   * backward in ONE pass over the (query tile, key tile) grid: scores key-major (directly the B operand of dq^T),
 //     P and dS transposed through a 1.5 KB per-wave LDS tile for dk^T / dv^T — no second score / exp pass.
 // Same work decomposition: one workgroup = one sample x 4 heads, one wave per head.
-typedef __attribute__((ext_vector_type(4))) short s16x4_;
-typedef __attribute__((address_space(3))) bf16x4* lds_b64_p;
-__device__ __forceinline__ f32x4 mfma_k16(bf16x4 a, bf16x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(s16x4_, a), __builtin_bit_cast(s16x4_, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ bf16x4 tr4(const bf16_t* a) { return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b64_p)(a)); }
-__device__ __forceinline__ bf16x4 cvt4(f32x4 v) {
-    bf16x4 r;
-    r[0] = (bf16_t)v[0]; r[1] = (bf16_t)v[1]; r[2] = (bf16_t)v[2]; r[3] = (bf16_t)v[3];
-    return r;
-}
-
-__device__ __forceinline__ bf16x4 zero4_() { bf16x4 z; z[0] = z[1] = z[2] = z[3] = (bf16_t)0.f; return z; }
-
 constexpr int RS16 = 24;          // image row stride (elements) at head dim 16: 16 + 8 pad => conflict-free 8-byte row reads
 
 // HD = 8 (the decoder's heads, layer-at-a-time decoder: 216-token sequences): the same kernels with the head dim
@@ -149,7 +136,7 @@ __global__ __launch_bounds__(64 * HPW) void attn16_fwd_kernel(AttnParams p) {
         if (qt * 16 >= p.Ts) break;
         const int query = qt * 16 + c16;
         const int qcls = cls[query];
-        const bf16x4 bq = (HD == 16 || g < 2) ? *reinterpret_cast<const bf16x4*>(Qi + query * RS16 + 4 * g) : zero4_();
+        const bf16x4 bq = (HD == 16 || g < 2) ? *reinterpret_cast<const bf16x4*>(Qi + query * RS16 + 4 * g) : zero4();
         f32x4 s[NT];
         float m = -INFINITY;
         if constexpr (MODE0) {
@@ -157,8 +144,8 @@ __global__ __launch_bounds__(64 * HPW) void attn16_fwd_kernel(AttnParams p) {
             // need it (the per-element class compare below was a quarter of this loop's VALU work)
 #pragma unroll
             for (int kt = 0; kt < NT; ++kt) {
-                const bf16x4 ak = (HD == 16 || g < 2) ? *reinterpret_cast<const bf16x4*>(Ki + (kt * 16 + c16) * RS16 + 4 * g) : zero4_();
-                s[kt] = mfma_k16(ak, bq, z4);
+                const bf16x4 ak = (HD == 16 || g < 2) ? *reinterpret_cast<const bf16x4*>(Ki + (kt * 16 + c16) * RS16 + 4 * g) : zero4();
+                s[kt] = mfma16k16(ak, bq, z4);
                 if ((kt + 1) * 16 > p.Ts) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) s[kt][r] = (kt * 16 + g * 4 + r < p.Ts) ? s[kt][r] * sc : -INFINITY;
@@ -172,8 +159,8 @@ __global__ __launch_bounds__(64 * HPW) void attn16_fwd_kernel(AttnParams p) {
         } else {
 #pragma unroll
         for (int kt = 0; kt < NT; ++kt) {
-            const bf16x4 ak = (HD == 16 || g < 2) ? *reinterpret_cast<const bf16x4*>(Ki + (kt * 16 + c16) * RS16 + 4 * g) : zero4_();
-            s[kt] = mfma_k16(ak, bq, z4);
+            const bf16x4 ak = (HD == 16 || g < 2) ? *reinterpret_cast<const bf16x4*>(Ki + (kt * 16 + c16) * RS16 + 4 * g) : zero4();
+            s[kt] = mfma16k16(ak, bq, z4);
             const int4 kc = *reinterpret_cast<const int4*>(cls + kt * 16 + g * 4);
             const int kcl[4] = {kc.x, kc.y, kc.z, kc.w};
 #pragma unroll
@@ -201,7 +188,7 @@ __global__ __launch_bounds__(64 * HPW) void attn16_fwd_kernel(AttnParams p) {
 #pragma unroll
         for (int kt = 0; kt < NT; ++kt) {
             const bf16x4 av = tr4(Vi + (kt * 16 + 4 * g + q4) * RS16 + 4 * p4);      // V^T[d = c16][key 4g + j]
-            o = mfma_k16(av, cvt4(s[kt]), o);
+            o = mfma16k16(av, cvt4(s[kt]), o);
         }
         if (query < p.Ts) {
             bf16x4 ov;
@@ -291,18 +278,18 @@ __global__ __launch_bounds__(64 * HPW) void attn16_bwd_kernel(AttnParams p) {
         if (qt * 16 >= p.Ts) break;
         const int query = qt * 16 + c16;
         const int qcls = cls[query];
-        const bf16x4 bq = (HD == 16 || g < 2) ? *reinterpret_cast<const bf16x4*>(Qi + query * RS16 + 4 * g) : zero4_();
-        const bf16x4 bdo = (HD == 16 || g < 2) ? *reinterpret_cast<const bf16x4*>(Di + query * RS16 + 4 * g) : zero4_();
+        const bf16x4 bq = (HD == 16 || g < 2) ? *reinterpret_cast<const bf16x4*>(Qi + query * RS16 + 4 * g) : zero4();
+        const bf16x4 bdo = (HD == 16 || g < 2) ? *reinterpret_cast<const bf16x4*>(Di + query * RS16 + 4 * g) : zero4();
         const float lqn = -lse[query];
         const bf16x4 QT = tr4(Qi + qt * 16 * RS16 + troff);      // Q^T[d = c16][query 4g + j]
         const bf16x4 DT = tr4(Di + qt * 16 * RS16 + troff);
         f32x4 dqT = z4;
         // P (and dP) of one (query tile, key tile) pair: S^T[key 4g + r][query c16]
         auto pair_p = [&](int kt, f32x4& pv, f32x4& dp) {
-            const bf16x4 ak = (HD == 16 || g < 2) ? *reinterpret_cast<const bf16x4*>(Ki + (kt * 16 + c16) * RS16 + 4 * g) : zero4_();
-            const bf16x4 av = (HD == 16 || g < 2) ? *reinterpret_cast<const bf16x4*>(Vi + (kt * 16 + c16) * RS16 + 4 * g) : zero4_();
-            const f32x4 s = mfma_k16(ak, bq, z4);
-            dp = mfma_k16(av, bdo, z4);
+            const bf16x4 ak = (HD == 16 || g < 2) ? *reinterpret_cast<const bf16x4*>(Ki + (kt * 16 + c16) * RS16 + 4 * g) : zero4();
+            const bf16x4 av = (HD == 16 || g < 2) ? *reinterpret_cast<const bf16x4*>(Vi + (kt * 16 + c16) * RS16 + 4 * g) : zero4();
+            const f32x4 s = mfma16k16(ak, bq, z4);
+            dp = mfma16k16(av, bdo, z4);
             if constexpr (MODE0) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) pv[r] = __builtin_amdgcn_exp2f(fminf(fmaf(s[r], sc, lqn), 0.f));
@@ -334,13 +321,13 @@ __global__ __launch_bounds__(64 * HPW) void attn16_bwd_kernel(AttnParams p) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) ds[r] = pv[r] * (dp[r] - dl);
             const bf16x4 pb = cvt4(pv), dsb = cvt4(ds);
-            dqT = mfma_k16(KT[kt], dsb, dqT);
+            dqT = mfma16k16(KT[kt], dsb, dqT);
             *reinterpret_cast<bf16x4*>(Tp + c16 * TRS + 4 * g) = pb;
             *reinterpret_cast<bf16x4*>(Td + c16 * TRS + 4 * g) = dsb;
             asm volatile("" ::: "memory");
             const bf16x4 Bp = tr4(Tp + ttoff), Bds = tr4(Td + ttoff);       // [k = query 4g + j][col key c16]
-            dkT[kt] = mfma_k16(QT, Bds, dkT[kt]);
-            dvT[kt] = mfma_k16(DT, Bp, dvT[kt]);
+            dkT[kt] = mfma16k16(QT, Bds, dkT[kt]);
+            dvT[kt] = mfma16k16(DT, Bp, dvT[kt]);
         }
         {   // dq in place over this head's q rows of the finished query tile; dk / dv below, once every read of K / V is done.
             // The gradients leave as whole row segments (store16_wg) instead of 8-byte pieces at the row stride.
@@ -372,6 +359,10 @@ __global__ __launch_bounds__(64 * HPW) void attn16_bwd_kernel(AttnParams p) {
 
 constexpr int FS = 128 + 8;        // full-row image stride (elements) of the padded (HS_BF_SWZ = 0) layout of blk128_fwd_kernel
 
+}  // namespace
+HS_PHASE_COUNTERS(hs_phase_cycles_b128, hsimae_debug_phases_b128, 32)      // scripts/phase_blk128_bwd.py; [0, 16): blk128_bwd_kernel, [16, 32): blk128_fwd_kernel
+namespace {
+
 // ---------------------------------------------------------------------------------------------------------------
 // The attention half of an encoder Block in ONE persistent kernel (d = 128, 8 heads, <= 32 tokens per sample):
 //   u = LN1(x);  q|k|v = u Wqkv^T + b;  o = softmax(q k^T / 4) v per head;  x1 = x + rs * (o Wp^T + bp)
@@ -381,26 +372,6 @@ constexpr int FS = 128 + 8;        // full-row image stride (elements) of the pa
 // its 48 columns of Wqkv and its 16 columns of Wp stay in registers for the whole launch, its q / k / v columns go
 // from the MFMA accumulators (operands swapped: a lane owns 4 consecutive columns of one token) into the LDS images
 // the attention reads, so the only workgroup barriers are LN1 -> products and attention -> projection.
-// Per-phase cycle accounting for scripts/phase_blk128_bwd.py (compiled only with -DHS_PHASE_TIMING; never in the shipped library)
-#ifdef HS_PHASE_TIMING
-}  // namespace
-__device__ unsigned long long hs_phase_cycles_b128[32];      // [0, 16): blk128_bwd_kernel, [16, 32): blk128_fwd_kernel
-extern "C" __attribute__((visibility("default"))) int hsimae_debug_phases_b128(unsigned long long* out, int reset) {
-    int rc = (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(hs_phase_cycles_b128), sizeof(unsigned long long) * 32);
-    if (reset) { unsigned long long z[32] = {0}; rc |= (int)hipMemcpyToSymbol(HIP_SYMBOL(hs_phase_cycles_b128), z, sizeof(z)); }
-    return rc;
-}
-namespace {
-#define PHB_DECL unsigned long long ph_t0 = __builtin_readcyclecounter(), ph_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#define PHB(i) { const unsigned long long ph_t = __builtin_readcyclecounter(); ph_acc[i] += ph_t - ph_t0; ph_t0 = ph_t; }
-#define PHB_FLUSH() if (threadIdx.x == 64 * 5) { for (int i = 0; i < 12; ++i) atomicAdd(&hs_phase_cycles_b128[i], ph_acc[i]); }
-#define PHF_FLUSH() if (threadIdx.x == 64 * 5) { for (int i = 0; i < 12; ++i) atomicAdd(&hs_phase_cycles_b128[16 + i], ph_acc[i]); }
-#else
-#define PHB_DECL
-#define PHB(i)
-#define PHB_FLUSH()
-#define PHF_FLUSH()
-#endif
 // XOR swizzle of the 16-byte chunks of an unpadded 256-byte image row (found for blk128_bwd_kernel in round 4 by exhaustive search
 // over the XOR-linear maps of the row's low 4 bits; scripts/micro/lds_audit_blk128.py): chunk c of row r sits at chunk c ^ bsw(r).
 __device__ __forceinline__ int bsw(int row) { return ((row & 1) << 1) ^ ((row & 2) << 1) ^ ((row & 4) << 1) ^ (((row >> 3) & 1) * 9); }
@@ -513,7 +484,7 @@ __global__ __launch_bounds__(512, 2) void blk128_fwd_kernel(Blk128Args p) {
                 cm[qt][kt][r] = (kc >= 0 && kc == qc) ? 0.f : -INFINITY;
             }
     }
-    PHB_DECL
+    PH_DECL(12)
     if (HS_BF_EARLY_WAIT) __builtin_amdgcn_s_waitcnt(0x0F70);       // the first group's rows (wanted at once): no load pending on EITHER way into the loop head
     for (int first = blockIdx.x * SPW; first < p.nsamples; first += gridDim.x * SPW) {
         // global row of image row i (slot-major), or -1
@@ -553,11 +524,11 @@ __global__ __launch_bounds__(512, 2) void blk128_fwd_kernel(Blk128Args p) {
                 if (gr >= 0) HS_NT(HS_NT_C, reinterpret_cast<bf16x8*>(p.u + gr * 128 + lc8), ub);
             }
         }
-        PHB(0)
+        PH(0)
         fetch(first + gridDim.x * SPW);                           // next group's rows fly during this one
-        PHB(1)
+        PH(1)
         lds_barrier();
-        PHB(2)
+        PH(2)
         // ---- q | k | v of this head: transposed accumulators -> 8-byte writes into the images
 #pragma unroll
         for (int m = 0; m < 3; ++m) {
@@ -572,7 +543,7 @@ __global__ __launch_bounds__(512, 2) void blk128_fwd_kernel(Blk128Args p) {
                 *reinterpret_cast<bf16x4*>(img + cell(mt * 16)) = cvt4(acc);
             }
         }
-        PHB(3)
+        PH(3)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");        // own writes before own reads (only this wave touches these columns)
         // ---- attention of this head (one head per wave) slot by slot, O into its own image
 #pragma unroll
@@ -588,7 +559,7 @@ __global__ __launch_bounds__(512, 2) void blk128_fwd_kernel(Blk128Args p) {
 #pragma unroll
                 for (int kt = 0; kt < NT; ++kt) {
                     const bf16x4 ak = *reinterpret_cast<const bf16x4*>(Kf + cell(r0 + kt * 16));
-                    sv[kt] = mfma_k16(ak, bqf, cm[qt][kt]);           // masked pairs start (and stay) at -inf
+                    sv[kt] = mfma16k16(ak, bqf, cm[qt][kt]);           // masked pairs start (and stay) at -inf
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         sv[kt][r] *= sc;
@@ -611,7 +582,7 @@ __global__ __launch_bounds__(512, 2) void blk128_fwd_kernel(Blk128Args p) {
                 f32x4 o = z4;
 #pragma unroll
                 for (int kt = 0; kt < NT; ++kt)
-                    o = mfma_k16(tr4(Vf + trof(r0 + kt * 16)), cvt4(sv[kt]), o);
+                    o = mfma16k16(tr4(Vf + trof(r0 + kt * 16)), cvt4(sv[kt]), o);
                 bf16x4 ov;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) ov[r] = (bf16_t)(o[r] * inv);
@@ -627,9 +598,9 @@ __global__ __launch_bounds__(512, 2) void blk128_fwd_kernel(Blk128Args p) {
 #pragma unroll
         for (int mt = 0; mt < MTT; ++mt) xr[mt] = *reinterpret_cast<const f32x4*>(XR + (mt * 16 + c16) * L::XS + hc + 4 * g);
 #endif
-        PHB(4)
+        PH(4)
         lds_barrier();
-        PHB(5)
+        PH(5)
         // (as in blk128_bwd_kernel, HS_BB_EARLY_WAIT: the next group's x rows — issued in front of the q|k|v products — are waited for
         //  HERE, explicitly, so that the group's o / x1 stores below are not what the next iteration's first vmcnt wait drains)
         if (HS_BF_EARLY_WAIT) __builtin_amdgcn_s_waitcnt(0x0F70);
@@ -663,7 +634,7 @@ __global__ __launch_bounds__(512, 2) void blk128_fwd_kernel(Blk128Args p) {
             const int64_t gr = grow(irow);
             if (gr >= 0) *reinterpret_cast<float4*>(p.lse + gr * 8 + (idx & 1) * 4) = *reinterpret_cast<const float4*>(lse_s + idx * 4);
         }
-        PHB(6)
+        PH(6)
         // ---- projection: this wave's 16 output columns; transposed accumulators -> x1 leaves as 16-byte pieces
         //      (rows c16, columns hc + 4 g ..: two heads complete a 128-byte line)
         const f32x4 pbias = *reinterpret_cast<const f32x4*>(vec_s + 640 + hc + 4 * g);
@@ -681,25 +652,21 @@ __global__ __launch_bounds__(512, 2) void blk128_fwd_kernel(Blk128Args p) {
                 *reinterpret_cast<f32x4*>(p.x1 + orow[mt] * 128 + hc + 4 * g) = ov;
             }
         }
-        PHB(7)
+        PH(7)
         // no barrier here: the next group's LayerNorm writes only U (its readers passed the barrier above), and its
         // q|k|v image writes come after its own first barrier, which every wave reaches after the row stores above
     }
-    PHF_FLUSH()
+    PH_FLUSH(hs_phase_cycles_b128, 16, 12, 64 * 5)
 }
 
 template <int NT, int SPW>
 int launch_blk128(const Blk128Args& a, hipStream_t s) {
     using L = LayB<NT, SPW>;
-    static bool attr_set = false;
-    if (!attr_set) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(blk128_fwd_kernel<NT, SPW>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)L::TOTAL); attr_set = true; }
     // persistent, one 8-wave workgroup per CU: the weights (64 registers) + the attention state need ~156 registers;
     // forced to 128 (two workgroups per CU) the kernel spills 24-68 of them and is 20 % slower.  At most 256 workgroups.
     constexpr int wgs = 256;
     const int groups = (a.nsamples + SPW - 1) / SPW;
-    hipLaunchKernelGGL((blk128_fwd_kernel<NT, SPW>), dim3(groups < wgs ? groups : wgs), dim3(512), (size_t)L::TOTAL, s, a);
-    return (int)hipGetLastError();
+    return hs_launch_lds<blk128_fwd_kernel<NT, SPW>>(dim3(groups < wgs ? groups : wgs), dim3(512), L::TOTAL, s, a);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -889,7 +856,7 @@ __global__ __launch_bounds__(512) void blk128_bwd_kernel(Blk128BwdArgs p) {
             for (int ks = 0; ks < 4; ++ks) wq[m][ks] = *reinterpret_cast<const bf16x8*>(p.wqkv + ((size_t)((m * 8 + head) * 4 + ks) * 64 + lane) * 8);
     }
 #endif
-    PHB_DECL
+    PH_DECL(12)
     if (HS_BB_EARLY_WAIT) __builtin_amdgcn_s_waitcnt(0x0F70);       // the resident weight fragments: no load pending on EITHER way into the loop head
     for (int first = blockIdx.x * SPW; first < p.nsamples; first += gridDim.x * SPW) {
 #if !HS_BB_WQ_RESIDENT
@@ -907,7 +874,7 @@ __global__ __launch_bounds__(512) void blk128_bwd_kernel(Blk128BwdArgs p) {
         }
 #endif
         lds_barrier();                                            // the group's images are complete
-        PHB(0)
+        PH(0)
         if constexpr (RC) {
             // ---- q | k | v of this head from U (as blk128_fwd_kernel): transposed accumulators -> 8-byte writes into the images
             const int fa = fresh(fa0);
@@ -935,7 +902,7 @@ __global__ __launch_bounds__(512) void blk128_bwd_kernel(Blk128BwdArgs p) {
         const int nfirst = first + gridDim.x * SPW;
         const bool more = nfirst < p.nsamples;
         if (more) { fetch_q(nfirst, nx, tx, 0, NQ / 2); fetch_u(nfirst, nx, tx); }
-        PHB(1)
+        PH(1)
         // ---- dO[:, this head's columns] = dx1 Wp, delta = rowsum(dO * O) of this head; dO replaces O in place (own columns)
         const int fa_o = fresh(fa0);
 #pragma unroll
@@ -958,7 +925,7 @@ __global__ __launch_bounds__(512) void blk128_bwd_kernel(Blk128BwdArgs p) {
 #endif
         }
         if (more) fetch_q(nfirst, nx, tx, NQ / 2, NQ);
-        PHB(2)
+        PH(2)
         // class / padding mask of a (query tile, key tile) pair, as the accumulator the score MFMA starts from (0 or -inf): rebuilt
         // from LDS per group — 16 registers that would otherwise live (or spill) through the product / epilogue phases
         f32x4 cm[NT][NT];
@@ -1006,8 +973,8 @@ __global__ __launch_bounds__(512) void blk128_bwd_kernel(Blk128BwdArgs p) {
                 for (int kt = 0; kt < NT; ++kt) {
                     const bf16x4 ak = *reinterpret_cast<const bf16x4*>(Kf + (r0 + kt * 16) * BIR + hcell);
                     const bf16x4 av = *reinterpret_cast<const bf16x4*>(Vf + (r0 + kt * 16) * BIR + hcell);
-                    const f32x4 sv = mfma_k16(ak, bq, cm[qt][kt]);
-                    dps[kt] = mfma_k16(av, bdo, z4);
+                    const f32x4 sv = mfma16k16(ak, bq, cm[qt][kt]);
+                    dps[kt] = mfma16k16(av, bdo, z4);
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         pvs[kt][r] = __builtin_amdgcn_exp2f(fmaf(sv[r], sc, lqn));
@@ -1028,8 +995,8 @@ __global__ __launch_bounds__(512) void blk128_bwd_kernel(Blk128BwdArgs p) {
 #else
                     const bf16x4 ak = *reinterpret_cast<const bf16x4*>(Kf + (r0 + kt * 16) * BIR + hcell);
                     const bf16x4 av = *reinterpret_cast<const bf16x4*>(Vf + (r0 + kt * 16) * BIR + hcell);
-                    const f32x4 sv = mfma_k16(ak, bq, cm[qt][kt]);
-                    const f32x4 dp = mfma_k16(av, bdo, z4);
+                    const f32x4 sv = mfma16k16(ak, bq, cm[qt][kt]);
+                    const f32x4 dp = mfma16k16(av, bdo, z4);
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         pv[r] = __builtin_amdgcn_exp2f(fmaf(sv[r], sc, lqn));
@@ -1037,13 +1004,13 @@ __global__ __launch_bounds__(512) void blk128_bwd_kernel(Blk128BwdArgs p) {
                     }
 #endif
                     const bf16x4 pb = cvt4(pv), dsb = cvt4(ds);
-                    dqT = mfma_k16(KT[kt], dsb, dqT);
+                    dqT = mfma16k16(KT[kt], dsb, dqT);
                     *reinterpret_cast<bf16x4*>(Tp + tw) = pb;
                     *reinterpret_cast<bf16x4*>(Td + tw) = dsb;
                     asm volatile("" ::: "memory");
                     const bf16x4 Bp = tr4(Tp + ttoff), Bds = tr4(Td + ttoff);
-                    dkT[kt] = mfma_k16(QT, Bds, dkT[kt]);
-                    dvT[kt] = mfma_k16(DT, Bp, dvT[kt]);
+                    dkT[kt] = mfma16k16(QT, Bds, dkT[kt]);
+                    dvT[kt] = mfma16k16(DT, Bp, dvT[kt]);
                 }
                 bf16x4 v;
 #pragma unroll
@@ -1084,9 +1051,9 @@ __global__ __launch_bounds__(512) void blk128_bwd_kernel(Blk128BwdArgs p) {
                 }
             }
         }
-        PHB(3)
+        PH(3)
         lds_barrier();                                            // dq | dk | dv images complete
-        PHB(4)
+        PH(4)
         // ---- dq|dk|dv leave as whole rows (the q / k / v weight gradients' operand), a few pieces in front of every m-tile of
         //      du[:, this wave's 16 columns] = dq|dk|dv Wqkv (contraction over the 384 image columns) -> fp32 tile
         auto store_q = [&](int i0, int i1) {
@@ -1100,7 +1067,7 @@ __global__ __launch_bounds__(512) void blk128_bwd_kernel(Blk128BwdArgs p) {
                           *reinterpret_cast<const bf16x8*>(Qf + (pc >> 4) * L::IMG + wide(irow, pc & 15)));
             }
         };
-        PHB(5)
+        PH(5)
         const int fa_u = fresh(fa0);
 #pragma unroll
         for (int mt = 0; mt < MTT; ++mt) {
@@ -1114,9 +1081,9 @@ __global__ __launch_bounds__(512) void blk128_bwd_kernel(Blk128BwdArgs p) {
             *reinterpret_cast<f32x4*>(DU + (mt * 16 + c16) * DUS + hc + 4 * g) = acc;
             asm volatile("" ::: "memory");
         }
-        PHB(6)
+        PH(6)
         lds_barrier();                                            // du tile complete; every read of the images is done
-        PHB(7)
+        PH(7)
         // One explicit wait for everything in flight — this group's epilogue rows, the next group's inputs (issued a phase or more
         // ago) and the dq|dk|dv row stores — BEFORE the first dx store (round 6).  gfx950 counts loads and stores in one in-order
         // counter and the accesses here sit under per-row predicates, so hipcc fell back to s_waitcnt vmcnt(0) in front of the second
@@ -1163,11 +1130,11 @@ __global__ __launch_bounds__(512) void blk128_bwd_kernel(Blk128BwdArgs p) {
                 }
             }
         }
-        PHB(8)
+        PH(8)
         if (more) commit(nx, tx);                                     // images / lse of the next group (their readers are past the barrier above)
-        PHB(9)
+        PH(9)
     }
-    PHB_FLUSH()
+    PH_FLUSH(hs_phase_cycles_b128, 0, 12, 64 * 5)
     // dgamma / dbeta: 32 threads per column octet -> LDS, one commit per column and workgroup
     lds_barrier();
     float* red = DU;
@@ -1186,13 +1153,9 @@ template <int NT, int SPW, bool RC>
 int launch_blk128_bwd(const Blk128BwdArgs& a, hipStream_t s) {
     using L = LayBB<NT, SPW, RC>;
     static_assert(L::TOTAL <= 160 * 1024, "LDS");
-    static bool attr_set = false;
-    if (!attr_set) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(blk128_bwd_kernel<NT, SPW, RC>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)L::TOTAL); attr_set = true; }
     constexpr int wgs = 256;                  // persistent, one 8-wave workgroup per CU, as the forward
     const int groups = (a.nsamples + SPW - 1) / SPW;
-    hipLaunchKernelGGL((blk128_bwd_kernel<NT, SPW, RC>), dim3(groups < wgs ? groups : wgs), dim3(512), (size_t)L::TOTAL, s, a);
-    return (int)hipGetLastError();
+    return hs_launch_lds<blk128_bwd_kernel<NT, SPW, RC>>(dim3(groups < wgs ? groups : wgs), dim3(512), L::TOTAL, s, a);
 }
 
 template <int NT, bool BWD, int HD = 16, int HPW = 4>
@@ -1201,26 +1164,14 @@ int launch_attn16(const AttnParams& p, hipStream_t s) {
     const int hgroups = (p.heads + HPW - 1) / HPW;
     const size_t lds = L::CLS + HPW * (size_t)(BWD ? L::BWD_WAVE : L::FWD_WAVE) + 32;      // + the last transposed read's overhang at HD = 8
     if (lds > 160 * 1024) return HS_EUNSUPPORTED;
-    static bool attr_set = false;
     const dim3 grid(p.nsamples * hgroups), blk(64 * HPW);
     if constexpr (BWD) {
-        if (!attr_set) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn16_bwd_kernel<NT, HD, HPW, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn16_bwd_kernel<NT, HD, HPW, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            attr_set = true;
-        }
-        if (p.mode == 0) hipLaunchKernelGGL((attn16_bwd_kernel<NT, HD, HPW, true>), grid, blk, lds, s, p);
-        else hipLaunchKernelGGL((attn16_bwd_kernel<NT, HD, HPW, false>), grid, blk, lds, s, p);
+        if (p.mode != 0) return hs_launch_lds<attn16_bwd_kernel<NT, HD, HPW, false>>(grid, blk, lds, s, p);
+        return hs_launch_lds<attn16_bwd_kernel<NT, HD, HPW, true>>(grid, blk, lds, s, p);
     } else {
-        if (!attr_set) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn16_fwd_kernel<NT, HD, HPW, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn16_fwd_kernel<NT, HD, HPW, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            attr_set = true;
-        }
-        if (p.mode == 0) hipLaunchKernelGGL((attn16_fwd_kernel<NT, HD, HPW, true>), grid, blk, lds, s, p);
-        else hipLaunchKernelGGL((attn16_fwd_kernel<NT, HD, HPW, false>), grid, blk, lds, s, p);
+        if (p.mode != 0) return hs_launch_lds<attn16_fwd_kernel<NT, HD, HPW, false>>(grid, blk, lds, s, p);
+        return hs_launch_lds<attn16_fwd_kernel<NT, HD, HPW, true>>(grid, blk, lds, s, p);
     }
-    return (int)hipGetLastError();
 }
 
 // Stand-alone attention (the layer-at-a-time schedule of every width; at d = 128 the fused attention half, blk128_fwd / blk128_bwd,

@@ -20,6 +20,7 @@
 // LDS: cls 0.25 + U/O image 34.8 + staging 99.3 + lse 4 + vectors 6 = 144.4 KB => one workgroup per CU, 4 waves per SIMD.
 #include "common.h"
 #include "kernels.h"
+#include "phase.h"
 #include "plan.h"
 #include <cstdlib>
 
@@ -38,22 +39,7 @@
 #define HS_W256_EARLY 0 /* projection weights (first half) and residual pieces fetched in front of the attention */
 #endif
 
-// Per-phase cycle accounting for scripts/phase_wide.py (compiled only with -DHS_PHASE_TIMING; never in the shipped library)
-#ifdef HS_PHASE_TIMING
-__device__ unsigned long long hs_phase_cycles_wide[16];
-extern "C" __attribute__((visibility("default"))) int hsimae_debug_phases_wide(unsigned long long* out, int reset) {
-    int rc = (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(hs_phase_cycles_wide), sizeof(unsigned long long) * 16);
-    if (reset) { unsigned long long z[16] = {0}; rc |= (int)hipMemcpyToSymbol(HIP_SYMBOL(hs_phase_cycles_wide), z, sizeof(z)); }
-    return rc;
-}
-#define PH_DECL unsigned long long ph_t0 = __builtin_readcyclecounter(), ph_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#define PH(i) { const unsigned long long ph_t = __builtin_readcyclecounter(); ph_acc[i] += ph_t - ph_t0; ph_t0 = ph_t; }
-#define PH_FLUSH() if (threadIdx.x == 64 * 5) { for (int i = 0; i < 12; ++i) atomicAdd(&hs_phase_cycles_wide[i], ph_acc[i]); }
-#else
-#define PH_DECL
-#define PH(i)
-#define PH_FLUSH()
-#endif
+HS_PHASE_COUNTERS(hs_phase_cycles_wide, hsimae_debug_phases_wide, 16)      // scripts/phase_wide.py
 
 namespace {
 
@@ -62,18 +48,6 @@ constexpr int PU = DW + 16;                         // U / O image row pitch (el
 constexpr int PS = 3 * DW + 8;                      // staging image row pitch: 8-byte tile writes 2-way, transpose reads 2-way (scripts/micro/lds_banks.py)
 constexpr int NTHW = 1024;
 constexpr int KSW = DW / 32;                        // k-steps over the model width
-
-typedef __attribute__((ext_vector_type(4))) short s16x4w;
-typedef __attribute__((address_space(3))) bf16x4* lds_b64w;
-__device__ __forceinline__ f32x4 mfma_k16w(bf16x4 a, bf16x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(s16x4w, a), __builtin_bit_cast(s16x4w, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ bf16x4 tr4w(const bf16_t* a) { return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b64w)(a)); }
-__device__ __forceinline__ bf16x4 cvt4w(f32x4 v) {
-    bf16x4 r;
-    r[0] = (bf16_t)v[0]; r[1] = (bf16_t)v[1]; r[2] = (bf16_t)v[2]; r[3] = (bf16_t)v[3];
-    return r;
-}
 
 struct Blk256Args {
     const float* x; const float* n1w; const float* n1b;
@@ -141,7 +115,7 @@ __global__ __launch_bounds__(NTHW, 1) void blk256_fwd_kernel(Blk256Args p) {
         return *reinterpret_cast<const bf16x8*>(p.wqkv + ((size_t)((m * HW + head) * KSW + ks) * 64 + lane) * 8);
     };
 
-    PH_DECL
+    PH_DECL(12)
     for (int first = blockIdx.x * SPW; first < p.nsamples; first += gridDim.x * SPW) {
         PH(11)
         // The per-lane address pieces are laundered once per group: left alone, hipcc hoists ~25 registers of loop-invariant
@@ -225,11 +199,11 @@ __global__ __launch_bounds__(NTHW, 1) void blk256_fwd_kernel(Blk256Args p) {
         bf16x4 qT[MTT], kT[MTT];
 #pragma unroll
         for (int mt = 0; mt < MTT; ++mt) {
-            qT[mt] = cvt4w(acc[0][mt]); kT[mt] = cvt4w(acc[1][mt]);
+            qT[mt] = cvt4(acc[0][mt]); kT[mt] = cvt4(acc[1][mt]);
             bf16_t* dst = Sf + (mt * 16 + c16) * PS + hc + 4 * g;
             *reinterpret_cast<bf16x4*>(dst) = qT[mt];
             *reinterpret_cast<bf16x4*>(dst + DW) = kT[mt];
-            *reinterpret_cast<bf16x4*>(dst + 2 * DW) = cvt4w(acc[2][mt]);
+            *reinterpret_cast<bf16x4*>(dst + 2 * DW) = cvt4(acc[2][mt]);
         }
         // loads first (see above): the projection weights of this wave's 16 output columns, the residual pieces of its output
         // tiles (L2-hot: the LayerNorm read the same rows) and the next group's rows — all in flight under the attention
@@ -283,7 +257,7 @@ __global__ __launch_bounds__(NTHW, 1) void blk256_fwd_kernel(Blk256Args p) {
                 float m = -INFINITY;
 #pragma unroll
                 for (int kt = 0; kt < NT; ++kt) {
-                    sv[kt] = mfma_k16w(kT[slot * NT + kt], qT[slot * NT + qt], cmk[kt]);     // masked pairs start (and stay) at -inf
+                    sv[kt] = mfma16k16(kT[slot * NT + kt], qT[slot * NT + qt], cmk[kt]);     // masked pairs start (and stay) at -inf
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         sv[kt][r] *= sc;
@@ -306,7 +280,7 @@ __global__ __launch_bounds__(NTHW, 1) void blk256_fwd_kernel(Blk256Args p) {
                 f32x4 o = z4;
 #pragma unroll
                 for (int kt = 0; kt < NT; ++kt)
-                    o = mfma_k16w(tr4w(Sf + (r0 + kt * 16 + 4 * g + q4) * PS + 2 * DW + hc + 4 * p4), cvt4w(sv[kt]), o);
+                    o = mfma16k16(tr4(Sf + (r0 + kt * 16 + 4 * g + q4) * PS + 2 * DW + hc + 4 * p4), cvt4(sv[kt]), o);
                 bf16x4 ov;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) ov[r] = (bf16_t)(o[r] * inv);
@@ -363,7 +337,7 @@ __global__ __launch_bounds__(NTHW, 1) void blk256_fwd_kernel(Blk256Args p) {
         lds_barrier();                                            // B4: the O image is read; the next group's LayerNorm may overwrite it
         PH(10)
     }
-    PH_FLUSH()
+    PH_FLUSH(hs_phase_cycles_wide, 0, 12, 64 * 5)
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -523,7 +497,7 @@ __global__ __launch_bounds__(NTHW, 1) void blk256_bwd_kernel(Blk256BwdArgs p) {
                 wc = wn;
             }
 #pragma unroll
-            for (int mt = 0; mt < MTT; ++mt) dob[mt] = cvt4w(acc[mt]);
+            for (int mt = 0; mt < MTT; ++mt) dob[mt] = cvt4(acc[mt]);
         }
         // class / padding mask of a (query tile, key tile) pair, as the accumulator the score MFMA starts from (0 or -inf)
         f32x4 cm[NT][NT];
@@ -550,7 +524,7 @@ __global__ __launch_bounds__(NTHW, 1) void blk256_bwd_kernel(Blk256BwdArgs p) {
             f32x4 dkT[NT], dvT[NT];
             bf16x4 KT[NT];
 #pragma unroll
-            for (int kt = 0; kt < NT; ++kt) { dkT[kt] = z4; dvT[kt] = z4; KT[kt] = tr4w(Kf + (r0 + kt * 16) * PB + troff); }
+            for (int kt = 0; kt < NT; ++kt) { dkT[kt] = z4; dvT[kt] = z4; KT[kt] = tr4(Kf + (r0 + kt * 16) * PB + troff); }
 #pragma unroll
             for (int qt = 0; qt < NT; ++qt) {
                 if (qt * 16 >= p.Ts) break;
@@ -559,8 +533,8 @@ __global__ __launch_bounds__(NTHW, 1) void blk256_bwd_kernel(Blk256BwdArgs p) {
                 const bf16x4 bq = *reinterpret_cast<const bf16x4*>(Qf + qcell);
                 const bf16x4 bdo = *reinterpret_cast<const bf16x4*>(Xf + qcell);
                 const float lqn = -lse_h[query];
-                const bf16x4 QT = tr4w(Qf + (r0 + qt * 16) * PB + troff);
-                const bf16x4 DT = tr4w(Xf + (r0 + qt * 16) * PB + troff);
+                const bf16x4 QT = tr4(Qf + (r0 + qt * 16) * PB + troff);
+                const bf16x4 DT = tr4(Xf + (r0 + qt * 16) * PB + troff);
                 f32x4 dqT = z4;
                 // delta_i = sum_j P_ij dP_ij: with at most NT = 2 key tiles per query tile both P and dP are in hand before dS
                 f32x4 pvs[NT], dps[NT];
@@ -569,8 +543,8 @@ __global__ __launch_bounds__(NTHW, 1) void blk256_bwd_kernel(Blk256BwdArgs p) {
                 for (int kt = 0; kt < NT; ++kt) {
                     const bf16x4 ak = *reinterpret_cast<const bf16x4*>(Kf + (r0 + kt * 16) * PB + hcell);
                     const bf16x4 av = *reinterpret_cast<const bf16x4*>(Vf + (r0 + kt * 16) * PB + hcell);
-                    const f32x4 sv = mfma_k16w(ak, bq, cm[qt][kt]);
-                    dps[kt] = mfma_k16w(av, bdo, z4);
+                    const f32x4 sv = mfma16k16(ak, bq, cm[qt][kt]);
+                    dps[kt] = mfma16k16(av, bdo, z4);
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         pvs[kt][r] = __builtin_amdgcn_exp2f(fmaf(sv[r], sc, lqn));
@@ -583,14 +557,14 @@ __global__ __launch_bounds__(NTHW, 1) void blk256_bwd_kernel(Blk256BwdArgs p) {
                     f32x4 ds;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) ds[r] = pvs[kt][r] * (dps[kt][r] - dl);
-                    const bf16x4 pb = cvt4w(pvs[kt]), dsb = cvt4w(ds);
-                    dqT = mfma_k16w(KT[kt], dsb, dqT);
+                    const bf16x4 pb = cvt4(pvs[kt]), dsb = cvt4(ds);
+                    dqT = mfma16k16(KT[kt], dsb, dqT);
                     *reinterpret_cast<bf16x4*>(Tp + tw) = pb;
                     *reinterpret_cast<bf16x4*>(Td + tw) = dsb;
                     asm volatile("" ::: "memory");
-                    const bf16x4 Bp = tr4w(Tp + ttoff), Bds = tr4w(Td + ttoff);
-                    dkT[kt] = mfma_k16w(QT, Bds, dkT[kt]);
-                    dvT[kt] = mfma_k16w(DT, Bp, dvT[kt]);
+                    const bf16x4 Bp = tr4(Tp + ttoff), Bds = tr4(Td + ttoff);
+                    dkT[kt] = mfma16k16(QT, Bds, dkT[kt]);
+                    dvT[kt] = mfma16k16(DT, Bp, dvT[kt]);
                 }
                 bf16x4 v;
 #pragma unroll
@@ -721,25 +695,17 @@ __global__ __launch_bounds__(NTHW, 1) void blk256_bwd_kernel(Blk256BwdArgs p) {
 template <int NT, int SPW>
 int launch_blk256_bwd(const Blk256BwdArgs& a, hipStream_t s) {
     using L = LayWB<NT, SPW>;
-    static bool attr_set = false;
-    if (!attr_set) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(blk256_bwd_kernel<NT, SPW>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)L::TOTAL); attr_set = true; }
     constexpr int wgs = 256;                  // persistent, one 16-wave workgroup per CU, at most 256 of them
     const int groups = (a.nsamples + SPW - 1) / SPW;
-    hipLaunchKernelGGL((blk256_bwd_kernel<NT, SPW>), dim3(groups < wgs ? groups : wgs), dim3(NTHW), (size_t)L::TOTAL, s, a);
-    return (int)hipGetLastError();
+    return hs_launch_lds<blk256_bwd_kernel<NT, SPW>>(dim3(groups < wgs ? groups : wgs), dim3(NTHW), L::TOTAL, s, a);
 }
 
 template <int NT, int SPW>
 int launch_blk256(const Blk256Args& a, hipStream_t s) {
     using L = LayW<NT, SPW>;
-    static bool attr_set = false;
-    if (!attr_set) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(blk256_fwd_kernel<NT, SPW>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)L::TOTAL); attr_set = true; }
     constexpr int wgs = 256;                  // persistent, one 16-wave workgroup per CU, at most 256 of them
     const int groups = (a.nsamples + SPW - 1) / SPW;
-    hipLaunchKernelGGL((blk256_fwd_kernel<NT, SPW>), dim3(groups < wgs ? groups : wgs), dim3(NTHW), (size_t)L::TOTAL, s, a);
-    return (int)hipGetLastError();
+    return hs_launch_lds<blk256_fwd_kernel<NT, SPW>>(dim3(groups < wgs ? groups : wgs), dim3(NTHW), L::TOTAL, s, a);
 }
 
 }  // namespace

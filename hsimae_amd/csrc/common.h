@@ -71,6 +71,11 @@ __device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
     // D: col = l&15, row = 4*(l>>4)+r.
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
+typedef __attribute__((ext_vector_type(4))) short s16x4;
+__device__ __forceinline__ f32x4 mfma16k16(bf16x4 a, bf16x4 b, f32x4 c) {
+    // D[16x16] += A[16x16] * B[16x16].  lane l: A[row l&15][k 4(l>>4)+j], B[k 4(l>>4)+j][col l&15]; D as mfma16.
+    return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(s16x4, a), __builtin_bit_cast(s16x4, b), c, 0, 0, 0);
+}
 
 // Workgroup barrier that orders LDS traffic only.  `__syncthreads()` also emits `s_waitcnt vmcnt(0)`, which on
 // gfx950 counts stores as well as loads: every barrier then drains the prefetched weight fragments and the
@@ -84,6 +89,10 @@ __device__ __forceinline__ bf16x8 zero8() {
     u32x4 z = {0u, 0u, 0u, 0u};
     return __builtin_bit_cast(bf16x8, z);
 }
+__device__ __forceinline__ bf16x4 zero4() {
+    u32x2 z = {0u, 0u};
+    return __builtin_bit_cast(bf16x4, z);
+}
 
 __device__ __forceinline__ bf16x8 cvt8(const float* v) {
     bf16x8 r;
@@ -91,8 +100,59 @@ __device__ __forceinline__ bf16x8 cvt8(const float* v) {
     for (int i = 0; i < 8; ++i) r[i] = (bf16_t)v[i];
     return r;
 }
+__device__ __forceinline__ bf16x4 cvt4(f32x4 v) {
+    bf16x4 r;
+    r[0] = (bf16_t)v[0]; r[1] = (bf16_t)v[1]; r[2] = (bf16_t)v[2]; r[3] = (bf16_t)v[3];
+    return r;
+}
+__device__ __forceinline__ bf16x8 pack2(f32x4 a, f32x4 b) {
+    bf16x8 r;
+    r[0] = (bf16_t)a[0]; r[1] = (bf16_t)a[1]; r[2] = (bf16_t)a[2]; r[3] = (bf16_t)a[3];
+    r[4] = (bf16_t)b[0]; r[5] = (bf16_t)b[1]; r[6] = (bf16_t)b[2]; r[7] = (bf16_t)b[3];
+    return r;
+}
 
 __device__ __forceinline__ float bf2f(bf16_t x) { return (float)x; }
+
+// Transpose read (ds_read_b64_tr_b16): 4 consecutive image rows of one column per lane: element j of lane (c16, g) =
+// img[row0(g) + j][col0 + c16]; `a` is the lane's own 8-byte piece img[row0(g) + (c16 >> 2)][col0 + 4 (c16 & 3) ..].
+typedef __attribute__((address_space(3))) bf16x4* lds_b64;
+__device__ __forceinline__ bf16x4 tr4(const bf16_t* a) { return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b64)(a)); }
+
+// 8 floats from / to global memory as two 16-byte accesses
+__device__ __forceinline__ void ld8(const float* p, float* o) {
+    const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
+    o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
+}
+__device__ __forceinline__ void st8(float* p, const float* v) {
+    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+    *reinterpret_cast<float4*>(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
+}
+// The same through a raw buffer (a wave-uniform descriptor + a 32-bit per-lane BYTE offset): the descriptor's extent is the bounds
+// check, so lanes past it read ZEROS and their stores are dropped -- no exec-masked branch around the accesses (with the branches
+// hipcc's wait-count pass fell back to s_waitcnt vmcnt(0) where a counted wait would have left a prefetch in flight) and no 64-bit
+// per-row-group address pairs.  The units build the descriptors (rows_rsrc, panel_rsrc): their extent rules differ.
+__device__ __forceinline__ void bld8(__amdgpu_buffer_rsrc_t r, unsigned bo, float* o) {
+    const f32x4 a = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)bo, 0, 0));
+    const f32x4 b = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)bo + 16, 0, 0));
+    o[0] = a[0]; o[1] = a[1]; o[2] = a[2]; o[3] = a[3]; o[4] = b[0]; o[5] = b[1]; o[6] = b[2]; o[7] = b[3];
+}
+__device__ __forceinline__ void bst8(__amdgpu_buffer_rsrc_t r, unsigned bo, const float* v) {
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f32x4{v[0], v[1], v[2], v[3]}), r, (int)bo, 0, 0);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f32x4{v[4], v[5], v[6], v[7]}), r, (int)bo + 16, 0, 0);
+}
+
+// Data that is invariant across the iterations of a persistent loop (the weight images of the samples a workgroup walks): left
+// alone, the compiler hoists every fragment load out of the loop and then spills them.  Laundering the pointers once per iteration
+// keeps the loads where they are used.
+template <class T>
+__device__ __forceinline__ const T* launder(const T* p) {
+    // launder it as a global-memory pointer: through a generic one every load becomes a flat_load, which ties the
+    // LDS counter (lgkmcnt) to L2 latency
+    const __attribute__((address_space(1))) T* g = (const __attribute__((address_space(1))) T*)p;
+    asm volatile("" : "+s"(g));
+    return (const T*)g;
+}
 
 // a * sigmoid(a) with the reciprocal taken as v_rcp_f32 + one Newton step (<= 1 ulp): the forward kernels' SiLU.
 // A plain v_rcp (1 ulp, biased) moved the loss by 1e-4 at stress weights; IEEE division costs ~10 VALU slots per
@@ -181,6 +241,24 @@ __host__ __device__ inline int64_t wpk_elems(int N, int K) {
 }
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+
+// Host: launch a kernel whose dynamic LDS may exceed the 64 KiB a kernel gets without asking.  The first launch of each kernel
+// instantiation in the process opts it in (errors ignored: the launch reports them); hs_launch_lds also returns the launch's error,
+// hs_enqueue_lds leaves that to a caller that issues several kernels and asks once.
+template <auto Kernel, class Args>
+void hs_enqueue_lds(dim3 grid, dim3 block, size_t lds, hipStream_t s, const Args& a) {
+    static bool opted_in = false;
+    if (!opted_in) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        opted_in = true;
+    }
+    hipLaunchKernelGGL(Kernel, grid, block, lds, s, a);
+}
+template <auto Kernel, class Args>
+int hs_launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t s, const Args& a) {
+    hs_enqueue_lds<Kernel>(grid, block, lds, s, a);
+    return (int)hipGetLastError();
+}
 
 // Streaming stores (write-once tensors that are read much later, by another kernel): `nt` stores do not allocate in
 // L2 / Infinity Cache, which keeps the lines the next kernels re-read resident.  HS_NT(enabled, ptr, value).

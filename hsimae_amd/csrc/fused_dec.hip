@@ -12,35 +12,13 @@
 // LDS staging tile, which is also how x / x1 / x2 move to and from HBM with 16-B accesses.
 #include "common.h"
 #include "kernels.h"
+#include "phase.h"
 #include "plan.h"
 #include <type_traits>
 #include <cstdlib>
 
-// Per-phase cycle accounting for scripts/phase_timing.py (compiled only with -DHS_PHASE_TIMING; never in the shipped library)
-#ifdef HS_PHASE_TIMING
-__device__ unsigned long long hs_phase_cycles[32];
-extern "C" __attribute__((visibility("default"))) int hsimae_debug_phases(unsigned long long* out, int reset) {
-    int rc = (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(hs_phase_cycles), sizeof(unsigned long long) * 32);
-    if (reset) { unsigned long long z[32] = {0}; rc |= (int)hipMemcpyToSymbol(HIP_SYMBOL(hs_phase_cycles), z, sizeof(z)); }
-    return rc;
-}
-#define PH_DECL unsigned long long ph_t0 = __builtin_readcyclecounter(), ph_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define PH(i) { const unsigned long long ph_t = __builtin_readcyclecounter(); ph_acc[i] += ph_t - ph_t0; ph_t0 = ph_t; }
-#define PH_FLUSH(base) if (threadIdx.x == 0) { for (int i = 0; i < 8; ++i) atomicAdd(&hs_phase_cycles[(base) + i], ph_acc[i]); }
-// a second set of stamps inside one phase (round 5: the du + dWqkv phase of dec_bwd_attn), slots 24..31
-#define PH2_DECL unsigned long long ph_t1 = 0, ph_acc2[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define PH2_START ph_t1 = __builtin_readcyclecounter();
-#define PH2(i) { const unsigned long long ph_t = __builtin_readcyclecounter(); ph_acc2[i] += ph_t - ph_t1; ph_t1 = ph_t; }
-#define PH2_FLUSH if (threadIdx.x == 0) { for (int i = 0; i < 8; ++i) atomicAdd(&hs_phase_cycles[24 + i], ph_acc2[i]); }
-#else
-#define PH_DECL
-#define PH(i)
-#define PH_FLUSH(base)
-#define PH2_DECL
-#define PH2_START
-#define PH2(i)
-#define PH2_FLUSH
-#endif
+HS_PHASE_COUNTERS(hs_phase_cycles, hsimae_debug_phases, 32)      // scripts/phase_timing.py
+// (dec_bwd_attn_kernel carries a second set of stamps inside one phase, its du + dWqkv phase since round 5: set 1, slots 24..31)
 
 #ifndef HS_NT_D
 #define HS_NT_D 1      /* x1 / o saved by the decoder forward for the backward as streaming stores (step -0.5 %) */
@@ -341,19 +319,6 @@ __device__ __forceinline__ void store_rows(const float* XS, int R, int Ts, float
     }
 }
 
-__device__ __forceinline__ bf16x4 cvt4(f32x4 v) {
-    bf16x4 r;
-    r[0] = (bf16_t)v[0]; r[1] = (bf16_t)v[1]; r[2] = (bf16_t)v[2]; r[3] = (bf16_t)v[3];
-    return r;
-}
-
-__device__ __forceinline__ bf16x8 pack2(f32x4 a, f32x4 b) {
-    bf16x8 r;
-    r[0] = (bf16_t)a[0]; r[1] = (bf16_t)a[1]; r[2] = (bf16_t)a[2]; r[3] = (bf16_t)a[3];
-    r[4] = (bf16_t)b[0]; r[5] = (bf16_t)b[1]; r[6] = (bf16_t)b[2]; r[7] = (bf16_t)b[3];
-    return r;
-}
-
 __device__ __forceinline__ bf16x8 rowfrag8(const bf16_t* img, int ld, int row, int coloff, int g) {
     // head dim 8: only k-group 0 carries data
     if (g == 0) return *reinterpret_cast<const bf16x8*>(img + row * ld + coloff);
@@ -433,20 +398,10 @@ struct DecW {               // one decoder block's parameters
     int h;
 };
 
-// The weight images are invariant across the samples a workgroup walks; left alone, the compiler hoists every
-// fragment load out of the sample loop and then spills them.  Laundering the pointers once per iteration keeps
-// the loads where they are used.
+// launder() (common.h) for an LDS offset: the same fence against hoisting, for weight images that are resident in LDS
 __device__ __forceinline__ int launder_i(int v) {
     asm volatile("" : "+s"(v));
     return v;
-}
-template <class T>
-__device__ __forceinline__ const T* launder(const T* p) {
-    // launder it as a global-memory pointer: through a generic one every load becomes a flat_load, which ties the
-    // LDS counter (lgkmcnt) to L2 latency
-    const __attribute__((address_space(1))) T* g = (const __attribute__((address_space(1))) T*)p;
-    asm volatile("" : "+s"(g));
-    return (const T*)g;
 }
 // Global addressing of the persistent backward kernels (round 6): a wave-uniform 64-bit base (SGPR pair) + a 32-bit per-lane BYTE
 // offset, which is the `global_load ... v_off, s[base]` form — one VGPR per access instead of a 64-bit VGPR pair per row group —
@@ -464,21 +419,10 @@ template <class T>
 __device__ __forceinline__ T* at_bytes(T* base, unsigned byte_off) {
     return reinterpret_cast<T*>(reinterpret_cast<char*>(base) + byte_off);
 }
-// One sample's rows as a raw buffer: `bytes` = the sample's extent (0 for a sample past the batch), so lanes whose row is past
-// the sequence read ZEROS and their stores are dropped by the bounds check — no exec-masked branch around the accesses (with the
-// branches hipcc's wait-count pass fell back to s_waitcnt vmcnt(0) where a counted wait would have left a prefetch in flight).
+// One sample's rows as a raw buffer for bld8 / bst8 (common.h): `bytes` = the sample's extent (0 for a sample past the batch), so
+// lanes whose row is past the sequence read ZEROS and their stores are dropped by the bounds check.
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t rows_rsrc(const void* base, int bytes) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);
-}
-__device__ __forceinline__ void bld8(__amdgpu_buffer_rsrc_t r, unsigned bo, float* o) {
-    const f32x4 a = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)bo, 0, 0));
-    const f32x4 b = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)bo + 16, 0, 0));
-    o[0] = a[0]; o[1] = a[1]; o[2] = a[2]; o[3] = a[3]; o[4] = b[0]; o[5] = b[1]; o[6] = b[2]; o[7] = b[3];
-}
-__device__ __forceinline__ void bst8(__amdgpu_buffer_rsrc_t r, unsigned bo, const float* v) {
-    typedef __attribute__((ext_vector_type(4))) unsigned int u4;
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, f32x4{v[0], v[1], v[2], v[3]}), r, (int)bo, 0, 0);
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, f32x4{v[4], v[5], v[6], v[7]}), r, (int)bo + 16, 0, 0);
 }
 __device__ __forceinline__ DecW launder_w(const DecW& a) {
     DecW w = a;
@@ -553,7 +497,7 @@ __global__ __launch_bounds__(256, 2) void dec_block_fwd_kernel(DecFwdArgs p) {
     const Geo4 q = geo();
     const int mt0 = q.wm * L::MHF;
 
-    PH_DECL
+    PH_DECL(8)
     for (int sample = blockIdx.x; sample < p.nsamples; sample += gridDim.x) {
         const size_t rb = (size_t)sample * p.Ts;
         const DecW w = launder_w(p.w);
@@ -662,17 +606,7 @@ __global__ __launch_bounds__(256, 2) void dec_block_fwd_kernel(DecFwdArgs p) {
         lds_barrier();
         PH(7)
     }
-    PH_FLUSH(16)
-}
-
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-__device__ __forceinline__ f32x4 mfma16k16(bf16x4 a, bf16x4 b, f32x4 c) {
-    // D[16x16] += A[16x16] * B[16x16].  lane l: A[row l&15][k 4(l>>4)+j], B[k 4(l>>4)+j][col l&15]; D as mfma16.
-    return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(s16x4, a), __builtin_bit_cast(s16x4, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ bf16x4 zero4() {
-    u32x2 z = {0u, 0u};
-    return __builtin_bit_cast(bf16x4, z);
+    PH_FLUSH(hs_phase_cycles, 16, 8, 0)
 }
 
 // ====================================================================== forward, second generation: attention half
@@ -838,8 +772,6 @@ __global__ __launch_bounds__(256, 4) void dec_attn_fwd_kernel(DecAttnFwdArgs p) 
 //   dec_bwd_mlp_kernel : reads x1, dY          -> dx1 = dY + LN2/SwiGLU branch grads ; dW1 dW3 dW2 db* dLN2
 //   dec_bwd_attn_kernel: reads x, dx1          -> dx  = dx1 + LN1/attention branch grads ; dWq dWk dWv dWp db* dLN1
 // Everything else (u, q, k, v, P, o, h1, h3, g) is recomputed from x / x1 inside the tile.
-typedef __attribute__((address_space(3))) bf16x4* lds_b64;
-
 // ---------------------------------------------------------------------- backward: LDS layouts (round 4)
 // Bank model: MI355X_MICROARCH.md "LDS" / scripts/micro/lds_banks.py; the audit of every access pattern of the two backward
 // kernels under the round-3 layout (pitch D + 8) and this one is scripts/micro/lds_audit_dec.py.  Round 3 measured 2.5 / 2.2
@@ -898,14 +830,7 @@ __device__ __forceinline__ bf16x8 rowfrag(const bf16_t* img, int mt, int ks, con
 __device__ __forceinline__ int tile_off(int mt, int nt, const GeoB& q) {
     return (mt * 16 + q.c16) * IR + (((2 * nt + (q.g >> 1)) ^ q.fr) << 3) + (q.g & 1) * 4;
 }
-typedef __attribute__((address_space(3))) bf16x4* lds_w64;
-__device__ __forceinline__ void st4(bf16_t* p, bf16x4 v) { *(lds_w64)(p) = v; }      // LDS address space + 8-byte type: ds_write_b64
-
-// 4 consecutive image rows of one column per lane: element j of lane (c16, g) = img[row0(g) + j][col0 + c16];
-// `a` is the lane's own 8-byte piece img[row0(g) + (c16 >> 2)][col0 + 4 (c16 & 3) ..].
-__device__ __forceinline__ bf16x4 tr4(const bf16_t* a) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b64)(a));
-}
+__device__ __forceinline__ void st4(bf16_t* p, bf16x4 v) { *(lds_b64)(p) = v; }      // LDS address space + 8-byte type: ds_write_b64
 
 // Row (token) fragment pair for one k-step of a weight-gradient product  dO[:, n0..]^T * A[:, k0..]  (contraction over
 // the image rows, 32 per MFMA) from an activation image: element j of lane group g = img[kk*32 + 4g + (j & 3) + 16 (j >> 2)][nt*16 + c16].
@@ -961,19 +886,6 @@ __device__ __forceinline__ void mm_cols(const bf16_t* A, const bf16_t* Wr, int m
             for (int j = 0; j < 2; ++j) acc[mi][j] = mfma16(b[j], a, acc[mi][j]);
         }
     }
-}
-
-__device__ __forceinline__ void ld8(const float* p, float* o) {
-    const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
-    o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
-}
-__device__ __forceinline__ void st8(float* p, const float* v) {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    *reinterpret_cast<float4*>(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
-}
-__device__ __forceinline__ float red8(float v) {
-    v = lanes_sum<8>(v);
-    return v;
 }
 
 // Commit per-thread column partials (wide layout: thread owns columns 8*(tid&7)..+7) with one atomic per column.
@@ -1065,7 +977,7 @@ __global__ __launch_bounds__(512, 2) void dec_bwd_mlp_kernel(DecBwdMlpArgs p) {
     for (int e = 0; e < 8; ++e) ones[e] = (bf16_t)1.0f;
     const bool bias_wave = (q.wave & 1) == 0;
 
-    PH_DECL
+    PH_DECL(8)
     // Round-5 experiment (HS_DEC_MLP_PREFETCH=1, not the default): the sample's x1 / dY rows fetched one sample AHEAD, behind the
     // epilogue's own re-reads in the in-order memory counter, as dec_bwd_attn_kernel has done since round 4.  The phase stamps
     // (profiles/r05_c_phase_timing.txt) have this kernel's prologue — 8 loads per thread at the top of the iteration, then
@@ -1114,11 +1026,11 @@ __global__ __launch_bounds__(512, 2) void dec_bwd_mlp_kernel(DecBwdMlpArgs p) {
                 float (&f)[8] = fa[i];
                 float (&dyv)[8] = dya[i];
                 ld8(n2w + c8, gm); ld8(n2b + c8, bt);
-                const float mean = red8(f[0] + f[1] + f[2] + f[3] + f[4] + f[5] + f[6] + f[7]) * (1.f / D);
+                const float mean = lanes_sum<8>(f[0] + f[1] + f[2] + f[3] + f[4] + f[5] + f[6] + f[7]) * (1.f / D);
                 float v = 0.f;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) { f[e] -= mean; v += f[e] * f[e]; }
-                const float rstd = rsqrtf(red8(v) * (1.f / D) + 1e-5f);
+                const float rstd = rsqrtf(lanes_sum<8>(v) * (1.f / D) + 1e-5f);
                 float u[8];
 #pragma unroll
                 for (int e = 0; e < 8; ++e) u[e] = f[e] * rstd * gm[e] + bt[e];
@@ -1287,15 +1199,15 @@ __global__ __launch_bounds__(512, 2) void dec_bwd_mlp_kernel(DecBwdMlpArgs p) {
                 float (&dyv)[8] = dye[i];
                 ld8(XS + row * LX + c8, du);
                 ld8(n2w + c8, gm);
-                const float mean = red8(xh[0] + xh[1] + xh[2] + xh[3] + xh[4] + xh[5] + xh[6] + xh[7]) * (1.f / D);
+                const float mean = lanes_sum<8>(xh[0] + xh[1] + xh[2] + xh[3] + xh[4] + xh[5] + xh[6] + xh[7]) * (1.f / D);
                 float v = 0.f;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) { xh[e] -= mean; v += xh[e] * xh[e]; }
-                const float rstd = rsqrtf(red8(v) * (1.f / D) + 1e-5f);
+                const float rstd = rsqrtf(lanes_sum<8>(v) * (1.f / D) + 1e-5f);
                 float a = 0.f, b = 0.f;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) { xh[e] *= rstd; t[e] = du[e] * gm[e]; a += t[e]; b += t[e] * xh[e]; }
-                a = red8(a) * (1.f / D); b = red8(b) * (1.f / D);
+                a = lanes_sum<8>(a) * (1.f / D); b = lanes_sum<8>(b) * (1.f / D);
                 float o[8];
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
@@ -1310,7 +1222,7 @@ __global__ __launch_bounds__(512, 2) void dec_bwd_mlp_kernel(DecBwdMlpArgs p) {
         PH(4)
     }
 
-    PH_FLUSH(8)
+    PH_FLUSH(hs_phase_cycles, 8, 8, 0)
     // ---- commit
     float* red = XS;
     float* vec = p.slab ? p.slab + kSlabTileFloats + (size_t)blockIdx.x * kVec : nullptr;
@@ -1631,8 +1543,8 @@ __global__ __launch_bounds__(512, 2) void dec_bwd_attn_kernel(DecBwdAttnArgs p) 
     //  either way into the loop head — otherwise the merged state makes the loop's first use of a prefetched row an s_waitcnt vmcnt(0),
     //  which on the back edge drains the previous sample's dx stores: attn.hip HS_BB_EARLY_WAIT)
     if (HS_DEC_PRELOOP_WAIT) __builtin_amdgcn_s_waitcnt(0x0F70);
-    PH_DECL
-    PH2_DECL
+    PH_DECL(8)
+    PHS_DECL(1, 8)
     for (int sample = blockIdx.x; sample < p.nsamples; sample += gridDim.x) {
         const size_t rb = (size_t)sample * p.Ts;
         const int wl = launder_i(0);                  // keeps the LDS weight reads inside the sample loop
@@ -1654,11 +1566,11 @@ __global__ __launch_bounds__(512, 2) void dec_bwd_attn_kernel(DecBwdAttnArgs p) 
                 const bf16x8 ov = ova[i];
                 ld8(CBl + 3 * D + c8, gm); ld8(CBl + 4 * D + c8, bt);
                 *reinterpret_cast<bf16x8*>(Ob + row * IR + wide) = ov;
-                const float mean = red8(f[0] + f[1] + f[2] + f[3] + f[4] + f[5] + f[6] + f[7]) * (1.f / D);
+                const float mean = lanes_sum<8>(f[0] + f[1] + f[2] + f[3] + f[4] + f[5] + f[6] + f[7]) * (1.f / D);
                 float v = 0.f;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) { f[e] -= mean; v += f[e] * f[e]; }
-                const float rstd = rsqrtf(red8(v) * (1.f / D) + 1e-5f);
+                const float rstd = rsqrtf(lanes_sum<8>(v) * (1.f / D) + 1e-5f);
                 float u[8];
 #pragma unroll
                 for (int e = 0; e < 8; ++e) u[e] = f[e] * rstd * gm[e] + bt[e];
@@ -1780,14 +1692,14 @@ __global__ __launch_bounds__(512, 2) void dec_bwd_attn_kernel(DecBwdAttnArgs p) 
         attn_head_bwd<MT>(Qb, Kb, Vb, Ob, lse + q.wave * R, dlt + q.wave * R, TT + q.wave * TT_WAVE, q.wave, p.Ts, q);
         lds_barrier();
         PH(5)
-        PH2_START
+        PHS_START(1)
         __builtin_amdgcn_sched_barrier(0);
         // (issuing this burst is 55 % of this phase, profiles/r05_f_phase_timing.txt: the waves sit at the issue while every CU of
         //  the chip asks for its sample at once.  Issued in three parts between the products below instead: 323.4 -> 318.3 us alone,
         //  nothing on top of the start stagger (309.0 vs 310.0 us, profiles/r05_i_stagger_sweep2.txt): one burst kept.)
         fetch_sample(sample + (int)gridDim.x);          // ~4 us (du + dWqkv + epilogue) ahead of its use
         __builtin_amdgcn_sched_barrier(0);
-        PH2(0)
+        PHS(1, 0)
         regeo_core();
         // du = dq Wq + dk Wk + dv Wv ; dWq|dWk|dWv += d{q,k,v}^T u
         f32x4 du[L::MH][2];
@@ -1797,7 +1709,7 @@ __global__ __launch_bounds__(512, 2) void dec_bwd_attn_kernel(DecBwdAttnArgs p) 
         mm_cols<L::MH>(Qb, WQl, mt0, q, du);
         mm_cols<L::MH>(Kb, WQl + D * LW, mt0, q, du);
         mm_cols<L::MH>(Vb, WQl + 2 * D * LW, mt0, q, du);
-        PH2(1)
+        PHS(1, 1)
         regeo();
         f32x4 accqb[3];
 #pragma unroll
@@ -1833,7 +1745,7 @@ __global__ __launch_bounds__(512, 2) void dec_bwd_attn_kernel(DecBwdAttnArgs p) 
         }
 #pragma unroll
         for (int t = 0; t < 3; ++t) dbqw[t] += r4 == 0 ? accqb[t][0] : (r4 == 1 ? accqb[t][1] : (r4 == 2 ? accqb[t][2] : accqb[t][3]));
-        PH2(2)
+        PHS(1, 2)
         regeo(); rewide();
         acc_to_xs<L::MH, true>(XS, mt0, MT, q, du);
         float xe[NPW][8], d1e[NPW][8];                // L2-hot re-reads for the LayerNorm backward, in flight over the barrier
@@ -1849,12 +1761,12 @@ __global__ __launch_bounds__(512, 2) void dec_bwd_attn_kernel(DecBwdAttnArgs p) 
             }
 #endif
         }
-        PH2(3)
+        PHS(1, 3)
         lds_barrier();
         // (both row groups' re-reads — and the next sample's rows, issued a phase ago — waited for once, before the first dx store:
         //  a wait for the second group's rows behind the first group's stores would be an s_waitcnt vmcnt(0) that drains them)
         if (HS_DEC_PRELOOP_WAIT) __builtin_amdgcn_s_waitcnt(0x0F70);
-        PH2(4)
+        PHS(1, 4)
         PH(6)
 #pragma unroll
         for (int i = 0; i < NPW; ++i) {
@@ -1866,15 +1778,15 @@ __global__ __launch_bounds__(512, 2) void dec_bwd_attn_kernel(DecBwdAttnArgs p) 
                 float (&d1)[8] = d1e[i];
                 ld8(XS + row * LX + c8, dv);
                 ld8(CBl + 3 * D + c8, gm);
-                const float mean = red8(xh[0] + xh[1] + xh[2] + xh[3] + xh[4] + xh[5] + xh[6] + xh[7]) * (1.f / D);
+                const float mean = lanes_sum<8>(xh[0] + xh[1] + xh[2] + xh[3] + xh[4] + xh[5] + xh[6] + xh[7]) * (1.f / D);
                 float v = 0.f;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) { xh[e] -= mean; v += xh[e] * xh[e]; }
-                const float rstd = rsqrtf(red8(v) * (1.f / D) + 1e-5f);
+                const float rstd = rsqrtf(lanes_sum<8>(v) * (1.f / D) + 1e-5f);
                 float a = 0.f, b = 0.f;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) { xh[e] *= rstd; t[e] = dv[e] * gm[e]; a += t[e]; b += t[e] * xh[e]; }
-                a = red8(a) * (1.f / D); b = red8(b) * (1.f / D);
+                a = lanes_sum<8>(a) * (1.f / D); b = lanes_sum<8>(b) * (1.f / D);
                 float o[8];
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
@@ -1889,8 +1801,8 @@ __global__ __launch_bounds__(512, 2) void dec_bwd_attn_kernel(DecBwdAttnArgs p) 
         PH(7)
     }
 
-    PH_FLUSH(0)
-    PH2_FLUSH
+    PH_FLUSH(hs_phase_cycles, 0, 8, 0)
+    PHS_FLUSH(1, hs_phase_cycles, 24, 8, 0)
     // ---- commit
     float* red = XS;
     float* vec = p.slab ? p.slab + kSlabTileFloats + (size_t)blockIdx.x * kVec : nullptr;
@@ -2023,27 +1935,14 @@ __global__ __launch_bounds__(NT_) void dec_dw_reduce_kernel(DecDwReduceArgs p) {
 template <int MT>
 int launch_fwd(const DecFwdArgs& a, hipStream_t s) {
     using L = DL<MT>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dec_block_fwd_kernel<MT>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, L::FWD_TOTAL);
-        attr_set = true;
-    }
     constexpr int wgs = 512;                  // workgroups: 2 per CU walking the samples
-    hipLaunchKernelGGL((dec_block_fwd_kernel<MT>), dim3(a.nsamples < wgs ? a.nsamples : wgs), dim3(256), L::FWD_TOTAL, s, a);
-    return (int)hipGetLastError();
+    return hs_launch_lds<dec_block_fwd_kernel<MT>>(dim3(a.nsamples < wgs ? a.nsamples : wgs), dim3(256), L::FWD_TOTAL, s, a);
 }
 
 template <int MT>
 int launch_attn_fwd(const DecAttnFwdArgs& a, hipStream_t s) {
     constexpr int LDS = 2 * MT * 16 * LU * 2;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dec_attn_fwd_kernel<MT>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((dec_attn_fwd_kernel<MT>), dim3(a.nsamples), dim3(256), LDS, s, a);
-    return (int)hipGetLastError();
+    return hs_launch_lds<dec_attn_fwd_kernel<MT>>(dim3(a.nsamples), dim3(256), LDS, s, a);
 }
 
 }  // namespace
@@ -2056,17 +1955,9 @@ int launch_bwd(const DecBwdMlpArgs& a, const DecBwdAttnArgs& b, hipStream_t s) {
     static_assert(3 * IMG >= L::R * LX * 4, "fp32 staging tile must fit over Gc|DH1|DH3");
     static_assert(LDS_A - 5 * IMG >= 16 * IR * 2, "image overrun of the unguarded du2 product must stay inside the allocation");
     constexpr int LDS_B = L::BWD_ATTN_LDS;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dec_bwd_mlp_kernel<MT>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, LDS_A);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dec_bwd_attn_kernel<MT>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B);
-        attr_set = true;
-    }
     const int grid = a.nsamples < 256 ? a.nsamples : 256;      // persistent: one workgroup per CU
-    hipLaunchKernelGGL((dec_bwd_mlp_kernel<MT>), dim3(grid), dim3(NT_), LDS_A, s, a);
-    hipLaunchKernelGGL((dec_bwd_attn_kernel<MT>), dim3(grid), dim3(NT_), LDS_B, s, b);
+    hs_enqueue_lds<dec_bwd_mlp_kernel<MT>>(dim3(grid), dim3(NT_), LDS_A, s, a);
+    hs_enqueue_lds<dec_bwd_attn_kernel<MT>>(dim3(grid), dim3(NT_), LDS_B, s, b);
     if (a.slab) {
         DecDwReduceArgs r;
         r.slab = a.slab; r.nwg = grid; r.h = a.w.h;

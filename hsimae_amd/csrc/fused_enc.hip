@@ -9,25 +9,11 @@
 // 64-column chunk.  Weight fragments are prefetched one chunk ahead.
 #include "common.h"
 #include "kernels.h"
+#include "phase.h"
 #include "plan.h"
 #include <cstdlib>
 
-// Per-phase cycle accounting for scripts/phase_timing.py (compiled only with -DHS_PHASE_TIMING; never in the shipped library)
-#ifdef HS_PHASE_TIMING
-__device__ unsigned long long hs_phase_cycles_enc[32];
-extern "C" __attribute__((visibility("default"))) int hsimae_debug_phases_enc(unsigned long long* out, int reset) {
-    int rc = (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(hs_phase_cycles_enc), sizeof(unsigned long long) * 32);
-    if (reset) { unsigned long long z[32] = {0}; rc |= (int)hipMemcpyToSymbol(HIP_SYMBOL(hs_phase_cycles_enc), z, sizeof(z)); }
-    return rc;
-}
-#define PH_DECL unsigned long long ph_t0 = __builtin_readcyclecounter(), ph_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define PH(i) { const unsigned long long ph_t = __builtin_readcyclecounter(); ph_acc[i] += ph_t - ph_t0; ph_t0 = ph_t; }
-#define PH_FLUSH(base) if (threadIdx.x == 0) { for (int i = 0; i < 8; ++i) atomicAdd(&hs_phase_cycles_enc[(base) + i], ph_acc[i]); }
-#else
-#define PH_DECL
-#define PH(i)
-#define PH_FLUSH(base)
-#endif
+HS_PHASE_COUNTERS(hs_phase_cycles_enc, hsimae_debug_phases_enc, 32)      // scripts/phase_timing.py
 
 #ifndef HS_NT_A
 #define HS_NT_A 1      /* dh1|dh3 / g of enc_mlp_bwd as streaming stores: step -1.3 % */
@@ -194,29 +180,6 @@ struct FrN {
     }
 };
 
-__device__ __forceinline__ bf16x4 cvt4(f32x4 v) {
-    bf16x4 r;
-    r[0] = (bf16_t)v[0]; r[1] = (bf16_t)v[1]; r[2] = (bf16_t)v[2]; r[3] = (bf16_t)v[3];
-    return r;
-}
-
-template <class T>
-__device__ __forceinline__ const T* launder(const T* p) { asm volatile("" : "+s"(p)); return p; }
-
-__device__ __forceinline__ void ld8(const float* p, float* o) {
-    const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
-    o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
-}
-__device__ __forceinline__ void st8(float* p, const float* v) {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    *reinterpret_cast<float4*>(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
-}
-template <int LPR>
-__device__ __forceinline__ float redrow(float v) {          // sum over the LPR adjacent lanes that own one row
-    v = lanes_sum<LPR>(v);
-    return v;
-}
-
 // b1 | b3 of the 4 hidden columns a lane owns in the swapped-operand products (zero past the hidden width: the padded W1 / W3
 // rows are zero too).  Fetched one chunk ahead with the weight fragments: loaded where they are used, every chunk began with an
 // exposed L2 round trip (s_waitcnt vmcnt(0) in front of the first MFMA).
@@ -283,7 +246,7 @@ __global__ __launch_bounds__(NTH, (MG<D, HPE>::WPCF)) void enc_mlp_fwd_kernel(En
     };
     fetch_panel(blockIdx.x);
 
-    PH_DECL
+    PH_DECL(8)
   int panel = blockIdx.x;
   do {
     const int row0 = panel * R;
@@ -311,11 +274,12 @@ __global__ __launch_bounds__(NTH, (MG<D, HPE>::WPCF)) void enc_mlp_fwd_kernel(En
 #pragma unroll
             for (int e = 0; e < 8; ++e) f[e] = fa[i][e];
             if constexpr (G::KEEP_XR) st8(XR + row * LX + c8, f);
-            const float mean = redrow<LPR>(f[0] + f[1] + f[2] + f[3] + f[4] + f[5] + f[6] + f[7]) * (1.f / D);
+            // (lanes_sum<LPR>: the sum over the LPR adjacent lanes that own one row)
+            const float mean = lanes_sum<LPR>(f[0] + f[1] + f[2] + f[3] + f[4] + f[5] + f[6] + f[7]) * (1.f / D);
             float v = 0.f;
 #pragma unroll
             for (int e = 0; e < 8; ++e) { f[e] -= mean; v += f[e] * f[e]; }
-            const float rstd = rsqrtf(redrow<LPR>(v) * (1.f / D) + 1e-5f);
+            const float rstd = rsqrtf(lanes_sum<LPR>(v) * (1.f / D) + 1e-5f);
 #pragma unroll
             for (int e = 0; e < 8; ++e) f[e] = f[e] * rstd * gm[e] + bt[e];
             *reinterpret_cast<bf16x8*>(U2 + row * LU + (((c8 >> 3) ^ swzp<D>(row)) << 3)) = cvt8(f);
@@ -433,7 +397,7 @@ __global__ __launch_bounds__(NTH, (MG<D, HPE>::WPCF)) void enc_mlp_fwd_kernel(En
     PH(4)
     if constexpr (PERSIST) lds_barrier();               // XS / XR are read: the next panel's LayerNorm may overwrite them
   } while (PERSIST && (panel += (int)gridDim.x) < npanels);
-    PH_FLUSH(8)
+    PH_FLUSH(hs_phase_cycles_enc, 8, 8, 0)
 }
 
 // (Round 5 built a weights-resident persistent form of the D = 128 forward kernel — ONE 8-wave workgroup per CU holding all of
@@ -465,19 +429,9 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t panel_rsrc(const void* base, l
     const long long b = rows > 0 ? (rows < 4096 ? rows : 4096) * row_bytes : 0;      // (a panel is <= 64 rows: the extent never nears 2^31)
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)b, 0x00020000);
 }
-__device__ __forceinline__ void bld8(__amdgpu_buffer_rsrc_t r, unsigned bo, float* o) {
-    const f32x4 a = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)bo, 0, 0));
-    const f32x4 b = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)bo + 16, 0, 0));
-    o[0] = a[0]; o[1] = a[1]; o[2] = a[2]; o[3] = a[3]; o[4] = b[0]; o[5] = b[1]; o[6] = b[2]; o[7] = b[3];
-}
-typedef __attribute__((ext_vector_type(4))) unsigned int u32q;
-__device__ __forceinline__ void bst8f(__amdgpu_buffer_rsrc_t r, unsigned bo, const float* v) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32q, f32x4{v[0], v[1], v[2], v[3]}), r, (int)bo, 0, 0);
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32q, f32x4{v[4], v[5], v[6], v[7]}), r, (int)bo + 16, 0, 0);
-}
 __device__ __forceinline__ void bst8h(__amdgpu_buffer_rsrc_t r, unsigned bo, bf16x8 v, int aux) {
-    if (aux) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32q, v), r, (int)bo, 0, 2);
-    else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32q, v), r, (int)bo, 0, 0);
+    if (aux) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, (int)bo, 0, 2);
+    else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, (int)bo, 0, 0);
 }
 
 template <int D, int HPE, bool LATE_ST = false>
@@ -499,7 +453,7 @@ __global__ __launch_bounds__(NTH, (MG<D, HPE>::WPC)) void enc_mlp_bwd_kernel(Enc
     const int c8 = (threadIdx.x % LPR) * 8;
     constexpr bool late_stores = LATE_ST;
 
-    PH_DECL
+    PH_DECL(8)
     // column-split decomposition (see FrN): wave w owns n-tile w of every 64-column hidden chunk and the output
     // n-tiles {2w, 2w+1} of the data gradient, each for all 4 m-tiles of the panel
     constexpr int MT4 = R / 16, NJO = D / 64;
@@ -531,11 +485,11 @@ __global__ __launch_bounds__(NTH, (MG<D, HPE>::WPC)) void enc_mlp_bwd_kernel(Enc
             const bool ok = row0 + row < p.M;
             float (&f)[8] = fa[i];
             float (&dyv)[8] = dya[i];
-            const float mean = redrow<LPR>(f[0] + f[1] + f[2] + f[3] + f[4] + f[5] + f[6] + f[7]) * (1.f / D);
+            const float mean = lanes_sum<LPR>(f[0] + f[1] + f[2] + f[3] + f[4] + f[5] + f[6] + f[7]) * (1.f / D);
             float v = 0.f;
 #pragma unroll
             for (int e = 0; e < 8; ++e) { f[e] -= mean; v += f[e] * f[e]; }
-            const float rstd = rsqrtf(redrow<LPR>(v) * (1.f / D) + 1e-5f);
+            const float rstd = rsqrtf(lanes_sum<LPR>(v) * (1.f / D) + 1e-5f);
 #pragma unroll
             for (int e = 0; e < 8; ++e) f[e] = f[e] * rstd * gm[e] + bt[e];
             const bf16x8 ub = cvt8(f);
@@ -704,7 +658,6 @@ __global__ __launch_bounds__(NTH, (MG<D, HPE>::WPC)) void enc_mlp_bwd_kernel(Enc
             const unsigned plane = (unsigned)p.plane_rows * 64u * 2u;          // bytes per 64-column plane
             const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc(p.g, 0, (int)(NCH * plane), 0x00020000);
             const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(p.dh13, 0, (int)(2 * NCH * plane), 0x00020000);
-            typedef __attribute__((ext_vector_type(4))) unsigned int u4;
             int tid = threadIdx.x;
             asm volatile("" : "+v"(tid));              // opaque: the lane offsets below are derived here, per chunk, not hoisted and kept (spilled) across the kernel
 #pragma unroll
@@ -714,9 +667,9 @@ __global__ __launch_bounds__(NTH, (MG<D, HPE>::WPC)) void enc_mlp_bwd_kernel(Enc
                 const int lrow = ok ? row : 0;
                 const int lo = lrow * LC + (((k8 >> 3) ^ swzc<D>(lrow)) << 3);
                 const unsigned po = ok ? (unsigned)c * plane + ((unsigned)(row0 + row) * 64u + (unsigned)k8) * 2u : 0xffffff00u;    // past the extent: dropped
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, *reinterpret_cast<const bf16x8*>(Gc + lo)), rg, (int)po, 0, HS_NT_A ? 2 : 0);
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, *reinterpret_cast<const bf16x8*>(DH1 + lo)), rd, (int)po, 0, HS_NT_A ? 2 : 0);
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, *reinterpret_cast<const bf16x8*>(DH3 + lo)), rd, (int)(ok ? po + NCH * plane : po), 0, HS_NT_A ? 2 : 0);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, *reinterpret_cast<const bf16x8*>(Gc + lo)), rg, (int)po, 0, HS_NT_A ? 2 : 0);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, *reinterpret_cast<const bf16x8*>(DH1 + lo)), rd, (int)po, 0, HS_NT_A ? 2 : 0);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, *reinterpret_cast<const bf16x8*>(DH3 + lo)), rd, (int)(ok ? po + NCH * plane : po), 0, HS_NT_A ? 2 : 0);
             }
         }
         lds_barrier();
@@ -753,15 +706,15 @@ __global__ __launch_bounds__(NTH, (MG<D, HPE>::WPC)) void enc_mlp_bwd_kernel(Enc
             float (&xh)[8] = xa[i];
             float (&dyv)[8] = dya[i];
             ld8(XS + row * LX + c8, du);
-            const float mean = redrow<LPR>(xh[0] + xh[1] + xh[2] + xh[3] + xh[4] + xh[5] + xh[6] + xh[7]) * (1.f / D);
+            const float mean = lanes_sum<LPR>(xh[0] + xh[1] + xh[2] + xh[3] + xh[4] + xh[5] + xh[6] + xh[7]) * (1.f / D);
             float v = 0.f;
 #pragma unroll
             for (int e = 0; e < 8; ++e) { xh[e] -= mean; v += xh[e] * xh[e]; }
-            const float rstd = rsqrtf(redrow<LPR>(v) * (1.f / D) + 1e-5f);
+            const float rstd = rsqrtf(lanes_sum<LPR>(v) * (1.f / D) + 1e-5f);
             float a = 0.f, b = 0.f;
 #pragma unroll
             for (int e = 0; e < 8; ++e) { xh[e] *= rstd; t[e] = du[e] * gm[e]; a += t[e]; b += t[e] * xh[e]; }
-            a = redrow<LPR>(a) * (1.f / D); b = redrow<LPR>(b) * (1.f / D);
+            a = lanes_sum<LPR>(a) * (1.f / D); b = lanes_sum<LPR>(b) * (1.f / D);
             if (ok) {
                 float o[8];
 #pragma unroll
@@ -770,7 +723,7 @@ __global__ __launch_bounds__(NTH, (MG<D, HPE>::WPC)) void enc_mlp_bwd_kernel(Enc
                     dgam[e] += du[e] * xh[e];
                     dbet[e] += du[e];
                 }
-                bst8f(dxr, (unsigned)(row * D + c8) * 4u, o);
+                bst8(dxr, (unsigned)(row * D + c8) * 4u, o);
                 if (p.rs_attn) {
                     const float rs = p.rs_attn[row0 + row];
 #pragma unroll
@@ -794,7 +747,7 @@ __global__ __launch_bounds__(NTH, (MG<D, HPE>::WPC)) void enc_mlp_bwd_kernel(Enc
         hs_gadd(p.det, (which ? p.g_n2b : p.g_n2w) + c, s);
     }
     PH(5)
-    PH_FLUSH(0)
+    PH_FLUSH(hs_phase_cycles_enc, 0, 8, 0)
 }
 
 }  // namespace
@@ -809,6 +762,7 @@ static EncMlpW mkw(const BlockW& b) {
     return w;
 }
 
+// (deliberately not hs_launch_lds, common.h: one flag opts in the three kernels of a <D, HP> together, forward and backward)
 template <int D, int HP>
 static void set_attrs() {
     static_assert(hsplan::mlp_shape(D, HP), "plan.h mlp_fusable must select every <D, HP> launched here");

@@ -14,27 +14,13 @@
 // access; the first version's per-element 2-byte stores made every GEMM store-issue bound (profiles/).
 #include "common.h"
 #include "kernels.h"
+#include "phase.h"
 #include "plan.h"
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
 
-// Per-phase cycle accounting for scripts/phase_timing.py (compiled only with -DHS_PHASE_TIMING; never in the shipped library)
-#ifdef HS_PHASE_TIMING
-__device__ unsigned long long hs_phase_cycles_gemm[64];
-extern "C" __attribute__((visibility("default"))) int hsimae_debug_phases_gemm(unsigned long long* out, int reset) {
-    int rc = (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(hs_phase_cycles_gemm), sizeof(unsigned long long) * 64);
-    if (reset) { unsigned long long z[64] = {0}; rc |= (int)hipMemcpyToSymbol(HIP_SYMBOL(hs_phase_cycles_gemm), z, sizeof(z)); }
-    return rc;
-}
-#define PH_DECL unsigned long long ph_t0 = __builtin_readcyclecounter(), ph_acc[4] = {0, 0, 0, 0};
-#define PH(i) { const unsigned long long ph_t = __builtin_readcyclecounter(); ph_acc[i] += ph_t - ph_t0; ph_t0 = ph_t; }
-#define PH_FLUSH(base) if (threadIdx.x == 0) { for (int i = 0; i < 4; ++i) atomicAdd(&hs_phase_cycles_gemm[(base) + i], ph_acc[i]); }
-#else
-#define PH_DECL
-#define PH(i)
-#define PH_FLUSH(base)
-#endif
+HS_PHASE_COUNTERS(hs_phase_cycles_gemm, hsimae_debug_phases_gemm, 64)      // scripts/phase_timing.py
 
 namespace {
 
@@ -323,7 +309,7 @@ __global__ __launch_bounds__(256, (EPI == E_LN_BWD || BM <= 64) ? 2 : 1) void ge
     };
     Grp cur;
     fetch(0, 0, 0, cur);
-    PH_DECL
+    PH_DECL(4)
 
     // one group of G k-steps of the current A chunk against the weight fragments in `cur`
     auto mma = [&](f32x4 (&acc)[MT][2], f32x4 (&acc2)[DUAL ? MT : 1][2], const Grp& cur, int gb, int nks, const unsigned (&sa)[F8 ? MT : 1]) {
@@ -785,7 +771,7 @@ __global__ __launch_bounds__(256, (EPI == E_LN_BWD || BM <= 64) ? 2 : 1) void ge
                 if (c < n_chunks) epilogue(c, accs[c], acc2);
         }
     }
-    PH_FLUSH(((AK * 3 + (EPI == E_LN_BWD ? 2 : (EPI == E_BF16 ? 0 : 1))) * 4) % 64)
+    PH_FLUSH(hs_phase_cycles_gemm, ((AK * 3 + (EPI == E_LN_BWD ? 2 : (EPI == E_BF16 ? 0 : 1))) * 4) % 64, 4, 0)
 }
 
 template <int AK, int EPI, int KC, int BM, int F8 = 0, int NCH = 1>
@@ -795,14 +781,7 @@ int launch(const GemmParams& p, hipStream_t s) {
     size_t tiles = (EPI == E_SWIGLU ? 2 : 1) * EpiRows<KC, F8, BM>::v * TS * sizeof(float);
     if (EPI == E_LN_BWD && NCH > 1) tiles = std::max(tiles, (size_t)NCH * 16 * TS * sizeof(float));
     const size_t lds = abytes + BM * 2 * sizeof(float) + tiles;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_kernel<AK, EPI, KC, BM, F8, NCH>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((gemm_kernel<AK, EPI, KC, BM, F8, NCH>), dim3(grid), dim3(256), lds, s, p);
-    return (int)hipGetLastError();
+    return hs_launch_lds<gemm_kernel<AK, EPI, KC, BM, F8, NCH>>(dim3(grid), dim3(256), lds, s, p);
 }
 
 // Which instantiation a call launches is decided in plan.h: plan_gemm() picks (KC, BM, F8, NCH) from the A kind, the epilogue, the

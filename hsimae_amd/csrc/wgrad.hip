@@ -22,14 +22,11 @@ namespace {
 constexpr int MC = 64;            // rows per chunk (2 k-steps)
 constexpr int TST = 128 + 8;      // LDS tile row stride (elements)
 
-typedef __attribute__((address_space(3))) bf16x4* lds_b64_ptr;
-
 __device__ __forceinline__ bf16x8 frag_tr_rows(const bf16_t* tile, int mbase, int col0, int lane) {
     // 16x32 MFMA operand whose k index runs over tile ROWS: element j of lane l = tile[mbase + 8*(l>>4) + j][col0 + (l&15)]
     const int g = lane >> 4, q = (lane & 15) >> 2, pq = lane & 3;
     const bf16_t* a0 = tile + (mbase + 8 * g + q) * TST + col0 + 4 * pq;
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b64_ptr)(a0));
-    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b64_ptr)(a0 + 4 * TST));
+    const bf16x4 lo = tr4(a0), hi = tr4(a0 + 4 * TST);
     bf16x8 r;
     r[0] = lo[0]; r[1] = lo[1]; r[2] = lo[2]; r[3] = lo[3];
     r[4] = hi[0]; r[5] = hi[1]; r[6] = hi[2]; r[7] = hi[3];
@@ -478,25 +475,19 @@ int hs_wgrad(const WgradParams& p, hipStream_t s) {
     if (const int rc = hsplan::plan_wgrad(p, pl)) return rc;
     if (!pl.grid) return HS_OK;
     constexpr int SB = WT<false>::STAGE_ELEMS * 2, SBB = WT<true>::STAGE_ELEMS * 2;      // bytes per ring stage
-    static bool attrs = false;
-    if (!attrs) {
-        attrs = true;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_dma_kernel<6, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 6 * SB);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_dma_kernel<4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * SBB);
-    }
     switch (pl.path) {
     case hsplan::WG_REG: hipLaunchKernelGGL(wgrad_kernel, dim3(pl.grid), dim3(256), 0, s, p); break;
-    case hsplan::WG_DMA6: hipLaunchKernelGGL((wgrad_dma_kernel<6, false>), dim3(pl.grid), dim3(256), 6 * SB, s, p); break;
-    case hsplan::WG_DMA3: hipLaunchKernelGGL((wgrad_dma_kernel<3, false>), dim3(pl.grid), dim3(256), 3 * SB, s, p); break;
+    case hsplan::WG_DMA6: hs_enqueue_lds<wgrad_dma_kernel<6, false>>(dim3(pl.grid), dim3(256), 6 * SB, s, p); break;
     case hsplan::WG_BIG:
     case hsplan::WG_BIG_SLAB: {
         WgradParams q = p;
         q.msplit = pl.msplit;
         if (pl.path == hsplan::WG_BIG) q.slab = nullptr;      // (a given slab the plan does not use: atomics)
-        hipLaunchKernelGGL((wgrad_dma_kernel<4, true>), dim3(pl.grid), dim3(512), 4 * SBB, s, q);
+        hs_enqueue_lds<wgrad_dma_kernel<4, true>>(dim3(pl.grid), dim3(512), 4 * SBB, s, q);
         if (pl.reduce_grid) hipLaunchKernelGGL(wgrad_slab_reduce_kernel, dim3(pl.reduce_grid), dim3(512), 0, s, q);
         break;
     }
+    case hsplan::WG_DMA3: hipLaunchKernelGGL((wgrad_dma_kernel<3, false>), dim3(pl.grid), dim3(256), 3 * SB, s, p); break;
     }
     return (int)hipGetLastError();
 }

@@ -174,6 +174,27 @@ def test_build_info_names_every_ablation_switch_and_the_loader_refuses_variants(
         assert r.returncode == 0 and "loaded" in r.stdout, r.stderr[-500:]
 
 
+def test_shared_device_primitives_are_defined_once():
+    """The device vocabulary the kernel units share has ONE definition each under csrc/ (common.h; the phase counters in phase.h),
+    the names of the per-unit copies it replaced are gone, and `static bool attr_set` (a launcher's own "opt in to dynamic LDS
+    once" block instead of common.h's hs_launch_lds) stands only where it was left on purpose: hs_loss in elem.hip, which opts in
+    to a fixed 150 KiB and launches with less.  (fused_enc.hip's set_attrs, one flag for the three kernels of a width, is the other
+    local block.)  Source text only: no library is loaded."""
+    csrc = os.path.join(ROOT, "hsimae_amd", "csrc")
+    text = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h", ".cpp"))}
+    for name in ("mfma16k16", "tr4", "cvt4", "zero4", "pack2", "ld8", "st8", "bld8", "bst8", "launder"):
+        defs = [f for f, t in text.items() for _ in re.finditer(r"__device__[^;{}()]*?\b%s\s*\(" % name, t)]
+        assert defs == ["common.h"], (name, defs)
+    for gone in ("mfma_k16", "mfma_k16w", "tr4w", "cvt4w", "zero4_", "red8", "redrow", "PHB_DECL", "PHF_FLUSH", "PH2_DECL"):
+        assert [f for f, t in text.items() if re.search(r"\b%s\b" % gone, t)] == [], gone
+    assert [(f, t.count("static bool attr_set")) for f, t in text.items() if "static bool attr_set" in t] == [("elem.hip", 1)]
+    # the phase macros are defined in phase.h alone, and every unit that stamps phases gets them from there
+    for f, t in text.items():
+        assert (re.search(r"#\s*define\s+PHS?(_\w+)?\(", t) is not None) == (f == "phase.h"), f
+        if f != "phase.h" and re.search(r"\bPH_DECL\(", t):
+            assert '#include "phase.h"' in t, f
+
+
 def test_weight_gradient_slab_is_sized_from_both_widths():
     """the caller's stream also runs the DECODER's weight-gradient launches when the decoder goes layer at a
     time; with embed_dim 128 and decoder_embed_dim 256 those take the 256 x 256-tile path (13 tiles x 19 row slices = 247
