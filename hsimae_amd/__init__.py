@@ -24,6 +24,7 @@ from .scene_data import SceneCubes, get_scene_set_dual, split_labeled, tile_orig
 from .gwpca import GWPCA, apply_gwpca  # noqa: F401
 from .classify import ClassLoss, ScoreMeter  # noqa: F401
 from .knn import KNNClassifier  # noqa: F401
+from .recon import SceneReconstruction, reconstruct_scene, recon_eval_scene, window_centres  # noqa: F401
 from .colormap import label_to_colormap, save_label_png  # noqa: F401
 
 __version__ = "0.1.0"

@@ -160,6 +160,16 @@ class KnnVoteParams(C.Structure):
                 ("label_map", vp), ("conf_map", vp), ("margin_map", vp), ("probs", vp), ("ldp", i32), ("bad", vp)]
 
 
+class ReconAccumulateParams(C.Structure):
+    _fields_ = [("pred_img", vp), ("mask_img", vp), ("n", i32), ("w0", i64), ("rows", vp), ("nrows", i32), ("cols", vp), ("ncols", i32),
+                ("H", i32), ("W", i32), ("C", i32), ("sum", vp), ("cnt", vp)]
+
+
+class ReconFinishParams(C.Structure):
+    _fields_ = [("scene", vp), ("scene_f64", i32), ("H", i32), ("W", i32), ("C", i32), ("sum", vp), ("cnt", vp),
+                ("recon", vp), ("cover", vp), ("rmse", vp), ("sam", vp), ("partials", vp), ("stats", vp)]
+
+
 class GradSeg(C.Structure):
     _fields_ = [("g", vp), ("group", vp), ("n", i64)]
 
@@ -184,6 +194,7 @@ ADAMW_MAX_GROUPS = 64   # HSIMAE_ADAMW_MAX_GROUPS
 CLIP_GRID = 1024        # HSIMAE_CLIP_GRID: doubles of scratch hsimae_grad_norm needs in `partials`
 CLIP_MAX_SEGS = 8       # HSIMAE_CLIP_MAX_SEGS
 LAMB_CHUNK = 4096       # HSIMAE_LAMB_CHUNK: floats of one tensor behind one workgroup of hsimae_lamb_step
+RECON_GRID = 1024       # HSIMAE_RECON_GRID: hsimae_recon_finish needs 4 doubles of scratch for each in `partials`
 EMA_MAX_GRID = 2048     # HSIMAE_EMA_MAX_GRID: workgroups (of 256 threads) hsimae_ema_update / hsimae_ema_swap launch at most
 
 
@@ -259,6 +270,8 @@ SYMBOLS = {
     "hsimae_row_normalize": (C.c_int, [C.POINTER(RowNormalizeParams), vp]),
     "hsimae_knn_topk": (C.c_int, [C.POINTER(KnnTopkParams), vp]),
     "hsimae_knn_vote": (C.c_int, [C.POINTER(KnnVoteParams), vp]),
+    "hsimae_recon_accumulate": (C.c_int, [C.POINTER(ReconAccumulateParams), vp]),
+    "hsimae_recon_finish": (C.c_int, [C.POINTER(ReconFinishParams), vp]),
     "hsimae_encode": (C.c_int, [C.POINTER(Config), C.POINTER(IO), vp]),
     "hsimae_encode_backward": (C.c_int, [C.POINTER(Config), C.POINTER(IO), vp, vp, BUCKET_CB, vp, vp]),
     "hsimae_agg_pool": (C.c_int, [vp, vp, i32, i32, i32, i32, vp]),

@@ -48,6 +48,29 @@ def scene_views(views):
     return tuple(int(v) for v in out)
 
 
+def scene_array(scene, bands, batch_size):
+    """The checks every whole-scene entry point makes of its `scene` and `batch_size` (DualViT._scene_args, reconstruct_scene)
+    -> (scene tensor, H, W, bands)."""
+    if isinstance(scene, torch.Tensor):
+        s = scene
+    else:
+        s = torch.from_numpy(np.asarray(scene))
+    if s.dim() != 3:
+        raise ValueError(f"scene must be [H, W, C], got shape {tuple(s.shape)}")
+    H, W, Cb = (int(v) for v in s.shape)
+    if s.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"scene must be float32 or float64, got {s.dtype}")
+    if Cb % 8:
+        raise ValueError(f"scene has {Cb} bands: the band count must be a multiple of 8 (b_patch_size)")
+    if Cb != bands:
+        raise ValueError(f"scene has {Cb} bands, the model was built for bands={bands}")
+    if H <= 0 or W <= 0:
+        raise ValueError(f"empty scene {tuple(s.shape)}")
+    if int(batch_size) < 1:
+        raise ValueError(f"batch_size must be >= 1, got {batch_size}")
+    return s, H, W, Cb
+
+
 class _FineTuneStep(torch.autograd.Function):
     """DualViT.forward in training as one autograd node: encoder / decoder parameter gradients are written by the kernels
     into the model's flat gradient buffer; the head's two parameters are ordinary autograd inputs."""
@@ -200,23 +223,7 @@ class DualViT(HSIMAE):
     def _scene_args(self, scene, pixels, batch_size):
         """The argument checks and the chunk size predict_scene and classify_scene share
         -> (scene tensor, H, W, bands, pixel indices (CPU int64) or None, the model's device, pixel count, pixels per chunk)."""
-        if isinstance(scene, torch.Tensor):
-            s = scene
-        else:
-            s = torch.from_numpy(np.asarray(scene))
-        if s.dim() != 3:
-            raise ValueError(f"scene must be [H, W, C], got shape {tuple(s.shape)}")
-        H, W, Cb = (int(v) for v in s.shape)
-        if s.dtype not in (torch.float32, torch.float64):
-            raise ValueError(f"scene must be float32 or float64, got {s.dtype}")
-        if Cb % 8:
-            raise ValueError(f"scene has {Cb} bands: the band count must be a multiple of 8 (b_patch_size)")
-        if Cb != self.patch_embed.bands:
-            raise ValueError(f"scene has {Cb} bands, the model was built for bands={self.patch_embed.bands}")
-        if H <= 0 or W <= 0:
-            raise ValueError(f"empty scene {tuple(s.shape)}")
-        if int(batch_size) < 1:
-            raise ValueError(f"batch_size must be >= 1, got {batch_size}")
+        s, H, W, Cb = scene_array(scene, self.patch_embed.bands, batch_size)
         pix = None
         if pixels is not None:
             pix = torch.as_tensor(pixels).detach().cpu()

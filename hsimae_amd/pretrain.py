@@ -61,9 +61,32 @@ def dp_context(device):
     return rank, world, device
 
 
+VAL_SEED = 1234
+
+
+def _validate(model, scene, mask_ratio, device):
+    """(mse, mean spectral angle) of reconstruct_scene on `scene` with a fixed seed of its own; the python `random` state is put
+    back and the device's generator is not touched, so the training streams do not notice the call."""
+    from .recon import reconstruct_scene
+    state = random.getstate()
+    training = model.training
+    try:
+        random.seed(VAL_SEED)
+        gen = torch.Generator(device=device)
+        gen.manual_seed(VAL_SEED)
+        model.eval()
+        r = reconstruct_scene(model, scene, mask_ratio=mask_ratio, generator=gen, return_recon=False, on_device=True)
+        mse, mean_sam = torch.stack([r.mse, r.mean_sam]).tolist()          # one read per validation
+    finally:
+        random.setstate(state)
+        model.train(training)
+    return mse, mean_sam
+
+
 def mask_pretraining(data_cubes, save_path, model_name, img_size=9, bands=32, mask_ratio=0.50, lr=5e-3, wd=5e-2, bs=512,
                      epochs=100, depth=12, dim=64, s_depth=6, dec_dim=48, dec_depth=2, resume_path=None, device="cuda:0",
-                     log=print, max_grad_norm=None, skip_nonfinite=False, optimizer="adamw", ema_decay=None, ema_warmup=True):
+                     log=print, max_grad_norm=None, skip_nonfinite=False, optimizer="adamw", ema_decay=None, ema_warmup=True,
+                     val_scene=None, val_every=1):
     """`optimizer`: "adamw" (the reference's recipe, the default) or "lamb": FusedLAMB with the same lr, wd and betas and
     max_grad_norm 1.0 where the caller left it None (LAMB's usual pre-normalisation); every epoch then also logs the smallest and
     largest trust ratio among the adapted tensors, as the epoch's last step left them.  No large-batch recipe has been measured.
@@ -74,6 +97,12 @@ def mask_pretraining(data_cubes, save_path, model_name, img_size=9, bands=32, ma
     `ema_decay` / `ema_warmup` go to the optimizer: it keeps a moving average of the weights on the device, `<stem>_ema.pkl` is
     written next to `model_name` (same keys; `model_name` stays the raw weights), and the per-epoch resume file carries the average
     in the optimizer's state.
+
+    `val_scene` [H, W, C]: after every `val_every`-th epoch rank 0 masks and reconstructs this scene at the run's `mask_ratio`
+    (recon.reconstruct_scene, stride 9, one pass, its own fixed seed: python `random` and the device generator are left as they
+    were), logs the mean squared error and the mean spectral angle, and train_log.npy is then a dict with the keys
+    "epoch_loss", "val_loss", "val_epoch", "val_mse", "val_mean_sam".  Without it the loop, its RNG streams and its files are
+    what they were.
 
     `bs` is the GLOBAL batch, as in the reference; under a data-parallel launch each rank takes bs / world cubes of every
     batch (same permutation and python-random stream on every rank), gradients are averaged with the bucketed RCCL
@@ -110,6 +139,9 @@ def mask_pretraining(data_cubes, save_path, model_name, img_size=9, bands=32, ma
     scheduler = CosineLRScheduler(optimizer, t_initial=iters, lr_min=1e-6, warmup_t=int(np.ceil(iters * 0.05)))
 
     epoch_loss_list, val_loss_list = [], []
+    val_epochs, val_mse, val_sam = [], [], []
+    if val_scene is not None and int(val_every) < 1:
+        raise ValueError(f"val_every must be >= 1, got {val_every}")
     iter_num, first_epoch = 0, 0
     if resume_path is not None and os.path.exists(resume_path):
         model._ensure_flat(device)                      # the optimizer state is laid out like the flat buffer
@@ -153,10 +185,20 @@ def mask_pretraining(data_cubes, save_path, model_name, img_size=9, bands=32, ma
             norm_max, skipped = torch.stack([optimizer.grad_norm_max.double(), optimizer.skipped_steps.double()]).tolist()
             optimizer.reset_grad_norm_max()
             log(f"epoch {epoch}: loss {epoch_loss:.6f}, largest gradient norm {norm_max:.6g}, {int(skipped)} steps skipped so far")
+        if val_scene is not None and rank == 0 and (epoch + 1) % int(val_every) == 0:
+            mse, mean_sam = _validate(model, val_scene, mask_ratio, device)
+            val_epochs.append(epoch)
+            val_mse.append(mse)
+            val_sam.append(mean_sam)
+            log(f"epoch {epoch}: loss {epoch_loss:.6f}, scene reconstruction mse {mse:.6g}, mean spectral angle {mean_sam:.6g} rad")
         if resume_path is not None and rank == 0:
             save_resume(resume_path, model, optimizer, scheduler, epoch + 1, iter_num, epoch_loss_list, device)
     if rank == 0:
         save_final(model, save_path, model_name, epoch_loss_list, val_loss_list)
+        if val_scene is not None:                       # the same file, with the validation figures under keys of their own
+            np.save(os.path.join(save_path, "train_log.npy"),
+                    np.array({"epoch_loss": list(epoch_loss_list), "val_loss": list(val_loss_list), "val_epoch": val_epochs,
+                              "val_mse": val_mse, "val_mean_sam": val_sam}, dtype=object))
         if ema_decay is not None:
             torch.save(optimizer.ema_state_dict(), os.path.join(save_path, os.path.splitext(model_name)[0] + "_ema.pkl"))
     return model, epoch_loss_list

@@ -742,6 +742,64 @@ typedef struct {
 } hsimae_knn_vote_params;
 int hsimae_knn_vote(const hsimae_knn_vote_params* p, void* stream);
 
+/* ------------------------------------------------------------------ masked reconstruction of a whole scene (csrc/recon.hip)
+ * ADDED under HSIMAE_VERSION 108 like the entry points above: nothing that 108 already had changes.  The way back from the
+ * windows hsimae_forward reconstructs to the scene they were cut from, and the error maps and sums behind PSNR and the spectral
+ * angle (SAM).  No atomics, no host wait: two runs are bit-identical; chunks and passes are ordered by the stream.
+ *
+ * Window grid: 9 x 9 windows (hsimae_scene_batch's) centred on the scene pixels (rows[ir], cols[ic]); window w = ir * ncols + ic.
+ * Only a window's un-reflected positions map back to the scene: position (i, j) of window (ir, ic) is pixel
+ * (rows[ir] - 4 + i, cols[ic] - 4 + j) when that lies inside the scene, and is ignored when the symmetric pad filled it.
+ *
+ * hsimae_recon_accumulate: one call per forward chunk.  pred_img / mask_img fp32 [n][C][9][9], contiguous as hsimae_forward
+ *   writes them, hold the windows w0 .. w0 + n - 1; rows int32 [nrows] and cols int32 [ncols] are DEVICE memory, strictly
+ *   ascending, inside the scene; sum fp32 [H][W][C] and cnt int32 [H][W][C] are zeroed once by the caller.  For every voxel
+ *   (r, c, b) and every window of the chunk with |rows[ir] - r| <= 4 and |cols[ic] - c| <= 4, in ascending w:
+ *     if mask_img[w - w0][b][r - rows[ir] + 4][c - cols[ic] + 4] != 0:  sum += pred_img[the same],  cnt += 1
+ *   in fp32, starting from what sum held.  A select, not a product: a pred_img value under mask 0 is never read into the
+ *   result.  A gather with one lane per voxel; a voxel no window of the chunk reconstructs is not written.
+ *   Refusals: params NULL -> HSIMAE_ENULL; n < 0, w0 < 0, H, W, C, nrows or ncols <= 0, nrows > H or ncols > W (all the host can
+ *   see of a list that is not strictly ascending inside the scene), w0 + n > nrows * ncols -> HSIMAE_EDIMS; with n > 0 a NULL
+ *   pointer -> HSIMAE_ENULL; a pointer not aligned to its element -> HSIMAE_EALIGN.  n = 0 -> HSIMAE_OK, nothing written.
+ *   List values the host cannot see are never trusted for an address: a centre further than 4 from the voxel is skipped.
+ *
+ * hsimae_recon_finish: two launches.  Per pixel, with x_b = the scene value as fp32 (fp64 -> fp32 rounds to nearest even, as the
+ *   windows), S = {b : cnt_b > 0}, m = |S|, r_b = sum_b / (float)cnt_b (IEEE fp32 division) on S and x_b elsewhere; each output
+ *   optional except stats:
+ *     recon fp32 [H][W][C] = r;      cover int32 [H][W] = m;
+ *     rmse  fp32 [H][W] = (float)sqrt(se / m), se = sum over S of (r - x)^2;
+ *     sam   fp32 [H][W] = (float)(2 atan2(sqrt(sum_S (r/nr - x/nx)^2), sqrt(sum_S (r/nr + x/nx)^2))), nr = sqrt(sum_S r^2),
+ *           nx = sqrt(sum_S x^2): the well-conditioned form of the angle, not acos of a ratio.  nr = nx = 0 -> 0; one of them
+ *           0 -> pi / 2.  m = 0 -> rmse = sam = 0.
+ *   All sums are fp64: lane l of the pixel's wave takes the bands l, l + 64, .. in order with fma, the 64 sums are added by the
+ *   xor tree (partner lane ^ 1, ^ 2, .. ^ 32).
+ *     stats fp64 [4] = sum of se, sum of m, sum of the fp64 sam, and the count, over the pixels with m > 0.  Wave v of workgroup
+ *           g takes the pixels 4 g + v, 4 g + v + 4 G, .. (G = min(ceil(H W / 4), HSIMAE_RECON_GRID) workgroups) in order, the
+ *           workgroup adds its waves 0 .. 3 into partials [G][4], and one workgroup adds those: per statistic, lane l of one
+ *           wave takes g = l, l + 64, .. in order, then the xor tree.
+ *     partials fp64, 4 * HSIMAE_RECON_GRID doubles of scratch, required.
+ *   A NaN that was accumulated shows in that pixel's outputs and in stats.
+ *   Refusals: params NULL -> HSIMAE_ENULL; H, W or C <= 0 -> HSIMAE_EDIMS; scene, sum, cnt, partials or stats NULL ->
+ *   HSIMAE_ENULL; a pointer not aligned to its element -> HSIMAE_EALIGN. */
+#define HSIMAE_RECON_GRID 1024       /* workgroups of the finish's first launch at most; partials holds 4 doubles for each */
+typedef struct {
+    const float* pred_img; const float* mask_img;
+    int32_t n; int64_t w0;
+    const int32_t* rows; int32_t nrows;
+    const int32_t* cols; int32_t ncols;
+    int32_t H, W, C;
+    float* sum; int32_t* cnt;
+} hsimae_recon_accumulate_params;
+int hsimae_recon_accumulate(const hsimae_recon_accumulate_params* p, void* stream);
+
+typedef struct {
+    const void* scene; int32_t scene_f64; int32_t H, W, C;
+    const float* sum; const int32_t* cnt;
+    float* recon; int32_t* cover; float* rmse; float* sam;
+    double* partials; double* stats;
+} hsimae_recon_finish_params;
+int hsimae_recon_finish(const hsimae_recon_finish_params* p, void* stream);
+
 /* ------------------------------------------------------------------ gradient norm, clipping and the non-finite step skip
  * (what torch.nn.utils.clip_grad_norm_ and an `isfinite(...).item()` test do on the host, kept in device memory: no host wait).
  * ADDED under HSIMAE_VERSION 108 like the entry points above: nothing that 108 already had changes; hsimae_adamw_step is as it was.
