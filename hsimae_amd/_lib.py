@@ -160,6 +160,16 @@ class KnnVoteParams(C.Structure):
                 ("label_map", vp), ("conf_map", vp), ("margin_map", vp), ("probs", vp), ("ldp", i32), ("bad", vp)]
 
 
+class KmeansAssignParams(C.Structure):
+    _fields_ = [("x", vp), ("ldx", i32), ("c", vp), ("ldc", i32), ("bias", vp), ("N", i32), ("K", i32), ("D", i32), ("first", i32),
+                ("H", i32), ("W", i32), ("p0", i64), ("pixels", vp), ("labels", vp), ("score", vp), ("margin", vp), ("changed", vp)]
+
+
+class KmeansUpdateParams(C.Structure):
+    _fields_ = [("x", vp), ("ldx", i32), ("labels", vp), ("N", i32), ("K", i32), ("D", i32), ("first", i32), ("normalize", i32),
+                ("c", vp), ("ldc", i32), ("bias", vp), ("counts", vp), ("sums", vp), ("changed", vp), ("scratch", vp), ("state", vp)]
+
+
 class ReconAccumulateParams(C.Structure):
     _fields_ = [("pred_img", vp), ("mask_img", vp), ("n", i32), ("w0", i64), ("rows", vp), ("nrows", i32), ("cols", vp), ("ncols", i32),
                 ("H", i32), ("W", i32), ("C", i32), ("sum", vp), ("cnt", vp)]
@@ -195,6 +205,8 @@ CLIP_GRID = 1024        # HSIMAE_CLIP_GRID: doubles of scratch hsimae_grad_norm 
 CLIP_MAX_SEGS = 8       # HSIMAE_CLIP_MAX_SEGS
 LAMB_CHUNK = 4096       # HSIMAE_LAMB_CHUNK: floats of one tensor behind one workgroup of hsimae_lamb_step
 RECON_GRID = 1024       # HSIMAE_RECON_GRID: hsimae_recon_finish needs 4 doubles of scratch for each in `partials`
+KMEANS_GRID = 2048      # HSIMAE_KMEANS_GRID: int32 partial counts hsimae_kmeans_assign writes into `changed`
+KMEANS_STATE = 8        # HSIMAE_KMEANS_STATE: doubles of hsimae_kmeans_update's state block (inertia, changed, iterations, empty, bad)
 EMA_MAX_GRID = 2048     # HSIMAE_EMA_MAX_GRID: workgroups (of 256 threads) hsimae_ema_update / hsimae_ema_swap launch at most
 
 
@@ -270,6 +282,8 @@ SYMBOLS = {
     "hsimae_row_normalize": (C.c_int, [C.POINTER(RowNormalizeParams), vp]),
     "hsimae_knn_topk": (C.c_int, [C.POINTER(KnnTopkParams), vp]),
     "hsimae_knn_vote": (C.c_int, [C.POINTER(KnnVoteParams), vp]),
+    "hsimae_kmeans_assign": (C.c_int, [C.POINTER(KmeansAssignParams), vp]),
+    "hsimae_kmeans_update": (C.c_int, [C.POINTER(KmeansUpdateParams), vp]),
     "hsimae_recon_accumulate": (C.c_int, [C.POINTER(ReconAccumulateParams), vp]),
     "hsimae_recon_finish": (C.c_int, [C.POINTER(ReconFinishParams), vp]),
     "hsimae_encode": (C.c_int, [C.POINTER(Config), C.POINTER(IO), vp]),

@@ -54,6 +54,8 @@ int hs_class_prob(const hsimae_class_prob_params& p, hipStream_t s);
 int hs_row_normalize(const hsimae_row_normalize_params& p, hipStream_t s);
 int hs_knn_topk(const hsimae_knn_topk_params& p, hipStream_t s);
 int hs_knn_vote(const hsimae_knn_vote_params& p, hipStream_t s);
+int hs_kmeans_assign(const hsimae_kmeans_assign_params& p, hipStream_t s);
+int hs_kmeans_update(const hsimae_kmeans_update_params& p, hipStream_t s);
 int hs_recon_accumulate(const hsimae_recon_accumulate_params& p, hipStream_t s);
 int hs_recon_finish(const hsimae_recon_finish_params& p, hipStream_t s);
 int hs_agg_pool(const float* latent, float* pooled, int N, int T, int L, int D, hipStream_t s);

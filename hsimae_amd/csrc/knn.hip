@@ -20,6 +20,7 @@
 //
 // No atomics anywhere; a row is touched by one wave: two runs are bit-identical.
 #include "common.h"
+#include "dot_tile.h"
 #include "kernels.h"
 
 namespace {
@@ -27,22 +28,15 @@ namespace {
 constexpr int KNN_MAXK = 64;          // one list entry per lane
 constexpr int KNN_MAXC = 1024;
 constexpr int KNN_MAXNB = 2048;       // workgroups at most: a stride loop beyond (rows of normalize / vote, query tiles of top-k)
-constexpr int TQ = 64, TB = 64, KS = 32;
-constexpr int SLD = KS + 1;           // LDS row stride of a slab: lane (i, h) reads [i][2 t + h], 33 i + h spreads over the banks
-constexpr int PLD = TB + 1;           // row stride of the handed-over block
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
+// the slabs, the 64 x 64 dot tile, beats() and the row norm: dot_tile.h (shared with kmeans.hip)
 
 __global__ __launch_bounds__(256) void row_normalize_kernel(hsimae_row_normalize_params p) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, D = p.D;
     for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < p.N; r += (int64_t)gridDim.x * 4) {       // wave-uniform
         const float* x = p.x + r * p.ld;
         float* o = p.out + r * p.ldo;
-        float ss = 0.f;
-        for (int c = lane; c < D; c += 64) ss = fmaf(x[c], x[c], ss);
-        for (int s = 1; s < 64; s <<= 1) ss += __shfl_xor(ss, s);
-        const float n = sqrtf(ss);
-        const float rn = 1.f / fmaxf(n, 1e-12f);
+        float n;
+        const float rn = row_inv_norm(x, D, lane, n);
         for (int c = lane; c < D; c += 64) o[c] = x[c] * rn;
         if (p.norms && lane == 0) p.norms[r] = n;
     }
@@ -52,69 +46,20 @@ __global__ __launch_bounds__(256) void row_normalize_kernel(hsimae_row_normalize
 __device__ __forceinline__ int lane_of(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
 __device__ __forceinline__ float lane_of(float v, int l) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l)); }
 
-// does candidate s go in front of entry e?  (strictly: an equal one stays behind; a NaN goes in front of nothing)
-__device__ __forceinline__ bool beats(float s, float e) { return !__builtin_isnan(s) && (__builtin_isnan(e) || s > e); }
-
-// one 64-row x 32-column slab of a [rows][ld] matrix: this thread's two 16-byte pieces, zero beyond `rows` and beyond D (fetch),
-// and their place in LDS (put).  The two halves are apart so that the global loads of the next slab fly during the MFMAs of this one.
-struct SlabRegs { f32x4 v[2]; };
-__device__ __forceinline__ SlabRegs fetch_slab(const float* src, int64_t row0, int64_t rows, int ld, int k0, int D) {
-    const int c4 = threadIdx.x & 7;
-    SlabRegs s;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int r = (threadIdx.x >> 3) + 32 * h;
-        s.v[h] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (row0 + r < rows && k0 + 4 * c4 < D) s.v[h] = *reinterpret_cast<const f32x4*>(src + (row0 + r) * ld + k0 + 4 * c4);    // D % 4 == 0
-    }
-    return s;
-}
-__device__ __forceinline__ void put_slab(float (*dst)[SLD], const SlabRegs& s) {
-    const int c4 = threadIdx.x & 7;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int r = (threadIdx.x >> 3) + 32 * h;
-        dst[r][4 * c4 + 0] = s.v[h][0]; dst[r][4 * c4 + 1] = s.v[h][1]; dst[r][4 * c4 + 2] = s.v[h][2]; dst[r][4 * c4 + 3] = s.v[h][3];
-    }
-}
-
 __global__ __launch_bounds__(256) void knn_topk_kernel(hsimae_knn_topk_params p) {
     __shared__ float slabs[2][TQ][SLD];          // the two operands' slabs; after a tile's last slab the block P lies over them
     float (*Qs)[SLD] = slabs[0], (*Bs)[SLD] = slabs[1];
     float (*P)[PLD] = reinterpret_cast<float (*)[PLD]>(&slabs[0][0][0]);       // the tile's dot products [query][bank row]
-    static_assert(TQ == TB && 2 * TQ * SLD >= TQ * PLD, "P fits over the slabs");
     __shared__ float Ls[TQ][KNN_MAXK];           // running lists, rank = column
     __shared__ int Li[TQ][KNN_MAXK];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, k = p.k, D = p.D;
-    const int qi = (wave & 1) * 32, bj = (wave >> 1) * 32;                 // this wave's 32 x 32 block of the tile
-    const int li = lane & 31, lh = lane >> 5;
     const int64_t qtiles = ((int64_t)p.Q + TQ - 1) / TQ;
     for (int64_t qt = blockIdx.x; qt < qtiles; qt += gridDim.x) {
         const int64_t q0 = qt * TQ;
         SlabRegs rq = fetch_slab(p.q, q0, p.Q, p.ldq, 0, D), rb = fetch_slab(p.bank, 0, p.M, p.ldb, 0, D);
         for (int64_t j0 = 0; j0 < p.M; j0 += TB) {
-            f32x16 acc;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-            for (int k0 = 0; k0 < D; k0 += KS) {
-                __syncthreads();                                           // the slab's readers (and P's, a tile earlier) are done
-                put_slab(Qs, rq);
-                put_slab(Bs, rb);
-                __syncthreads();
-                // the next slab of this tile, or the first of the next tile (it arrives during the list updates); none after the last
-                const bool more = k0 + KS < D;
-                if (more || j0 + TB < p.M) {
-                    rq = fetch_slab(p.q, q0, p.Q, p.ldq, more ? k0 + KS : 0, D);
-                    rb = fetch_slab(p.bank, more ? j0 : j0 + TB, p.M, p.ldb, more ? k0 + KS : 0, D);
-                }
-#pragma unroll
-                for (int t = 0; t < KS / 2; ++t)                           // lane half h carries k0 + 2 t + h: ascending k
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(Qs[qi + li][2 * t + lh], Bs[bj + li][2 * t + lh], acc, 0, 0, 0);
-            }
-            __syncthreads();                                               // every wave has read its last slab
-#pragma unroll
-            for (int i = 0; i < 16; ++i) P[qi + (i & 3) + 8 * (i >> 2) + 4 * lh][bj + li] = acc[i];
-            __syncthreads();
+            const f32x16 acc = dot_tile(Qs, Bs, rq, rb, p.q, q0, p.Q, p.ldq, p.bank, j0, p.M, p.ldb, D);
+            hand_over(P, acc);
             // the lists of this wave's 16 rows; before this tile every row holds min(k, j0) entries
             const int len0 = j0 < k ? (int)j0 : k;
             const bool valid = j0 + lane < p.M;

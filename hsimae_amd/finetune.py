@@ -397,6 +397,96 @@ class DualViT(HSIMAE):
                 knn.check()
         return SceneClassification(*out)
 
+    # ------------------------------------------------------------------ a land-cover map without labels
+    def cluster_scene(self, scene, n_clusters, pixels=None, fit_pixels=None, features="encoder", metric=None, flip=0, max_iter=20,
+                      n_init=1, generator=None, batch_size=8192, on_device=False, init="random"):
+        """k-means (cluster.KMeans: hsimae_kmeans_assign / hsimae_kmeans_update) on the features of a scene's pixels: the
+        segmentation a pretrained encoder gives without any label.
+        features="encoder": `scene_features` (flip code `flip`), default metric "cosine"; features="spectra": the scene's own
+        [H * W, C] rows as fp32 (C zero-padded to the next multiple of 4), default metric "euclidean": the classical baseline,
+        with no encoder pass.  `fit_pixels` (pixel indices r * W + c, default: `pixels`) are the rows the centroids are fitted
+        on; every one of `pixels` (default: all) is then labelled.  The features of the fitted pixels stay resident across the
+        rounds (Base, 610 x 340 x 32 at T * D = 512 columns: 425 MB); with `fit_pixels` given (a grid, say), the other pixels are
+        labelled chunk by chunk through KMeans.predict_into, so a large scene never holds all its features.
+        `init`: "random" (KMeans': distinct fitted rows from torch.randperm on `generator`), a 1-D integer array of n_clusters
+        pixel indices whose features seed the centroids, or a float tensor [n_clusters, D] of seed centroids in feature space.
+        `max_iter`, `n_init`: KMeans'.  `scene`, `batch_size`, eval / no-grad behaviour: as predict_scene.
+        -> SceneClustering(labels int64 [H, W] in 1 .. n_clusters, 0 where not asked; score fp32 [H, W]; margin fp32 [H, W] (best
+        - second best score); centroids fp32 [n_clusters, D]; counts int64 [n_clusters] over the fitted pixels; inertia; n_iter),
+        on the CPU after one wait for the copies; on_device=True: all stay on the model's device and, with n_init = 1, nothing
+        waits for the host.  The fitted object of the last call stays reachable as `self.last_kmeans`."""
+        from .cluster import KMeans, SceneClustering
+        if features not in ("encoder", "spectra"):
+            raise ValueError(f'features must be "encoder" or "spectra", got {features!r}')
+        (flip,) = scene_views((flip,))
+        metric = metric or ("cosine" if features == "encoder" else "euclidean")
+        def index(p, what, HW):
+            p = torch.as_tensor(p).detach().cpu()
+            if p.dim() != 1 or p.dtype.is_floating_point or p.dtype == torch.bool or not p.numel():
+                raise ValueError(f"{what} must be a non-empty 1-D array of integer pixel indices (r * W + c)")
+            p = p.to(torch.int64).contiguous()
+            if int(p.min()) < 0 or int(p.max()) >= HW:
+                raise ValueError(f"{what}: pixel index out of range [0, {HW})")
+            return p
+
+        if features == "encoder":
+            s, H, W, Cb, pix, dev, n_total, _ = self._scene_args(scene, pixels, batch_size)
+        else:                                              # the scene's own rows: any band count, the encoder is not run
+            s = scene if isinstance(scene, torch.Tensor) else torch.from_numpy(np.asarray(scene))
+            if s.dim() != 3 or s.dtype not in (torch.float32, torch.float64) or not s.numel():
+                raise ValueError(f"scene must be a non-empty float32 or float64 [H, W, C], got {tuple(s.shape)} {s.dtype}")
+            H, W, Cb = (int(v) for v in s.shape)
+            dev = self.cls_head.weight.device
+            if dev.type != "cuda":
+                raise RuntimeError("hsimae_amd runs on MI355X only (no CPU fallback): move the model to a GPU")
+            pix = None if pixels is None else index(pixels, "pixels", H * W)
+            n_total = H * W if pix is None else pix.numel()
+        fit_pix = None if fit_pixels is None else index(fit_pixels, "fit_pixels", H * W)
+        seed_pix = None
+        if not isinstance(init, str):
+            t = torch.as_tensor(init)
+            if t.dim() == 1:
+                seed_pix = index(t, "init", H * W)
+                if seed_pix.numel() != int(n_clusters):
+                    raise ValueError(f"init names {seed_pix.numel()} seed pixels for {n_clusters} clusters")
+        with torch.no_grad(), torch.cuda.device(dev):
+            s = s.to(dev).contiguous()
+            if features == "spectra":
+                rows = s.reshape(H * W, Cb).to(torch.float32)
+                if Cb % 4:
+                    rows = torch.nn.functional.pad(rows, (0, 4 - Cb % 4))
+
+                def feats(p):
+                    return rows if p is None else rows[p.to(dev)]
+            else:
+                def feats(p):
+                    return self.scene_features(s, p, batch_size, flip=flip, on_device=True)
+            if seed_pix is not None:
+                init = feats(seed_pix)
+            elif not isinstance(init, str):
+                init = torch.as_tensor(init).to(device=dev, dtype=torch.float32)
+            km = KMeans(n_clusters, metric=metric, max_iter=max_iter, n_init=n_init, init=init, generator=generator, first=1)
+            labels = torch.zeros(H * W, dtype=torch.int64, device=dev)
+            score = torch.zeros(H * W, dtype=torch.float32, device=dev)
+            margin = torch.zeros(H * W, dtype=torch.float32, device=dev)
+            if fit_pix is None:                            # fit on the asked pixels: their features are held once
+                f = feats(pix)
+                km.fit(f)
+                km.predict_into(f, H, W, None if pix is None else pix.to(dev), labels, score, margin)
+                del f
+            else:
+                km.fit(feats(fit_pix))
+                items = torch.arange(H * W, dtype=torch.int64) if pix is None else pix
+                group = self.KNN_GROUP_ROWS
+                for g0 in range(0, n_total, group):
+                    part = items[g0:g0 + group]
+                    km.predict_into(feats(part), H, W, part.to(dev), labels, score, margin)
+            self.last_kmeans = km
+            out = [labels.view(H, W), score.view(H, W), margin.view(H, W), km.centroids, km.counts, km.inertia_, km.n_iter_]
+            if not on_device:
+                out = [t.cpu() for t in out]
+        return SceneClustering(*out)
+
     # ------------------------------------------------------------------ stochastic depth (Models.py:235-263, 687-731)
     def drop_rates(self):
         """DropPath probability of every encoder block in execution order (blocks_1, blocks_2, blocks)."""

@@ -413,3 +413,68 @@ def knn_eval_scene(scene, train_index, train_labels, test_gt, gt, pretrained, de
                            batch_size=batch_size, on_device=True).labels
     name = os.path.basename(str(pretrained)) if model_name is None else model_name
     return _score_and_save(pred, test_gt, gt, n_class, device, save_dir, name, save_images)
+
+
+def cluster_eval_scene(scene, gt, pretrained, n_clusters=None, depth=12, dim=96, s_depth=6, features="encoder", metric=None, flip=0,
+                       max_iter=20, n_init=1, generator=None, init="random", fit_pixels=None, device="cuda:0", batch_size=8192,
+                       save_dir=None, model_name=None, save_images=False):
+    """The evaluation of a checkpoint that needs no label to produce its map: k-means on the frozen encoder's pooled features over
+    the whole scene (HSIViT.cluster_scene), scored against `gt` the way the unsupervised HSI literature scores a clustering.
+    `pretrained`: the path of a state dict, loaded as knn_eval_scene loads it (a pretraining and a fine-tuned checkpoint both
+    work); it may be None with features="spectra", the classical baseline of k-means on the spectra themselves, which runs no
+    encoder.  `n_clusters` defaults to the number of real classes in `gt` (distinct labels other than 0).  `features`, `metric`,
+    `flip`, `max_iter`, `n_init`, `generator`, `init`, `fit_pixels`: cluster_scene's.
+    The contingency counts of (gt, cluster) over the labelled pixels are taken on the device (ScoreMeter with max(clusters,
+    classes) + 1 labels); from that small table, on the host in fp64 (hsimae_amd.cluster): the one-to-one matching of clusters to
+    classes that maximises the matched pixels (Hungarian), clusters left unmatched mapped to their majority class, then
+    `scores` on the mapped map, and purity, NMI (arithmetic-mean normalisation) and ARI of the raw partition.
+    save_images=True writes test_model_scene's two pictures from the mapped map into <save_dir>/<stem of model_name>/, which
+    needs every class label inside the colour palette: otherwise ValueError, before anything is clustered.
+    -> (oa, aa, kappa, per-class recall, nmi, ari, purity, mapped prediction map, raw cluster map), both maps int64 shaped like gt."""
+    from .cluster import ari, cluster_mapping, nmi, purity
+    from .colormap import PALETTE
+    device = torch.device(device)
+    if len(scene.shape) != 3:
+        raise ValueError(f"scene must be [H, W, C], got shape {tuple(scene.shape)}")
+    if features not in ("encoder", "spectra"):
+        raise ValueError(f'features must be "encoder" or "spectra", got {features!r}')
+    if pretrained is None and features == "encoder":
+        raise ValueError('features="encoder" needs a pretrained checkpoint')
+    gt = np.asarray(gt)
+    if gt.shape != tuple(scene.shape[:2]) or gt.dtype.kind not in "iu" or gt.min() < 0:
+        raise ValueError(f"gt must be a map of non-negative integer labels shaped {tuple(scene.shape[:2])}")
+    classes = np.unique(gt[gt != 0])
+    if not classes.size:
+        raise ValueError("gt holds no labelled pixel")
+    n_class = int(classes.max()) + 1
+    K = int(classes.size if n_clusters is None else n_clusters)
+    if save_images:
+        if save_dir is None:
+            raise ValueError("save_images=True needs save_dir")
+        if n_class > PALETTE.shape[0]:
+            raise ValueError(f"save_images=True: label {n_class - 1} is outside the palette's {PALETTE.shape[0]} colours")
+    c = int(scene.shape[2])
+    bands = c if features == "encoder" else 32                 # (the spectra path never runs the encoder)
+    model = HSIViT(img_size=9, patch_size=3, in_chans=1, bands=bands, b_patch_size=8, num_class=n_class, embed_dim=dim, depth=depth,
+                   num_heads=dim // 16, s_depth=s_depth, sep_pos_embed=True, use_learnable_pos_emb=False).to(device)
+    if pretrained is not None and features == "encoder":
+        model_dict = model.state_dict()
+        loaded = torch.load(pretrained, map_location=device)
+        model_dict.update({k_: v for k_, v in loaded.items() if k_ in model_dict and v.shape == model_dict[k_].shape})
+        model.load_state_dict(model_dict)
+    model.eval()
+    raw = model.cluster_scene(scene, K, fit_pixels=fit_pixels, features=features, metric=metric, flip=flip, max_iter=max_iter,
+                              n_init=n_init, generator=generator, batch_size=batch_size, on_device=True, init=init).labels
+    meter = ScoreMeter(max(K, n_class - 1) + 1, device)
+    meter.update(gt.reshape(-1), raw.reshape(-1))              # rows: gt, columns: cluster; gt = 0 is not counted
+    table = meter.cm.cpu().numpy().astype(np.float64)[1:n_class, 1:K + 1]
+    present = np.flatnonzero(table.sum(1) > 0)                 # classes 1 + present
+    lut = np.zeros(K + 1, np.int64)
+    lut[1:] = 1 + present[cluster_mapping(table[present])]
+    raw = raw.cpu().numpy().reshape(gt.shape)
+    mapped = lut[raw]
+    oa, aa, kappa, ca = scores(gt.reshape(-1), mapped.reshape(-1))
+    if save_images:
+        name = os.path.basename(str(pretrained)) if model_name is None else model_name
+        _save_maps(save_dir, name, oa, mapped, np.where(gt == 0, 0, mapped))
+    return oa, aa, kappa, ca, nmi(table), ari(table), purity(table), mapped, raw

@@ -742,6 +742,72 @@ typedef struct {
 } hsimae_knn_vote_params;
 int hsimae_knn_vote(const hsimae_knn_vote_params* p, void* stream);
 
+/* ------------------------------------------------------------------ k-means on frozen features (csrc/kmeans.hip)
+ * ADDED under HSIMAE_VERSION 108 like the entry points above: nothing that 108 already had changes.  Lloyd's algorithm over the
+ * rows x fp32 [N][ldx] and K centroids c fp32 [K][ldc] of D columns: one round is hsimae_kmeans_assign, then hsimae_kmeans_update.
+ * No atomics, no host wait: two runs are bit-identical, and a round at a fixed point changes nothing, bit for bit.
+ * One formulation serves both metrics: score(i, k) = x_i . c_k - bias_k, the label is the argmax.  Euclidean: bias_k =
+ * 1/2 ||c_k||^2 (argmax score = argmin ||x_i - c_k||^2).  Cosine (spherical k-means): unit rows, unit centroids, bias NULL = 0.
+ * Limits of both: D > 0, D % 4 = 0, 1 <= K, first >= 0, leading dimensions >= D, else HSIMAE_EDIMS; K > 1024 or D > 4096 ->
+ * HSIMAE_EUNSUPPORTED; params NULL, or with N > 0 a required pointer NULL -> HSIMAE_ENULL; x or c not 16-byte aligned, ldx % 4 or
+ * ldc % 4 != 0, another pointer not aligned to its element -> HSIMAE_EALIGN; N = 0 -> HSIMAE_OK, nothing written (the dimension
+ * checks come first).  A refusal writes nothing.
+ *
+ * hsimae_kmeans_assign: for every row i, dot_ik as hsimae_knn_topk forms it (the exact-fp32 fmaf chain from +0 over the columns
+ *   0 .. D - 1, the same for every centroid), score_ik = dot_ik - bias_k in fp32 (one rounding; bias NULL: the dot product
+ *   itself).  The best centroid: a strictly larger score wins, equal scores stay with the lower index, a NaN score beats nothing
+ *   (among NaNs only: the lowest index).  At the row's pixel (`pixels[i]`, or p0 + i when `pixels` is NULL; nothing is written
+ *   for a pixel outside [0, H * W), as hsimae_knn_vote): labels int64 = first + best index; score fp32 or NULL = the best
+ *   score; margin fp32 or NULL = best - second best score (the best score itself when K = 1; a NaN second when every other
+ *   score is NaN).  changed int32 [HSIMAE_KMEANS_GRID] or NULL: before a label is overwritten it is compared with the value
+ *   there; entry g receives the number of rows of workgroup g whose label changed (0 for workgroups that do not exist), so the
+ *   sum of all entries is the number of changed labels.  H or W <= 0 -> HSIMAE_EDIMS.
+ *
+ * hsimae_kmeans_update: from x, labels int64 [N] in row order (cluster k = labels[i] - first) and the centroids c the labels were
+ *   assigned against (read, then overwritten), two launches:
+ *     counts int64 [K]  = members of cluster k
+ *     sums fp64 [K][D]  = the member rows added in ascending row order from 0, one fp64 chain per element (no grid dependence)
+ *     c[k]              = fp32(sums[k] / counts[k]) (fp64 division, one rounding); with normalize != 0 that mean is then
+ *                         normalised in fp32 by hsimae_row_normalize's rule and order, in place
+ *     bias fp32 [K] or NULL: bias_k = fp32(1/2 sum_d c_kd^2), the sum in fp64 over the stored fp32 centroid: lane l of one wave
+ *                         takes d = l, l + 64, .. in order with fma, then the xor tree (partner lane ^ 1, ^ 2, .. ^ 32)
+ *     an empty cluster keeps c[k] and bias_k bit for bit (sums[k] = 0, counts[k] = 0)
+ *     state fp64 [HSIMAE_KMEANS_STATE]:
+ *       [0] inertia    = sum_i ||x_i - c_old[labels[i]]||^2 in fp64: per (cluster, 64-column slab) lane l adds fma(d, d, .)
+ *                        over the members in ascending row order for column 64 slab + l, the xor tree adds the lanes; then lane l
+ *                        of one wave takes the (cluster, slab) partials l, l + 64, .. in order, and the xor tree
+ *       [1] changed    = the sum of `changed` int32 [HSIMAE_KMEANS_GRID] as hsimae_kmeans_assign wrote it (NULL: 0)
+ *       [2] iterations = its previous value + 1 if changed > 0 (the caller zeroes state once before the first round)
+ *       [3] empty      = clusters without a member
+ *       [4] bad        = labels outside [first, first + K): such a row belongs to no cluster and is counted here
+ *       [5 .. 7]       = 0
+ *     scratch fp64 [K * ceil(D / 64) + 1], required.  sums, counts, c, state required.
+ *   Seeding is one update over the K seed rows with labels first .. first + K - 1 and changed NULL. */
+#define HSIMAE_KMEANS_GRID 2048      /* workgroups of hsimae_kmeans_assign at most (a stride loop beyond); ints in `changed` */
+#define HSIMAE_KMEANS_STATE 8        /* doubles in `state` */
+typedef struct {
+    const float* x; int32_t ldx;
+    const float* c; int32_t ldc;
+    const float* bias;
+    int32_t N, K, D, first;
+    int32_t H, W; int64_t p0; const int64_t* pixels;
+    int64_t* labels; float* score; float* margin;
+    int32_t* changed;
+} hsimae_kmeans_assign_params;
+int hsimae_kmeans_assign(const hsimae_kmeans_assign_params* p, void* stream);
+
+typedef struct {
+    const float* x; int32_t ldx;
+    const int64_t* labels;
+    int32_t N, K, D, first, normalize;
+    float* c; int32_t ldc;
+    float* bias;
+    int64_t* counts; double* sums;
+    const int32_t* changed;
+    double* scratch; double* state;
+} hsimae_kmeans_update_params;
+int hsimae_kmeans_update(const hsimae_kmeans_update_params* p, void* stream);
+
 /* ------------------------------------------------------------------ masked reconstruction of a whole scene (csrc/recon.hip)
  * ADDED under HSIMAE_VERSION 108 like the entry points above: nothing that 108 already had changes.  The way back from the
  * windows hsimae_forward reconstructs to the scene they were cut from, and the error maps and sums behind PSNR and the spectral
