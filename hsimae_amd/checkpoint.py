@@ -54,3 +54,17 @@ def load_resume(path, model, optimizer, scheduler, device=None):
         scheduler.load_state_dict(blob["scheduler"])
     set_rng_state(blob["rng"], device)
     return blob["epoch"], blob["iter_num"], list(blob["epoch_loss_list"])
+
+
+def load_matching(model, path, device, match_shapes):
+    """Load the state dict saved at `path` into `model` by key, as the reference does (Model_Finetuning.py:85-96, 256-260): keys
+    the model does not have are dropped, keys the file does not have keep the model's values; then `model.eval()`.
+    match_shapes=False is the reference's own filter, for a checkpoint of THIS architecture (test_model loading what
+    dual_branch_finetuning saved): a tensor of another shape is a wrong `dim` / `depth` / class count, and load_state_dict raises.
+    match_shapes=True also drops tensors whose shape differs: the label-free evaluations (knn / cluster / recon) take a
+    checkpoint of either stage, and a pretraining one may carry a head or a decoder of other widths that they never run."""
+    own = model.state_dict()
+    loaded = torch.load(path, map_location=device)
+    own.update({k: v for k, v in loaded.items() if k in own and (not match_shapes or v.shape == own[k].shape)})
+    model.load_state_dict(own)
+    return model.eval()

@@ -26,6 +26,7 @@ import torch.nn as nn
 
 from . import _lib
 from .model import HSIMAE
+from .scene_pass import ScenePass, as_scene, gpu_of, largest_chunk, pixel_indices, to_host
 
 # what DualViT.classify_scene returns
 SceneClassification = collections.namedtuple("SceneClassification", ["labels", "confidence", "margin", "probs"])
@@ -49,23 +50,14 @@ def scene_views(views):
 
 
 def scene_array(scene, bands, batch_size):
-    """The checks every whole-scene entry point makes of its `scene` and `batch_size` (DualViT._scene_args, reconstruct_scene)
-    -> (scene tensor, H, W, bands)."""
-    if isinstance(scene, torch.Tensor):
-        s = scene
-    else:
-        s = torch.from_numpy(np.asarray(scene))
-    if s.dim() != 3:
-        raise ValueError(f"scene must be [H, W, C], got shape {tuple(s.shape)}")
+    """The checks every whole-scene entry point that runs the encoder makes of its `scene` and `batch_size` (DualViT._scene_args,
+    reconstruct_scene): scene_pass.as_scene, and bands the model can take -> (scene tensor, H, W, bands)."""
+    s = as_scene(scene)
     H, W, Cb = (int(v) for v in s.shape)
-    if s.dtype not in (torch.float32, torch.float64):
-        raise ValueError(f"scene must be float32 or float64, got {s.dtype}")
     if Cb % 8:
         raise ValueError(f"scene has {Cb} bands: the band count must be a multiple of 8 (b_patch_size)")
     if Cb != bands:
         raise ValueError(f"scene has {Cb} bands, the model was built for bands={bands}")
-    if H <= 0 or W <= 0:
-        raise ValueError(f"empty scene {tuple(s.shape)}")
     if int(batch_size) < 1:
         raise ValueError(f"batch_size must be >= 1, got {batch_size}")
     return s, H, W, Cb
@@ -169,16 +161,17 @@ class DualViT(HSIMAE):
     SCENE_WORKSPACE_BUDGET = 8 << 30
 
     def _scene_chunk(self, batch_size):
-        lib, cfg = _lib.load(), self._config()
-        T, L = self.input_size[0], self.input_size[1] ** 2
-        lo, hi = 1, int(batch_size)
-        while lo < hi:                                    # largest n <= batch_size within the budget (at least 1)
-            mid = (lo + hi + 1) // 2
-            if 0 <= lib.hsimae_workspace_bytes(C.byref(cfg), mid, T, L) <= self.SCENE_WORKSPACE_BUDGET:
-                lo = mid
-            else:
-                hi = mid - 1
-        return lo
+        grid = (self.input_size[0], self.input_size[1] ** 2)      # the unmasked encoder keeps the full token grid
+        return largest_chunk(_lib.load(), self._config(), [grid], batch_size, self.SCENE_WORKSPACE_BUDGET)
+
+    def _scene_pass(self, scene, pixels, batch_size, by_p0=False):
+        """The argument checks the entry points share (scene, batch_size, pixels; the device last) and the ScenePass over `pixels`;
+        over all pixels (None): the index list arange(H * W), or with by_p0 no list (hsimae_scene_windows' range from p0)."""
+        s, H, W, _ = scene_array(scene, self.patch_embed.bands, batch_size)
+        pix = None if pixels is None else pixel_indices(pixels, H * W)
+        if pix is None and not by_p0:
+            pix = torch.arange(H * W, dtype=torch.int64, device=gpu_of(self))
+        return ScenePass(self, s, pix, self._scene_chunk(batch_size))
 
     def predict_scene(self, scene, pixels=None, batch_size=8192, return_logits=False, on_device=False):
         """Per-pixel classification map of a whole scene (what `test_model` computes from `data_cubes`, :268-283), from the
@@ -191,62 +184,23 @@ class DualViT(HSIMAE):
         for the encoder's workspace to fit SCENE_WORKSPACE_BUDGET bytes.
         -> int64 [H, W] map (CPU), and with return_logits=True also fp32 [n, num_class] logits (CPU) in pixel order.
         on_device=True: both stay on the model's device and nothing waits for the host."""
-        s, H, W, Cb, pix, dev, n_total, chunk = self._scene_args(scene, pixels, batch_size)
-        lib = _lib.load()
-        T, L = self.input_size[0], self.input_size[1] ** 2
+        sp = self._scene_pass(scene, pixels, batch_size, by_p0=True)
+        lib, H, W, dev = _lib.load(), sp.H, sp.W, sp.dev
         with torch.no_grad(), torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            s = s.to(dev).contiguous()
-            pix_d = None if pix is None else pix.to(dev)
             labels = torch.zeros(H * W, dtype=torch.int64, device=dev)
-            logits_all = torch.empty(n_total, self.num_class, dtype=torch.float32, device=dev) if return_logits else None
-            win, n1, n2 = self._scene_buffers(chunk, Cb, dev)
-            for k0 in range(0, n_total, chunk):
-                n = min(chunk, n_total - k0)
-                sp = _lib.SceneParams(scene=s.data_ptr(), scene_f64=int(s.dtype == torch.float64), H=H, W=W, C=Cb,
-                                      p0=k0 if pix_d is None else 0, pixels=None if pix_d is None else pix_d.data_ptr() + 8 * k0,
-                                      N=n, out=win.data_ptr(), sn=win.stride(0), sb=win.stride(2), sh=win.stride(3),
-                                      sw=win.stride(4))
-                _lib.check(lib.hsimae_scene_windows(C.byref(sp), stream), "hsimae_scene_windows")
-                _, _, _, st = self._run_forward(win[:n], 0.0, (n1[:n], n2[:n]), (T, L), want_latent=True, encoder_only=True)
+            logits_all = torch.empty(sp.n_total, self.num_class, dtype=torch.float32, device=dev) if return_logits else None
+            for k0, n in sp.chunks():
+                wp = sp.window_params(k0, n)
+                _lib.check(lib.hsimae_scene_windows(C.byref(wp), sp.stream), "hsimae_scene_windows")
+                st = sp.encode(n)
                 logits, _ = self.head(st["latent"])
                 st.release()
-                _lib.check(lib.hsimae_class_argmax(C.byref(sp), logits.data_ptr(), logits.stride(0), self.num_class, 1,
-                                                   labels.data_ptr(), stream), "hsimae_class_argmax")
+                _lib.check(lib.hsimae_class_argmax(C.byref(wp), logits.data_ptr(), logits.stride(0), self.num_class, 1,
+                                                   labels.data_ptr(), sp.stream), "hsimae_class_argmax")
                 if logits_all is not None:
                     logits_all[k0:k0 + n].copy_(logits)
-            out = labels.view(H, W) if on_device else labels.view(H, W).cpu()
-        if return_logits:
-            return out, (logits_all if on_device else logits_all.cpu())
-        return out
-
-    def _scene_args(self, scene, pixels, batch_size):
-        """The argument checks and the chunk size predict_scene and classify_scene share
-        -> (scene tensor, H, W, bands, pixel indices (CPU int64) or None, the model's device, pixel count, pixels per chunk)."""
-        s, H, W, Cb = scene_array(scene, self.patch_embed.bands, batch_size)
-        pix = None
-        if pixels is not None:
-            pix = torch.as_tensor(pixels).detach().cpu()
-            if pix.dim() != 1 or pix.dtype.is_floating_point or pix.dtype == torch.bool:
-                raise ValueError("pixels must be a 1-D array of integer pixel indices (r * W + c)")
-            pix = pix.to(torch.int64).contiguous()
-            if pix.numel() and (int(pix.min()) < 0 or int(pix.max()) >= H * W):
-                raise ValueError(f"pixel index out of range [0, {H * W}): min {int(pix.min())}, max {int(pix.max())}")
-        dev = self.cls_head.weight.device
-        if dev.type != "cuda":
-            raise RuntimeError("hsimae_amd runs on MI355X only (no CPU fallback): move the model to a GPU")
-        n_total = H * W if pix is None else pix.numel()
-        chunk = max(1, min(self._scene_chunk(batch_size), n_total))
-        return s, H, W, Cb, pix, dev, n_total, chunk
-
-    def _scene_buffers(self, chunk, Cb, dev):
-        """The encoder's input of one chunk, band-fastest as the reference's HSIdataset yields it ([chunk, 9, 9, C] viewed
-        [chunk, 1, C, 9, 9]), and the increasing noise that keeps every token in its place."""
-        T, L = self.input_size[0], self.input_size[1] ** 2
-        win = torch.empty(chunk, 9, 9, Cb, dtype=torch.float32, device=dev).permute(0, 3, 1, 2).unsqueeze(1)
-        n1 = torch.arange(T, dtype=torch.float32, device=dev).expand(chunk, T).contiguous()
-        n2 = torch.arange(L, dtype=torch.float32, device=dev).expand(chunk, L).contiguous()
-        return win, n1, n2
+            out, logits_all = to_host([labels.view(H, W), logits_all], on_device)
+        return (out, logits_all) if return_logits else out
 
     def classify_scene(self, scene, pixels=None, batch_size=8192, views=(0,), return_probs=False, on_device=False):
         """predict_scene with what a classifier's user asks for next: the class probabilities behind every label, averaged over
@@ -263,64 +217,38 @@ class DualViT(HSIMAE):
         order with return_probs=True, else None), on the CPU after one wait for the copies; on_device=True: all stay on the
         model's device and nothing waits for the host."""
         views = scene_views(views)
-        s, H, W, Cb, pix, dev, n_total, chunk = self._scene_args(scene, pixels, batch_size)
-        lib = _lib.load()
-        T, L, nc = self.input_size[0], self.input_size[1] ** 2, self.num_class
+        sp = self._scene_pass(scene, pixels, batch_size)
+        lib, nc, H, W, dev = _lib.load(), self.num_class, sp.H, sp.W, sp.dev
         with torch.no_grad(), torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            s = s.to(dev).contiguous()
-            items = torch.arange(H * W, dtype=torch.int64, device=dev) if pix is None else pix.to(dev)
-            labels = torch.zeros(H * W, dtype=torch.int64, device=dev)
-            conf = torch.zeros(H * W, dtype=torch.float32, device=dev)
-            margin = torch.zeros(H * W, dtype=torch.float32, device=dev)
-            probs = torch.empty(n_total, nc, dtype=torch.float32, device=dev) if return_probs else None
-            acc = torch.empty(chunk, nc, dtype=torch.float32, device=dev)      # the views' sum of one chunk (view 0 overwrites it)
-            flips = [torch.full((chunk,), v, dtype=torch.uint8, device=dev) for v in views]
-            bad = torch.zeros(1, dtype=torch.int32, device=dev)
-            win, n1, n2 = self._scene_buffers(chunk, Cb, dev)
-            for k0 in range(0, n_total, chunk):
-                n = min(chunk, n_total - k0)
+            labels, conf, margin, probs = self._scene_maps(sp, return_probs)
+            acc = torch.empty(sp.chunk, nc, dtype=torch.float32, device=dev)   # the views' sum of one chunk (view 0 overwrites it)
+            flips = [torch.full((sp.chunk,), v, dtype=torch.uint8, device=dev) for v in views]
+            for k0, n in sp.chunks():
                 for vi, fl in enumerate(flips):
-                    bp = _lib.SceneBatchParams(scene=s.data_ptr(), scene_f64=int(s.dtype == torch.float64), H=H, W=W, C=Cb,
-                                               items=items.data_ptr() + 8 * k0, N=n, n_items=H * W, flips=fl.data_ptr(),
-                                               out=win.data_ptr(), sn=win.stride(0), sb=win.stride(2), sh=win.stride(3),
-                                               sw=win.stride(4), bad=bad.data_ptr())
-                    _lib.check(lib.hsimae_scene_batch(C.byref(bp), stream), "hsimae_scene_batch")
-                    _, _, _, st = self._run_forward(win[:n], 0.0, (n1[:n], n2[:n]), (T, L), want_latent=True, encoder_only=True)
+                    sp.cut(k0, n, fl)
+                    st = sp.encode(n)
                     logits, _ = self.head(st["latent"])
                     st.release()
                     cp = _lib.ClassProbParams(logits=logits.data_ptr(), ld=logits.stride(0), N=n, C=nc, first=1, view=vi,
                                               n_views=len(views), acc=acc.data_ptr(), lda=nc, H=H, W=W,
-                                              pixels=items.data_ptr() + 8 * k0, label_map=labels.data_ptr(),
+                                              pixels=sp.items.data_ptr() + 8 * k0, label_map=labels.data_ptr(),
                                               conf_map=conf.data_ptr(), margin_map=margin.data_ptr(),
                                               probs=None if probs is None else probs.data_ptr() + 4 * nc * k0, ldp=nc)
-                    _lib.check(lib.hsimae_class_prob(C.byref(cp), stream), "hsimae_class_prob")
-            out = [labels.view(H, W), conf.view(H, W), margin.view(H, W), probs]
-            if not on_device:
-                out = [None if t is None else t.cpu() for t in out]
-                if int(bad.item()):                       # (the indices were checked on the host: this cannot happen)
-                    raise RuntimeError("classify_scene: a pixel index was outside the scene")
+                    _lib.check(lib.hsimae_class_prob(C.byref(cp), sp.stream), "hsimae_class_prob")
+            out = to_host([labels.view(H, W), conf.view(H, W), margin.view(H, W), probs], on_device)
+            if not on_device and int(sp.bad.item()):      # (the indices were checked on the host: this cannot happen)
+                raise RuntimeError("classify_scene: a pixel index was outside the scene")
         return SceneClassification(*out)
 
-    # ------------------------------------------------------------------ features of a scene, and their k-NN evaluation
-    def _scene_feature_rows(self, s, H, W, Cb, items, flips, bufs, out, bad):
-        """One chunk: the windows of the pixels `items` (device int64 [n]) flipped by `flips`, the unmasked encoder, and the
-        AGG pooling written into `out` (fp32 [n, T * D], contiguous rows of the caller's result).  The head GEMM is not run."""
-        lib = _lib.load()
-        T, L, D = self.input_size[0], self.input_size[1] ** 2, self.dim
-        n = int(items.shape[0])
-        win, n1, n2 = bufs
-        stream = torch.cuda.current_stream(s.device).cuda_stream
-        bp = _lib.SceneBatchParams(scene=s.data_ptr(), scene_f64=int(s.dtype == torch.float64), H=H, W=W, C=Cb,
-                                   items=items.data_ptr(), N=n, n_items=H * W, flips=flips.data_ptr(),
-                                   out=win.data_ptr(), sn=win.stride(0), sb=win.stride(2), sh=win.stride(3),
-                                   sw=win.stride(4), bad=bad.data_ptr())
-        _lib.check(lib.hsimae_scene_batch(C.byref(bp), stream), "hsimae_scene_batch")
-        _, _, _, st = self._run_forward(win[:n], 0.0, (n1[:n], n2[:n]), (T, L), want_latent=True, encoder_only=True)
-        lat = st["latent"].contiguous()
-        _lib.check(lib.hsimae_agg_pool(lat.data_ptr(), out.data_ptr(), n, T, L, D, stream), "hsimae_agg_pool")
-        st.release()
+    def _scene_maps(self, sp, want_probs):
+        """The device-resident results classify_scene and knn_scene fill: labels, confidence and margin per pixel of the scene (0
+        where not asked for), and with want_probs the [n, num_class] probabilities in pixel order."""
+        n_px, dev = sp.H * sp.W, sp.dev
+        return (torch.zeros(n_px, dtype=torch.int64, device=dev), torch.zeros(n_px, dtype=torch.float32, device=dev),
+                torch.zeros(n_px, dtype=torch.float32, device=dev),
+                torch.empty(sp.n_total, self.num_class, dtype=torch.float32, device=dev) if want_probs else None)
 
+    # ------------------------------------------------------------------ features of a scene, and their k-NN evaluation
     def scene_features(self, scene, pixels=None, batch_size=8192, flip=0, on_device=True):
         """The pooled encoder features of a scene's pixels: what `head()` feeds the classification layer, fp32 [n, T * D], rows in
         pixel order (row-major over the scene, or the order of `pixels`).  Per chunk, on the current stream: the windows flipped
@@ -329,19 +257,14 @@ class DualViT(HSIMAE):
         pretraining has no trained `cls_head`.  `scene`, `pixels`, `batch_size`, eval / no-grad behaviour: as predict_scene.
         on_device=True (the default): the result stays on the model's device and nothing waits for the host."""
         (flip,) = scene_views((flip,))
-        s, H, W, Cb, pix, dev, n_total, chunk = self._scene_args(scene, pixels, batch_size)
-        T, D = self.input_size[0], self.dim
-        with torch.no_grad(), torch.cuda.device(dev):
-            s = s.to(dev).contiguous()
-            items = torch.arange(H * W, dtype=torch.int64, device=dev) if pix is None else pix.to(dev)
-            feats = torch.empty(n_total, T * D, dtype=torch.float32, device=dev)
-            flips = torch.full((chunk,), flip, dtype=torch.uint8, device=dev)
-            bad = torch.zeros(1, dtype=torch.int32, device=dev)
-            bufs = self._scene_buffers(chunk, Cb, dev)
-            for k0 in range(0, n_total, chunk):
-                n = min(chunk, n_total - k0)
-                self._scene_feature_rows(s, H, W, Cb, items[k0:k0 + n], flips, bufs, feats[k0:k0 + n], bad)
-        return feats if on_device else feats.cpu()
+        sp = self._scene_pass(scene, pixels, batch_size)
+        with torch.no_grad(), torch.cuda.device(sp.dev):
+            feats = torch.empty(sp.n_total, sp.T * self.dim, dtype=torch.float32, device=sp.dev)
+            flips = torch.full((sp.chunk,), flip, dtype=torch.uint8, device=sp.dev)
+            for k0, n in sp.chunks():
+                sp.cut(k0, n, flips)
+                sp.pooled_into(feats[k0:k0 + n], n)
+        return to_host([feats], on_device)[0]
 
     KNN_GROUP_ROWS = 32768
 
@@ -358,42 +281,33 @@ class DualViT(HSIMAE):
         labels were checked.  The fitted classifier of the last call stays reachable as `self.last_knn` (its bank: `.bank`)."""
         from .knn import KNNClassifier
         bank_flips = scene_views(bank_flips)
-        s, H, W, Cb, pix, dev, n_total, chunk = self._scene_args(scene, pixels, batch_size)
-        nc = self.num_class
+        sp = self._scene_pass(scene, pixels, batch_size)   # its device scene is the one the bank's passes use too
+        H, W, n_total, dev = sp.H, sp.W, sp.n_total, sp.dev
         with torch.no_grad(), torch.cuda.device(dev):
-            s = s.to(dev).contiguous()
             y = torch.as_tensor(np.asarray(bank_labels) if not isinstance(bank_labels, torch.Tensor) else bank_labels)
             if y.dim() != 1 or y.dtype.is_floating_point or y.dtype == torch.bool:
                 raise ValueError("bank_labels must be a 1-D array of integer labels")
-            bank = [self.scene_features(s, bank_pixels, batch_size, flip=f, on_device=True) for f in bank_flips]
+            bank = [self.scene_features(sp.scene, bank_pixels, batch_size, flip=f, on_device=True) for f in bank_flips]
             if bank[0].shape[0] != y.numel():
                 raise ValueError(f"{y.numel()} labels for {bank[0].shape[0]} bank pixels")
-            knn = KNNClassifier(k=k, temperature=temperature, num_class=nc, first=1)
+            knn = KNNClassifier(k=k, temperature=temperature, num_class=self.num_class, first=1)
             knn.fit(bank[0] if len(bank) == 1 else torch.cat(bank), y.to(dev).repeat(len(bank_flips)))
             del bank
             self.last_knn = knn                            # the fitted classifier of the last call (its bank: knn.bank)
-            T, D = self.input_size[0], self.dim
-            items = torch.arange(H * W, dtype=torch.int64, device=dev) if pix is None else pix.to(dev)
-            labels = torch.zeros(H * W, dtype=torch.int64, device=dev)
-            conf = torch.zeros(H * W, dtype=torch.float32, device=dev)
-            margin = torch.zeros(H * W, dtype=torch.float32, device=dev)
-            probs = torch.empty(n_total, nc, dtype=torch.float32, device=dev) if return_probs else None
+            labels, conf, margin, probs = self._scene_maps(sp, return_probs)
             # the k-NN launches want more rows than one encoder chunk has (2,095 at Base: 33 workgroups of hsimae_knn_topk on 256
             # CUs): the features of whole chunks are collected up to KNN_GROUP_ROWS rows, then searched and voted on together
-            group = max(1, self.KNN_GROUP_ROWS // chunk) * chunk
-            feats = torch.empty(min(group, n_total), T * D, dtype=torch.float32, device=dev)
-            flips = torch.zeros(chunk, dtype=torch.uint8, device=dev)
-            bad = torch.zeros(1, dtype=torch.int32, device=dev)
-            bufs = self._scene_buffers(chunk, Cb, dev)
+            group = max(1, self.KNN_GROUP_ROWS // sp.chunk) * sp.chunk
+            feats = torch.empty(min(group, n_total), sp.T * self.dim, dtype=torch.float32, device=dev)
+            flips = torch.zeros(sp.chunk, dtype=torch.uint8, device=dev)
             for g0 in range(0, n_total, group):
                 gn = min(group, n_total - g0)
-                for k0 in range(g0, g0 + gn, chunk):
-                    n = min(chunk, g0 + gn - k0)
-                    self._scene_feature_rows(s, H, W, Cb, items[k0:k0 + n], flips, bufs, feats[k0 - g0:k0 - g0 + n], bad)
-                knn.predict_into(feats[:gn], H, W, items[g0:g0 + gn], labels, conf, margin, None if probs is None else probs[g0:g0 + gn])
-            out = [labels.view(H, W), conf.view(H, W), margin.view(H, W), probs]
+                for k0, n in sp.chunks(g0, g0 + gn):
+                    sp.cut(k0, n, flips)
+                    sp.pooled_into(feats[k0 - g0:k0 - g0 + n], n)
+                knn.predict_into(feats[:gn], H, W, sp.items[g0:g0 + gn], labels, conf, margin, None if probs is None else probs[g0:g0 + gn])
+            out = to_host([labels.view(H, W), conf.view(H, W), margin.view(H, W), probs], on_device)
             if not on_device:
-                out = [None if t is None else t.cpu() for t in out]
                 knn.check()
         return SceneClassification(*out)
 
@@ -420,35 +334,16 @@ class DualViT(HSIMAE):
             raise ValueError(f'features must be "encoder" or "spectra", got {features!r}')
         (flip,) = scene_views((flip,))
         metric = metric or ("cosine" if features == "encoder" else "euclidean")
-        def index(p, what, HW):
-            p = torch.as_tensor(p).detach().cpu()
-            if p.dim() != 1 or p.dtype.is_floating_point or p.dtype == torch.bool or not p.numel():
-                raise ValueError(f"{what} must be a non-empty 1-D array of integer pixel indices (r * W + c)")
-            p = p.to(torch.int64).contiguous()
-            if int(p.min()) < 0 or int(p.max()) >= HW:
-                raise ValueError(f"{what}: pixel index out of range [0, {HW})")
-            return p
-
-        if features == "encoder":
-            s, H, W, Cb, pix, dev, n_total, _ = self._scene_args(scene, pixels, batch_size)
-        else:                                              # the scene's own rows: any band count, the encoder is not run
-            s = scene if isinstance(scene, torch.Tensor) else torch.from_numpy(np.asarray(scene))
-            if s.dim() != 3 or s.dtype not in (torch.float32, torch.float64) or not s.numel():
-                raise ValueError(f"scene must be a non-empty float32 or float64 [H, W, C], got {tuple(s.shape)} {s.dtype}")
-            H, W, Cb = (int(v) for v in s.shape)
-            dev = self.cls_head.weight.device
-            if dev.type != "cuda":
-                raise RuntimeError("hsimae_amd runs on MI355X only (no CPU fallback): move the model to a GPU")
-            pix = None if pixels is None else index(pixels, "pixels", H * W)
-            n_total = H * W if pix is None else pix.numel()
-        fit_pix = None if fit_pixels is None else index(fit_pixels, "fit_pixels", H * W)
-        seed_pix = None
-        if not isinstance(init, str):
-            t = torch.as_tensor(init)
-            if t.dim() == 1:
-                seed_pix = index(t, "init", H * W)
-                if seed_pix.numel() != int(n_clusters):
-                    raise ValueError(f"init names {seed_pix.numel()} seed pixels for {n_clusters} clusters")
+        # the scene's own rows need no band count the encoder can take: it is not run
+        s = scene_array(scene, self.patch_embed.bands, batch_size)[0] if features == "encoder" else as_scene(scene)
+        H, W, Cb = (int(v) for v in s.shape)
+        seeds = init if not isinstance(init, str) and torch.as_tensor(init).dim() == 1 else None     # pixels that seed the centroids
+        pix, fit_pix, seed_pix = (None if p is None else pixel_indices(p, H * W, what, allow_empty=False)
+                                  for p, what in ((pixels, "pixels"), (fit_pixels, "fit_pixels"), (seeds, "init")))
+        n_total = H * W if pix is None else pix.numel()
+        if seed_pix is not None and seed_pix.numel() != int(n_clusters):
+            raise ValueError(f"init names {seed_pix.numel()} seed pixels for {n_clusters} clusters")
+        dev = gpu_of(self)
         with torch.no_grad(), torch.cuda.device(dev):
             s = s.to(dev).contiguous()
             if features == "spectra":
@@ -482,9 +377,8 @@ class DualViT(HSIMAE):
                     part = items[g0:g0 + group]
                     km.predict_into(feats(part), H, W, part.to(dev), labels, score, margin)
             self.last_kmeans = km
-            out = [labels.view(H, W), score.view(H, W), margin.view(H, W), km.centroids, km.counts, km.inertia_, km.n_iter_]
-            if not on_device:
-                out = [t.cpu() for t in out]
+            out = to_host([labels.view(H, W), score.view(H, W), margin.view(H, W), km.centroids, km.counts, km.inertia_, km.n_iter_],
+                          on_device)
         return SceneClustering(*out)
 
     # ------------------------------------------------------------------ stochastic depth (Models.py:235-263, 687-731)

@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .checkpoint import load_matching
 from .classify import ClassLoss, ScoreMeter
 from .colormap import save_label_png
 from .data import DeviceLoader
@@ -198,10 +199,7 @@ def _finetune(datasets, h, c, gt, save_dir, model_name, pretrained, lr, wd, dept
     save_path = os.path.join(save_dir, model_name.replace(".pkl", ""))
     os.makedirs(save_path, exist_ok=True)
     if pretrained:
-        model_dict = model.state_dict()
-        loaded = torch.load(pretrained, map_location=device)
-        model_dict.update({k: v for k, v in loaded.items() if k in model_dict})
-        model.load_state_dict(model_dict)
+        load_matching(model, pretrained, device, match_shapes=False).train()
 
     if optimizer not in ("adamw", "lamb"):
         raise ValueError(f'optimizer must be "adamw" or "lamb", got {optimizer!r}')
@@ -297,6 +295,12 @@ def _finetune(datasets, h, c, gt, save_dir, model_name, pretrained, lr, wd, dept
     return val_value, epoch_loss_list, val_loss_list
 
 
+def eval_vit(img_size, bands, n_class, dim, depth, s_depth, device):
+    """The evaluation model of the five wrappers below: the reference's HSIViT (Model_Finetuning.py:250-255) at these widths."""
+    return HSIViT(img_size=img_size, patch_size=3, in_chans=1, bands=bands, b_patch_size=8, num_class=n_class, embed_dim=dim,
+                  depth=depth, num_heads=dim // 16, s_depth=s_depth, sep_pos_embed=True, use_learnable_pos_emb=False).to(device)
+
+
 def test_model(data_cubes, test_gt, gt, save_dir, model_name, depth=12, dim=96, s_depth=6, device="cuda:0", save_images=False):
     """Model_Finetuning.test_model (:243-300): every cube of the scene through HSIViT loaded key-filtered from the
     fine-tuned checkpoint, class = 1 + argmax over logits[:, 1:], scores on the labeled test pixels.
@@ -305,13 +309,8 @@ def test_model(data_cubes, test_gt, gt, save_dir, model_name, depth=12, dim=96, 
     device = torch.device(device)
     h, w, c = data_cubes[0].shape
     n_class = int(np.max(gt) + 1)
-    model = HSIViT(img_size=h, patch_size=3, in_chans=1, bands=c, b_patch_size=8, num_class=n_class, embed_dim=dim, depth=depth,
-                   num_heads=dim // 16, s_depth=s_depth, sep_pos_embed=True, use_learnable_pos_emb=False).to(device)
-    model_dict = model.state_dict()
-    loaded = torch.load(os.path.join(save_dir, model_name), map_location=device)
-    model_dict.update({k: v for k, v in loaded.items() if k in model_dict})
-    model.load_state_dict(model_dict)
-    model.eval()
+    model = load_matching(eval_vit(h, c, n_class, dim, depth, s_depth, device), os.path.join(save_dir, model_name), device,
+                          match_shapes=False)
     dataset = HSIdataset(data_cubes, device=device)
     lib = _lib.load()
     n_total = len(dataset)
@@ -370,13 +369,8 @@ def test_model_scene(scene, test_gt, gt, save_dir, model_name, depth=12, dim=96,
         raise ValueError(f"scene must be [H, W, C], got shape {tuple(scene.shape)}")
     c = int(scene.shape[2])
     n_class = int(np.max(gt) + 1)
-    model = HSIViT(img_size=9, patch_size=3, in_chans=1, bands=c, b_patch_size=8, num_class=n_class, embed_dim=dim, depth=depth,
-                   num_heads=dim // 16, s_depth=s_depth, sep_pos_embed=True, use_learnable_pos_emb=False).to(device)
-    model_dict = model.state_dict()
-    loaded = torch.load(os.path.join(save_dir, model_name), map_location=device)
-    model_dict.update({k: v for k, v in loaded.items() if k in model_dict})
-    model.load_state_dict(model_dict)
-    model.eval()
+    model = load_matching(eval_vit(9, c, n_class, dim, depth, s_depth, device), os.path.join(save_dir, model_name), device,
+                          match_shapes=False)
     if views != (0,) or save_images:
         pred = model.classify_scene(scene, batch_size=batch_size, views=views, on_device=True).labels
     else:
@@ -402,13 +396,7 @@ def knn_eval_scene(scene, train_index, train_labels, test_gt, gt, pretrained, de
         raise ValueError("save_images=True needs save_dir")
     c = int(scene.shape[2])
     n_class = int(np.max(gt) + 1)
-    model = HSIViT(img_size=9, patch_size=3, in_chans=1, bands=c, b_patch_size=8, num_class=n_class, embed_dim=dim, depth=depth,
-                   num_heads=dim // 16, s_depth=s_depth, sep_pos_embed=True, use_learnable_pos_emb=False).to(device)
-    model_dict = model.state_dict()
-    loaded = torch.load(pretrained, map_location=device)
-    model_dict.update({k_: v for k_, v in loaded.items() if k_ in model_dict and v.shape == model_dict[k_].shape})
-    model.load_state_dict(model_dict)
-    model.eval()
+    model = load_matching(eval_vit(9, c, n_class, dim, depth, s_depth, device), pretrained, device, match_shapes=True)
     pred = model.knn_scene(scene, train_index, train_labels, k=k, temperature=temperature, bank_flips=bank_flips,
                            batch_size=batch_size, on_device=True).labels
     name = os.path.basename(str(pretrained)) if model_name is None else model_name
@@ -455,14 +443,9 @@ def cluster_eval_scene(scene, gt, pretrained, n_clusters=None, depth=12, dim=96,
             raise ValueError(f"save_images=True: label {n_class - 1} is outside the palette's {PALETTE.shape[0]} colours")
     c = int(scene.shape[2])
     bands = c if features == "encoder" else 32                 # (the spectra path never runs the encoder)
-    model = HSIViT(img_size=9, patch_size=3, in_chans=1, bands=bands, b_patch_size=8, num_class=n_class, embed_dim=dim, depth=depth,
-                   num_heads=dim // 16, s_depth=s_depth, sep_pos_embed=True, use_learnable_pos_emb=False).to(device)
+    model = eval_vit(9, bands, n_class, dim, depth, s_depth, device).eval()
     if pretrained is not None and features == "encoder":
-        model_dict = model.state_dict()
-        loaded = torch.load(pretrained, map_location=device)
-        model_dict.update({k_: v for k_, v in loaded.items() if k_ in model_dict and v.shape == model_dict[k_].shape})
-        model.load_state_dict(model_dict)
-    model.eval()
+        load_matching(model, pretrained, device, match_shapes=True)
     raw = model.cluster_scene(scene, K, fit_pixels=fit_pixels, features=features, metric=metric, flip=flip, max_iter=max_iter,
                               n_init=n_init, generator=generator, batch_size=batch_size, on_device=True, init=init).labels
     meter = ScoreMeter(max(K, n_class - 1) + 1, device)

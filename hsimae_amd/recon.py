@@ -17,7 +17,9 @@ import numpy as np
 import torch
 
 from . import _lib
+from .checkpoint import load_matching
 from .finetune import DualViT, scene_array
+from .scene_pass import ScenePass, gpu_of, largest_chunk, to_host
 
 SceneReconstruction = collections.namedtuple(
     "SceneReconstruction", ["recon", "count", "cover", "rmse", "sam", "loss", "mse", "psnr", "mean_sam", "coverage"])
@@ -47,21 +49,9 @@ def _centres_on(dev, length, stride, count):
 
 
 def _recon_chunk(model, mask_ratio, batch_size, n_windows):
-    """The largest n <= batch_size whose hsimae_workspace_bytes fits DualViT.SCENE_WORKSPACE_BUDGET at the worst grid the pass
-    may draw (at least 1)."""
-    lib, cfg = _lib.load(), model._config()
-    T, L = model.input_size[0], model.input_size[1] ** 2
-    best = max(1, min(int(batch_size), int(n_windows)))
-    for len_t, len_l in model.grid_candidates(T, L, mask_ratio):
-        lo, hi = 1, best
-        while lo < hi:
-            mid = (lo + hi + 1) // 2
-            if 0 <= lib.hsimae_workspace_bytes(C.byref(cfg), mid, len_t, len_l) <= DualViT.SCENE_WORKSPACE_BUDGET:
-                lo = mid
-            else:
-                hi = mid - 1
-        best = lo
-    return best
+    """The largest n <= min(batch_size, n_windows) whose workspace fits DualViT.SCENE_WORKSPACE_BUDGET at every grid the pass may draw."""
+    grids = model.grid_candidates(model.input_size[0], model.input_size[1] ** 2, mask_ratio)
+    return largest_chunk(_lib.load(), model._config(), grids, batch_size, DualViT.SCENE_WORKSPACE_BUDGET, cap=n_windows)
 
 
 def reconstruct_scene(model, scene, mask_ratio=0.75, stride=9, passes=1, generator=None, batch_size=4096, return_recon=True,
@@ -91,39 +81,29 @@ def reconstruct_scene(model, scene, mask_ratio=0.75, stride=9, passes=1, generat
         raise ValueError("reconstruct_scene needs a model with a decoder")
     s, H, W, Cb = scene_array(scene, model.patch_embed.bands, batch_size)
     rows, cols = window_centres(H, stride), window_centres(W, stride)
-    dev = next(model.parameters()).device
-    if dev.type != "cuda":
-        raise RuntimeError("hsimae_amd runs on MI355X only (no CPU fallback): move the model to a GPU")
+    dev = gpu_of(model)
     lib = _lib.load()
     T, L = model.input_size[0], model.input_size[1] ** 2
     nrows, ncols = len(rows), len(cols)
     n_win = nrows * ncols
-    chunk = _recon_chunk(model, mask_ratio, batch_size, n_win)
     was = model.want_recons
     model.want_recons = True
     try:
         with torch.no_grad(), torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            s = s.to(dev).contiguous()
             rows_d, cols_d = _centres_on(dev, H, stride, nrows), _centres_on(dev, W, stride, ncols)
             items = (rows_d.to(torch.int64)[:, None] * W + cols_d.to(torch.int64)[None, :]).reshape(-1).contiguous()
+            sp = ScenePass(model, s, items, _recon_chunk(model, mask_ratio, batch_size, n_win))
+            s, stream = sp.scene, sp.stream
             acc = torch.zeros(H, W, Cb, dtype=torch.float32, device=dev)
             cnt = torch.zeros(H, W, Cb, dtype=torch.int32, device=dev)
-            bad = torch.zeros(1, dtype=torch.int32, device=dev)
             loss_sum = torch.zeros((), dtype=torch.float64, device=dev)
-            win = torch.empty(chunk, 9, 9, Cb, dtype=torch.float32, device=dev).permute(0, 3, 1, 2).unsqueeze(1)
             for _ in range(passes):
                 grid = model.get_dim_patches(T, L, mask_ratio)
-                for w0 in range(0, n_win, chunk):
-                    n = min(chunk, n_win - w0)
-                    bp = _lib.SceneBatchParams(scene=s.data_ptr(), scene_f64=int(s.dtype == torch.float64), H=H, W=W, C=Cb,
-                                               items=items.data_ptr() + 8 * w0, N=n, n_items=H * W, out=win.data_ptr(),
-                                               sn=win.stride(0), sb=win.stride(2), sh=win.stride(3), sw=win.stride(4),
-                                               bad=bad.data_ptr())
-                    _lib.check(lib.hsimae_scene_batch(C.byref(bp), stream), "hsimae_scene_batch")
+                for w0, n in sp.chunks():
+                    win = sp.cut(w0, n)
                     n1 = torch.rand(n, T, device=dev, generator=generator)
                     n2 = torch.rand(n, L, device=dev, generator=generator)
-                    loss, pred_img, mask_img, st = model._run_forward(win[:n], mask_ratio, (n1, n2), grid, want_latent=False)
+                    loss, pred_img, mask_img, st = model._run_forward(win, mask_ratio, (n1, n2), grid, want_latent=False)
                     st.release()
                     ap = _lib.ReconAccumulateParams(pred_img=pred_img.data_ptr(), mask_img=mask_img.data_ptr(), n=n, w0=w0,
                                                     rows=rows_d.data_ptr(), nrows=nrows, cols=cols_d.data_ptr(), ncols=ncols,
@@ -141,9 +121,8 @@ def reconstruct_scene(model, scene, mask_ratio=0.75, stride=9, passes=1, generat
                                         rmse=rmse.data_ptr(), sam=sam.data_ptr(), partials=partials.data_ptr(),
                                         stats=stats.data_ptr())
             _lib.check(lib.hsimae_recon_finish(C.byref(fp), stream), "hsimae_recon_finish")
-            out = [recon, cnt, cover, rmse, sam, (loss_sum / (passes * n_win)).float()] + scene_scalars(stats, s, H * W * Cb)
-            if not on_device:
-                out = [None if t is None else t.cpu() for t in out]
+            out = to_host([recon, cnt, cover, rmse, sam, (loss_sum / (passes * n_win)).float()] + scene_scalars(stats, s, H * W * Cb),
+                          on_device)
     finally:
         model.want_recons = was
     return SceneReconstruction(*out)
@@ -170,11 +149,7 @@ def recon_eval_scene(scene, pretrained, depth=12, dim=64, s_depth=6, dec_depth=2
     model = HSIMAE(img_size=9, patch_size=3, in_chans=1, bands=int(scene.shape[2]), b_patch_size=8, embed_dim=dim, depth=depth,
                    num_heads=dim // 16, s_depth=s_depth, decoder_embed_dim=dec_dim, decoder_depth=dec_depth,
                    decoder_num_heads=dec_dim // 8, norm_pix_loss=True, trunc_init=True).to(device)
-    model_dict = model.state_dict()
-    loaded = torch.load(pretrained, map_location=device)
-    model_dict.update({k: v for k, v in loaded.items() if k in model_dict and v.shape == model_dict[k].shape})
-    model.load_state_dict(model_dict)
-    model.eval()
+    load_matching(model, pretrained, device, match_shapes=True)
     random.seed(seed)
     gen = torch.Generator(device=device)
     gen.manual_seed(int(seed))

@@ -19,8 +19,7 @@ import torch
 
 from . import _lib
 from .data import draw_flips
-
-PATCH = 9
+from .scene_pass import PATCH, as_scene, batch_params, window_buffer
 
 
 def tile_origins(length: int, size: int = PATCH) -> np.ndarray:
@@ -118,20 +117,6 @@ def get_scene_set_dual(data, gt, patch_size=9, percent=None, num=None, mask=None
     return train_index, train_labels, scene, test_gt, gt_raw
 
 
-def _as_hwc(scene) -> torch.Tensor:
-    if isinstance(scene, torch.Tensor):
-        s = scene.detach()
-    else:
-        s = torch.from_numpy(np.ascontiguousarray(np.asarray(scene)))
-    if s.dim() != 3:
-        raise ValueError(f"scene must be [H, W, C], got shape {tuple(s.shape)}")
-    if s.dtype not in (torch.float32, torch.float64):
-        raise ValueError(f"scene must be float32 or float64, got {s.dtype}")
-    if min(s.shape) <= 0:
-        raise ValueError(f"empty scene {tuple(s.shape)}")
-    return s
-
-
 def _resident(s: torch.Tensor, device) -> torch.Tensor:
     if s.device.type != "cuda":
         device = torch.device(device)
@@ -144,7 +129,7 @@ def _resident(s: torch.Tensor, device) -> torch.Tensor:
 def device_scene(scene, device="cuda:0") -> torch.Tensor:
     """The [H, W, C] fp32 / fp64 scene as a contiguous device tensor: a contiguous device tensor is used as it is (shared, not
     copied, whatever `device` says); anything else is uploaded to `device` once."""
-    return _resident(_as_hwc(scene), device)
+    return _resident(as_scene(scene), device)
 
 
 class SceneCubes:
@@ -154,7 +139,7 @@ class SceneCubes:
     checked on the host and uploaded once; every batch is one hsimae_scene_batch launch."""
 
     def __init__(self, scene, pixels=None, gt=None, train=False, device="cuda:0"):
-        s = _as_hwc(scene)
+        s = as_scene(scene)
         H, W, Cb = (int(v) for v in s.shape)
         pix = None
         if pixels is not None:
@@ -193,13 +178,9 @@ class SceneCubes:
         fl = None if flips is None else torch.as_tensor(np.asarray(flips, dtype=np.uint8)).to(self.device)
         if fl is not None and fl.numel() != n:
             raise ValueError(f"{fl.numel()} flip bytes for {n} items")
-        Cb = self.bands
-        out = torch.empty(n, PATCH, PATCH, Cb, dtype=torch.float32, device=self.device).permute(0, 3, 1, 2).unsqueeze(1)
+        out = window_buffer(n, self.bands, self.device)
         y = None if self._y is None else torch.empty(n, dtype=torch.int64, device=self.device)
-        p = _lib.SceneBatchParams(scene=self.scene.data_ptr(), scene_f64=int(self.scene.dtype == torch.float64), H=self.H, W=self.W,
-                                  C=Cb, items=idx.data_ptr(), N=n, n_items=self._n, pixels=_lib.ptr(self._pix),
-                                  labels=_lib.ptr(self._y), flips=_lib.ptr(fl), out=out.data_ptr(), sn=out.stride(0),
-                                  sb=out.stride(2), sh=out.stride(3), sw=out.stride(4), y=_lib.ptr(y), bad=self._bad.data_ptr())
+        p = batch_params(self.scene, out, idx.data_ptr(), n, self._n, self._bad, flips=fl, pixels=self._pix, labels=self._y, y=y)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
             _lib.check(_lib.load().hsimae_scene_batch(C.byref(p), stream), "hsimae_scene_batch")

@@ -9,7 +9,6 @@ every leg in a fresh process, the legs alternating.
 """
 import argparse
 import contextlib
-import ctypes as C
 import io
 import json
 import os
@@ -42,36 +41,29 @@ def eager_scene(m, scene, stride, gen):
     """reconstruct_scene's loop with the way back in eager torch: the same windows, forward and noise; then per chunk one
     index_put_(accumulate=True) each for sums and counts over the un-reflected masked positions, and at the end the division,
     three reductions per pixel and acos.  -> (mse, mean_sam, coverage) as device scalars."""
-    from hsimae_amd import _lib, window_centres
+    from hsimae_amd import window_centres
     from hsimae_amd.recon import _recon_chunk
-    lib = _lib.load()
+    from hsimae_amd.scene_pass import ScenePass
     dev = torch.device("cuda")
     s = torch.from_numpy(scene).to(dev) if not isinstance(scene, torch.Tensor) else scene
     rows = torch.from_numpy(window_centres(H, stride)).to(dev).long()
     cols = torch.from_numpy(window_centres(W, stride)).to(dev).long()
     items = (rows[:, None] * W + cols[None, :]).reshape(-1).contiguous()
     n_win = items.numel()
-    chunk = _recon_chunk(m, RATIO, CHUNK, n_win)
+    sp = ScenePass(m, s, items, _recon_chunk(m, RATIO, CHUNK, n_win))
     T, L = m.input_size[0], m.input_size[1] ** 2
     acc = torch.zeros(H * W * BANDS, dtype=torch.float32, device=dev)
     cnt = torch.zeros(H * W * BANDS, dtype=torch.float32, device=dev)
-    bad = torch.zeros(1, dtype=torch.int32, device=dev)
-    win = torch.empty(chunk, 9, 9, BANDS, dtype=torch.float32, device=dev).permute(0, 3, 1, 2).unsqueeze(1)
     off = torch.arange(9, device=dev) - 4
     band = torch.arange(BANDS, device=dev)
-    stream = torch.cuda.current_stream().cuda_stream
     m.want_recons = True
     with torch.no_grad():
         grid = m.get_dim_patches(T, L, RATIO)
-        for w0 in range(0, n_win, chunk):
-            n = min(chunk, n_win - w0)
-            bp = _lib.SceneBatchParams(scene=s.data_ptr(), scene_f64=int(s.dtype == torch.float64), H=H, W=W, C=BANDS,
-                                       items=items.data_ptr() + 8 * w0, N=n, n_items=H * W, out=win.data_ptr(), sn=win.stride(0),
-                                       sb=win.stride(2), sh=win.stride(3), sw=win.stride(4), bad=bad.data_ptr())
-            _lib.check(lib.hsimae_scene_batch(C.byref(bp), stream), "hsimae_scene_batch")
+        for w0, n in sp.chunks():
+            win = sp.cut(w0, n)
             n1 = torch.rand(n, T, device=dev, generator=gen)
             n2 = torch.rand(n, L, device=dev, generator=gen)
-            _, pred, mask, st = m._run_forward(win[:n], RATIO, (n1, n2), grid, want_latent=False)
+            _, pred, mask, st = m._run_forward(win, RATIO, (n1, n2), grid, want_latent=False)
             st.release()
             it = items[w0:w0 + n]
             r = (it // W)[:, None] + off[None, :]                                        # [n, 9]

@@ -161,6 +161,36 @@ def test_predict_scene_is_chunk_invariant():
     assert torch.equal(la.reshape(-1)[clear], lb.reshape(-1)[clear])
 
 
+def test_scene_pass_handles_a_one_pixel_chunk_tail():
+    """50 pixels in chunks of 7: seven whole chunks and a last one of a single pixel (ScenePass.chunks).  A chunk of one and a
+    call of one launch the same shapes, so the tail's rows equal the same call made on that pixel alone, bit for bit."""
+    m = tiny_hsivit(seed=3)
+    scene = torch.from_numpy(scene_23x19(seed=7)).cuda()
+    pix = torch.randperm(23 * 19, generator=torch.Generator().manual_seed(8))[:50]
+    assert m._scene_chunk(7) == 7 and pix.numel() % 7 == 1
+    rest = torch.ones(23 * 19, dtype=torch.bool)
+    rest[pix] = False
+
+    feats = m.scene_features(scene, pix, batch_size=7).cpu()
+    assert feats.shape == (50, 4 * 32) and torch.isfinite(feats).all()
+    assert torch.equal(feats[49:], m.scene_features(scene, pix[49:], batch_size=7).cpu())
+
+    got = m.classify_scene(scene, pix, batch_size=7, views=(0, 3), return_probs=True)      # on_device=False: raises if `bad` is set
+    one = m.classify_scene(scene, pix[49:], batch_size=7, views=(0, 3), return_probs=True)
+    assert got.probs.shape == (50, 7) and torch.equal(got.probs[49:], one.probs)
+    for a, b in zip(got[:3], one[:3]):                                  # labels, confidence, margin of that pixel
+        assert a.shape == (23, 19) and torch.equal(a.reshape(-1)[pix[49:]], b.reshape(-1)[pix[49:]])
+        assert torch.isfinite(a.double()).all() and (a.reshape(-1)[rest] == 0).all()
+        assert (b.reshape(-1)[torch.arange(23 * 19) != pix[49]] == 0).all()
+    assert torch.isfinite(got.probs).all() and (got.labels.reshape(-1)[pix] >= 1).all()
+
+    bank = pix[:20]
+    knn = m.knn_scene(scene, bank, 1 + torch.arange(20) % 6, pixels=pix, k=5, batch_size=7, return_probs=True, on_device=True)
+    m.last_knn.check()                                                  # no index outside the bank, no bad label
+    assert torch.isfinite(knn.probs).all() and (knn.labels.reshape(-1).cpu()[rest] == 0).all()
+    assert (knn.labels.reshape(-1).cpu()[pix] >= 1).all()
+
+
 def test_predict_scene_base_width_against_oracle():
     from hsimae_amd import HSIViT
     cfg = O.OracleConfig(bands=32)
