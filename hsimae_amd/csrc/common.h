@@ -157,10 +157,14 @@ __device__ __forceinline__ const T* launder(const T* p) {
 // a * sigmoid(a) with the reciprocal taken as v_rcp_f32 + one Newton step (<= 1 ulp): the forward kernels' SiLU.
 // A plain v_rcp (1 ulp, biased) moved the loss by 1e-4 at stress weights; IEEE division costs ~10 VALU slots per
 // element (scale / fmas / fixup), which made the gate the largest VALU item of the fused forward kernels.
+// Below a = -88.72 __expf(-a) is +inf: d = inf, r = 0 and the Newton residual fma(-inf, 0, 1) is NaN, where a * sigmoid(a) is -0.
+// fminf returns its other operand for a NaN (one v_min_f32): the residual becomes 1, the step leaves r = fma(1, 0, 0) = 0 and the
+// result is a * 0 for every finite a.  Everywhere else the residual is a few 2^-24 and the min does not change it.  (Clamping the
+// exponent's argument costs the same instruction but leaves r = e^-88, not 0: a * r is then wrong for |a| beyond ~1e10.)
 __device__ __forceinline__ float silu_nr(float a) {
     const float d = 1.f + __expf(-a);
     float r = __builtin_amdgcn_rcpf(d);
-    r = fmaf(fmaf(-d, r, 1.f), r, r);
+    r = fmaf(fminf(fmaf(-d, r, 1.f), 1.f), r, r);
     return a * r;
 }
 

@@ -262,11 +262,17 @@ typedef struct {
 } hsimae_pack_desc;
 int hsimae_pack_matrix(const hsimae_pack_desc* desc_dev, int32_t ndesc, int32_t max_elems, void* stream);
 
-/* MLP half of an encoder Block in one kernel each way (Models.py:305 `x + mlp(norm2(x))`, SwiGLU :231-232), d = 128 with
- * hidden width padded to 352 (Base): forward  x2 = x1 + rowscale * (b2 + (silu(u2 W1^T + b1) * (u2 W3^T + b3)) W2^T) (+ res2),
- * u2 = LN2(x1); backward recomputes u2 / h1 / h3 and writes dx1 (fp32) plus the bf16 operands of the block's weight
- * gradients: u2, dh1|dh3 [M, 2*352], g [M, 352], dY and dx1 copies; LayerNorm-2 parameter grads are accumulated.
- * Weight images as produced by hsimae_pack_params (w13T = W1^T | W3^T along K).  rs_mlp / rs_attn: DropPath row factors. */
+/* MLP half of an encoder Block in one kernel each way (Models.py:305 `x + mlp(norm2(x))`, SwiGLU :231-232):
+ * forward  x2 = x1 + rowscale * (b2 + (silu(u2 W1^T + b1) * (u2 W3^T + b3)) W2^T) (+ res2), u2 = LN2(x1); backward recomputes
+ * u2 / h1 / h3 and writes dx1 (fp32) plus the bf16 operands of the block's weight gradients: u2, dh1|dh3 [M, 2 hp], g [M, hp]
+ * (columns [hidden, hp) are zeros), dY and dx1 copies; LayerNorm-2 parameter grads are accumulated onto g_n2w / g_n2b.
+ * Accepted (d, hp), hp = hidden rounded up to 32: (128, 352) Base, (256, 704) Large, (64, 192) the decoder width, i.e. hidden in
+ * (hp - 32, hp]; anything else is HSIMAE_EUNSUPPORTED.  w1b / w3b are read below `hidden` only.
+ * Weight images as produced by hsimae_pack_params (w13T = W1^T | W3^T along K, W3^T at k = hp).  rowscale / rs_mlp / rs_attn:
+ * DropPath row factors (NULL = 1): dyb = bf16(rs_mlp dY), dx1b = bf16(rs_attn dx1), dx1 itself carries neither.
+ * Optional outputs of the backward, each NULL or passed as a whole: {u2, dyb}, {dh13, g}, dx1b; dx1 does not depend on them.
+ * Returns: M <= 0: HSIMAE_OK, nothing touched.  HSIMAE_ENULL: x1 / x2 / w (forward), x1 / dy / dx1 / w / g_n2w / g_n2b
+ * (backward) NULL, or one of {u2, dyb} / {dh13, g} without the other.  HSIMAE_EDIMS: 0 < plane_rows < M. */
 typedef struct {
     const float* n2w; const float* n2b; const float* w1b; const float* w3b; const float* w2b;
     const hs_bf16* w1; const hs_bf16* w3; const hs_bf16* w2; const hs_bf16* w2T; const hs_bf16* w13T;

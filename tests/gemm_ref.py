@@ -32,6 +32,9 @@ C1_F8 = 2048.0
 C2 = 4.0
 # LayerNorm statistics in fp32 (a tree sum over the row, x - mean, rsqrt): relative to (1 + kappa), kappa = rstd * mean|x|.
 C_LN = 16.0
+# __expf / v_rcp_f32 in the SiLU epilogues and the fused MLP kernels: relative error of silu and its derivative factors, on top of
+# the bf16 rounding of the result (tests/test_gpu_gemm.py, tests/mlp_ref.py)
+EPS_FN = 2.0 ** -18
 
 
 # ------------------------------------------------------------------------------------------------ the dispatch rule
@@ -152,15 +155,19 @@ def ln64(x, gamma, beta, width=None, eps=1e-5, unbiased=False):
     return y, xh, rstd, kappa
 
 
-def ln_out_bound(y64, xhat, kappa, gamma, beta, width=None):
-    """Bound for the bf16 LayerNorm output (u_out) against ln64: one bf16 rounding plus the fp32 statistics' error."""
-    K = y64.shape[1]
+def ln_stat_bound(xhat, kappa, gamma, beta, width=None):
+    """The statistics part of ln_out_bound: the error of the fp32 LayerNorm value before it is rounded to bf16."""
+    K = xhat.shape[1]
     w = K if not width else width
-    g = torch.zeros(K, dtype=torch.float64, device=y64.device)
+    g = torch.zeros(K, dtype=torch.float64, device=xhat.device)
     b = torch.zeros_like(g)
     g[:w], b[:w] = gamma[:w].double().abs(), beta[:w].double().abs()
-    stat = C_LN * U * (1 + kappa) * g * (xhat.abs() + 1) + C2 * U * b
-    return UB * y64.abs() + (1 + UB) * stat
+    return C_LN * U * (1 + kappa) * g * (xhat.abs() + 1) + C2 * U * b
+
+
+def ln_out_bound(y64, xhat, kappa, gamma, beta, width=None):
+    """Bound for the bf16 LayerNorm output (u_out) against ln64: one bf16 rounding plus the fp32 statistics' error."""
+    return UB * y64.abs() + (1 + UB) * ln_stat_bound(xhat, kappa, gamma, beta, width)
 
 
 def ln_bwd64(du, x, gamma, width):

@@ -27,7 +27,7 @@ EB, EF, ER, EP, ES, ESB, ELB = (_lib.E_BF16, _lib.E_F32, _lib.E_RES_F32, _lib.E_
 BF16, FP8 = _lib.PREC_BF16, _lib.PREC_FP8
 OK, EDIMS, EUNSUP, ENULL = 0, -1, -2, -4
 GUARD_ROWS = 3
-EPS_FN = 2.0 ** -18        # __expf / rcp in the SiLU epilogues (relative, on top of the bf16 rounding of the result)
+EPS_FN = R.EPS_FN           # __expf / rcp in the SiLU epilogues (relative, on top of the bf16 rounding of the result)
 
 from gemm_ref import F8_PLAIN, PLAIN, TABLE, expected, inst_name  # noqa: E402  (the dispatch rule: shared with the CPU test of plan_gemm)
 
@@ -168,9 +168,9 @@ def a_rows(M, K, ld, dtype, seed, fp8):
 
 
 # ------------------------------------------------------------------------------------------------ the matrix
-def run_case(case, M, seed, rowscale=False, res2=True, ln_width=0):
+def run_case(case, M, seed, rowscale=False, res2=True, ln_width=0, extreme_bias=False):
     """Launch one case with canaries; returns (inputs, outputs) for the checks.  rowscale: DropPath factors (a_rowscale on
-    A_F32 operands, out_rowscale in E_RES_F32)."""
+    A_F32 operands, out_rowscale in E_RES_F32).  extreme_bias: every 7th bias entry at -1000 / +1000."""
     ak, epi, prec, N, nv, K, bm, kc = case
     fp8 = prec == FP8
     g = torch.Generator(device=DEV).manual_seed(seed + 1)
@@ -183,6 +183,8 @@ def run_case(case, M, seed, rowscale=False, res2=True, ln_width=0):
     W2 = torch.randn(N, K, device=DEV, generator=g) * 0.1 - 0.01
     bias = torch.randn(N, device=DEV, generator=g) * 0.3
     bias2 = torch.randn(N, device=DEV, generator=g) * 0.3
+    if extreme_bias:
+        bias[3::7], bias[5::7] = -1000.0, 1000.0
     kw = dict(A=A, lda=lda, M=M, N=N, K=K, n_valid=nv, ldo=ldo, prec=prec)
     if fp8:
         kw["W8"], kw["S8"] = pack8(W, N, K)
@@ -380,6 +382,19 @@ def test_layernorm_fp8(case):
         if epi == EB:
             assert bool((out[:M, nv:N].float() == 0).all())
         untouched(out, canary[0], col_mask(M + GUARD_ROWS, out.shape[1], [(0, nv if epi == EF else N)], M), "out")
+
+
+def test_swiglu_extreme_preactivations():
+    """E_SWIGLU with gate pre-activations near -1000 and +1000 (through the bias): below -88.72 the exponential of the forward
+    SiLU overflows.  The gate must be finite and inside the usual check on the kernel's own h13.  (At -1000 sigmoid is 0 in
+    float64 as well; between -88.72 and -745 the reference is a number below bf16's range that the relative check cannot admit.)"""
+    case = (LN, ES, BF16, 272, 267, 256, 0, 0)
+    for i, M in enumerate((65, 333)):
+        inp, canary = run_case(case, M, seed=41 + i, extreme_bias=True)
+        h1 = inp["h13"][:M, :267].float()
+        assert float(h1.min()) < -900 and float(h1.max()) > 900
+        assert bool(torch.isfinite(inp["out"][:M, :272].float()).all()), "E_SWIGLU: the gate is not finite"
+        check_case(case, inp, canary)
 
 
 @pytest.mark.parametrize("prec", [BF16, FP8])

@@ -219,7 +219,8 @@ def test_gemm_swiglu_forward_and_backward_epilogues(d, h):
 def test_fused_encoder_mlp_half_forward_backward(M, drop):
     """hsimae_enc_mlp_fwd / hsimae_enc_mlp_bwd (one kernel each way, Base width) against a plain PyTorch fp32
     restatement of `x + rs * mlp(norm2(x))` (Models.py:305, 231-232) and its autograd, ragged row counts, optional
-    DropPath row factors; also the bf16 weight-gradient operands the backward emits."""
+    DropPath row factors; also the bf16 weight-gradient operands the backward emits.
+    (tests/test_gpu_mlp.py holds every instantiation of these kernels element by element to a float64 reference.)"""
     torch.manual_seed(6)
     d, h = 128, 344
     hp = rup(h, 32)
@@ -448,6 +449,48 @@ def test_fused_decoder_block_forward_backward(N, Ts, split, slab):
             continue
         e = float((G_[n].double() - ref[n].double()).pow(2).mean().sqrt() / ref[n].double().pow(2).mean().sqrt().clamp_min(1e-30))
         assert e < 2.5e-2, (n, e)
+
+
+@pytest.mark.parametrize("split", [1, 0])
+def test_fused_decoder_block_forward_extreme_gate_preactivations(split):
+    """Forward only, N = 2, Ts = 17: some rows of w1 scaled until the gate pre-activation passes -95 and +95 (below -88.72 the
+    exponential of the forward SiLU overflows).  x2 stays finite and within the gate of the test above."""
+    torch.manual_seed(5)
+    N, Ts, d, heads, h = 2, 17, 64, 8, 172
+    hp, M = rup(h, 32), N * Ts
+    x = torch.randn(M, d, device=DEV)
+    P = {k: torch.randn(d, d, device=DEV) * 0.15 for k in ("q", "k", "v", "p")}
+    P.update(w1=torch.randn(h, d, device=DEV) * 0.12, w3=torch.randn(h, d, device=DEV) * 0.12, w2=torch.randn(d, h, device=DEV) * 0.1)
+    P["w1"][3:40:4] *= 60.0
+    B = {k: torch.randn(n, device=DEV) * 0.1 for k, n in (("q", d), ("k", d), ("v", d), ("p", d), ("w1", h), ("w3", h), ("w2", d))}
+    n1w, n1b, n2w, n2b = (1 + 0.1 * torch.randn(d, device=DEV), 0.1 * torch.randn(d, device=DEV),
+                          1 + 0.1 * torch.randn(d, device=DEV), 0.1 * torch.randn(d, device=DEV))
+    imgs = [pack([(P["q"], 0, 0, 0), (P["k"], 0, d, 0), (P["v"], 0, 2 * d, 0)], 3 * d, d), pack([(P["p"], 0, 0, 0)], d, d),
+            pack([(P["w1"], 0, 0, 0)], hp, d), pack([(P["w3"], 0, 0, 0)], hp, d), pack([(P["w2"], 0, 0, 0)], d, hp), pack([(P["w2"], 1, 0, 0)], hp, d)]
+    bqkv = torch.cat([B["q"], B["k"], B["v"]]).contiguous()
+    W = _lib.DecBlockWeights(n1w=n1w.data_ptr(), n1b=n1b.data_ptr(), bqkv=bqkv.data_ptr(), pb=B["p"].data_ptr(), n2w=n2w.data_ptr(),
+                             n2b=n2b.data_ptr(), w1b=B["w1"].data_ptr(), w3b=B["w3"].data_ptr(), w2b=B["w2"].data_ptr(),
+                             qkv=imgs[0].data_ptr(), p=imgs[1].data_ptr(), w1=imgs[2].data_ptr(), w3=imgs[3].data_ptr(), w2=imgs[4].data_ptr(),
+                             w2T=imgs[5].data_ptr(), qf=P["q"].data_ptr(), kf=P["k"].data_ptr(), vf=P["v"].data_ptr(), pf=P["p"].data_ptr(),
+                             w1f=P["w1"].data_ptr(), w3f=P["w3"].data_ptr(), hidden=h)
+    x1, x2 = torch.full((M, d), float("nan"), device=DEV), torch.full((M, d), float("nan"), device=DEV)
+    o = torch.zeros(M, d, dtype=torch.bfloat16, device=DEV)
+    lse = torch.zeros(M, heads, device=DEV)
+    _lib.check(_lib.load().hsimae_dec_block_fwd(C.byref(W), x.data_ptr(), x1.data_ptr(), x2.data_ptr(), o.data_ptr(), lse.data_ptr(),
+                                                N, Ts, split, stream()), "hsimae_dec_block_fwd")
+    torch.cuda.synchronize()
+    u = torch.nn.functional.layer_norm(x, (d,), n1w, n1b, 1e-5)
+    q, k, v = (u @ bf(P[n]).t() + B[n] for n in ("q", "k", "v"))
+    sh = lambda z: z.reshape(N, Ts, heads, d // heads).permute(0, 2, 1, 3)
+    att = ((sh(q) @ sh(k).transpose(-1, -2)) * (d // heads) ** -0.5).softmax(-1) @ sh(v)
+    y1 = x + att.permute(0, 2, 1, 3).reshape(M, d) @ bf(P["p"]).t() + B["p"]
+    u2 = torch.nn.functional.layer_norm(y1, (d,), n2w, n2b, 1e-5)
+    h1 = u2 @ bf(P["w1"]).t() + B["w1"]
+    assert float(h1.min()) < -95 and float(h1.max()) > 95
+    y2 = y1 + (torch.nn.functional.silu(h1) * (u2 @ bf(P["w3"]).t() + B["w3"])) @ bf(P["w2"]).t() + B["w2"]
+    print(f"EXTREMES dec split={split}: {int((~torch.isfinite(x2)).sum())} of {x2.numel()} x2 elements not finite, rel_err {rel_err(x2.nan_to_num(0.0), y2):.2e}")
+    assert bool(torch.isfinite(x2).all())
+    assert rel_err(x2, y2) < 1e-2
 
 
 # ----------------------------------------------------------------------------------------------- attention
