@@ -16,6 +16,7 @@
 // Latency kernels: a fine-tuning batch is 32 rows of about 10 classes.  Nothing here waits for the host.
 #include "common.h"
 #include "kernels.h"
+#include "row_wave.h"
 
 namespace {
 
@@ -28,12 +29,12 @@ __host__ __device__ inline ClsPartials cls_carve(void* ws) {
     return ClsPartials{static_cast<double*>(ws), reinterpret_cast<long long*>(static_cast<double*>(ws) + CLS_MAXNB)};
 }
 
-// (arg_better, the argmax rule of the predictions: common.h)
+// (arg_better, the argmax rule of the predictions: common.h; the row's statistics, its argmax and the xor tree: row_wave.h)
 __global__ __launch_bounds__(256) void cls_rows_kernel(hsimae_cls_params p, ClsPartials part) {
     __shared__ double wsum[4];
     __shared__ long long wcnt[4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, C = p.C;
-    const float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
+    const float LN2 = 0.6931471805599453f;
     double lsum = 0.0;
     long long cnt = 0;
     for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < p.N; r += (int64_t)gridDim.x * 4) {       // wave-uniform
@@ -46,19 +47,15 @@ __global__ __launch_bounds__(256) void cls_rows_kernel(hsimae_cls_params p, ClsP
             float bv = -__builtin_inff();
             int bi = 0x7fffffff;
             for (int c = p.first + lane; c < C; c += 64) arg_better(bv, bi, z[c], c);              // ascending: first of a tie stays
-            for (int s = 1; s < 64; s <<= 1) arg_better(bv, bi, __shfl_xor(bv, s), __shfl_xor(bi, s));
+            wave_argmax(bv, bi);
             if (lane == 0) p.pred[r] = bi;
         }
         if (!valid) {                                     // ignored: no loss, an exactly zero gradient row
             if (p.dlogits) for (int c = lane; c < p.ldd; c += 64) p.dlogits[r * p.ldd + c] = 0.f;
             continue;
         }
-        float m = -__builtin_inff();
-        for (int c = lane; c < C; c += 64) m = fmaxf(m, z[c]);
-        for (int s = 1; s < 64; s <<= 1) m = fmaxf(m, __shfl_xor(m, s));
-        float sum = 0.f;
-        for (int c = lane; c < C; c += 64) sum += __builtin_amdgcn_exp2f((z[c] - m) * LOG2E);
-        for (int s = 1; s < 64; s <<= 1) sum += __shfl_xor(sum, s);
+        float m, sum;
+        row_softmax_stats(z, 0, C, lane, m, sum);
         const float loss = __builtin_amdgcn_logf(sum) * LN2 - (z[y] - m);
         lsum += (double)loss;
         ++cnt;
@@ -67,7 +64,7 @@ __global__ __launch_bounds__(256) void cls_rows_kernel(hsimae_cls_params p, ClsP
             float* d = p.dlogits + r * p.ldd;
             for (int c = lane; c < p.ldd; c += 64) {
                 float g = 0.f;
-                if (c < C) g = __builtin_amdgcn_exp2f((z[c] - m) * LOG2E) * rs - (c == y ? 1.f : 0.f);
+                if (c < C) g = row_exp(z[c], m) * rs - (c == y ? 1.f : 0.f);
                 d[c] = g;
             }
         }
@@ -88,7 +85,7 @@ __global__ __launch_bounds__(256) void cls_finish_kernel(ClsPartials part, int n
         double s = 0.0;
         long long n = 0;
         for (int b = lane; b < nb; b += 64) { s += part.sum[b]; n += part.cnt[b]; }
-        for (int k = 1; k < 64; k <<= 1) { s += __shfl_xor(s, k); n += __shfl_xor(n, k); }
+        wave_tree<TreeAdd>(s, n);
         if (lane == 0) {
             inv_s = n > 0 ? 1.f / (float)n : 0.f;
             if (blockIdx.x == 0) {
@@ -173,8 +170,6 @@ __global__ __launch_bounds__(256) void scores_kernel(const int64_t* __restrict__
     }
 }
 
-inline bool misaligned(const void* q, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(q) & mask) != 0; }
-
 int confusion_check(const int64_t* gt, const int64_t* pred, int64_t n, int C, const int64_t* cm, const int32_t* bad) {
     if (n < 0 || C < 2) return HS_EDIMS;
     if (C > CLS_MAXC) return HS_EUNSUPPORTED;
@@ -211,7 +206,7 @@ int hs_cls_loss(const hsimae_cls_params& p, hipStream_t s) {
     const ClsPartials part = cls_carve(p.workspace);
     int nb = 0;
     if (p.N > 0) {
-        nb = (p.N + 3) / 4 < CLS_MAXNB ? (p.N + 3) / 4 : CLS_MAXNB;
+        nb = (int)rows_grid(p.N, CLS_MAXNB);
         hipLaunchKernelGGL(cls_rows_kernel, dim3(nb), dim3(256), 0, s, p, part);
     }
     const int64_t total = p.dlogits ? (int64_t)p.N * p.ldd : 0;

@@ -8,6 +8,7 @@
 //   64 x 64 block P that lies over the slabs.  Rows beyond the matrices and columns beyond D are zero-filled in the slabs.
 #pragma once
 #include "common.h"
+#include "row_wave.h"
 
 constexpr int TQ = 64, TB = 64, KS = 32;
 constexpr int SLD = KS + 1;           // LDS row stride of a slab: lane (i, h) reads [i][2 t + h], 33 i + h spreads over the banks
@@ -86,7 +87,6 @@ __device__ __forceinline__ void hand_over(float (*P)[PLD], const f32x16& acc) {
 __device__ __forceinline__ float row_inv_norm(const float* x, int D, int lane, float& n) {
     float ss = 0.f;
     for (int c = lane; c < D; c += 64) ss = fmaf(x[c], x[c], ss);
-    for (int s = 1; s < 64; s <<= 1) ss += __shfl_xor(ss, s);
-    n = sqrtf(ss);
+    n = sqrtf(tree_sum(ss));
     return 1.f / fmaxf(n, 1e-12f);
 }

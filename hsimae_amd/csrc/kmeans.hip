@@ -24,6 +24,7 @@
 #include "common.h"
 #include "dot_tile.h"
 #include "kernels.h"
+#include "row_wave.h"
 
 namespace {
 
@@ -33,13 +34,16 @@ constexpr int KM_NONE = 0x7fffffff;           // "no centroid yet": loses every 
 // the better of two scores under beats(): a number over a NaN, the larger number
 __device__ __forceinline__ float better_of(float a, float b) { return beats(b, a) ? b : a; }
 
-// (best score, its centroid, second best score) of the centroids seen so far; merging is order-free: ties go by the index
-struct Best { float b; int i; float b2; };
-__device__ __forceinline__ void merge(Best& a, float s, int i, float s2) {
-    const bool take = beats(s, a.b) || (!beats(a.b, s) && i < a.i);
-    if (take) { a.b2 = better_of(s2, a.b); a.b = s; a.i = i; }
-    else a.b2 = better_of(a.b2, s);
-}
+// (best score, its centroid, second best score) of the centroids seen so far, and f, the merge of another such triple into it
+// (the form wave_tree takes); merging is order-free: ties go by the index
+struct Best {
+    float b; int i; float b2;
+    static __device__ __forceinline__ void f(float& b, int& i, float& b2, float s, int si, float s2) {
+        const bool take = beats(s, b) || (!beats(b, s) && si < i);
+        if (take) { b2 = better_of(s2, b); b = s; i = si; }
+        else b2 = better_of(b2, s);
+    }
+};
 
 __global__ __launch_bounds__(256) void kmeans_assign_kernel(hsimae_kmeans_assign_params p) {
     __shared__ float slabs[2][TQ][SLD];          // the two operands' slabs; after a tile's last slab the block P lies over them
@@ -66,18 +70,14 @@ __global__ __launch_bounds__(256) void kmeans_assign_kernel(hsimae_kmeans_assign
             for (int c = 0; c < 16; ++c) {
                 const int col = part * 16 + c, j = j0 + col;
                 const float s = P[row][col] - Bt[col];
-                merge(best, j < K ? s : qnan, j < K ? j : KM_NONE, qnan);
+                Best::f(best.b, best.i, best.b2, j < K ? s : qnan, j < K ? j : KM_NONE, qnan);
             }
         }
-        for (int s = 16; s < 64; s <<= 1) {
-            const float ob = __shfl_xor(best.b, s), ob2 = __shfl_xor(best.b2, s);
-            const int oi = __shfl_xor(best.i, s);
-            merge(best, ob, oi, ob2);
-        }
+        wave_tree<Best, 16>(best.b, best.i, best.b2);                          // the row's four parts: lane ^ 16, ^ 32
         const int64_t i = i0 + row;
         if (part == 0 && i < p.N) {
-            const int64_t pix = p.pixels ? p.pixels[i] : p.p0 + i;
-            if (pix >= 0 && pix < HW) {
+            const int64_t pix = row_pixel(p.pixels, p.p0, i, HW);
+            if (pix >= 0) {
                 const int64_t lab = (int64_t)p.first + best.i;
                 if (p.changed) changed += p.labels[pix] != lab;
                 p.labels[pix] = lab;
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(256) void kmeans_assign_kernel(hsimae_kmeans_assign
         }
     }
     if (p.changed) {                                                           // the same in every thread
-        for (int s = 1; s < 64; s <<= 1) changed += __shfl_xor(changed, s);
+        changed = tree_sum(changed);
         if (lane == 0) Ch[wave] = changed;
         __syncthreads();
         if (threadIdx.x == 0) p.changed[blockIdx.x] = Ch[0] + Ch[1] + Ch[2] + Ch[3];
@@ -153,7 +153,7 @@ __global__ __launch_bounds__(64) void kmeans_sums_kernel(hsimae_kmeans_update_pa
     }
     if (live) p.sums[(int64_t)k * p.D + col] = sum;
     else ine = 0.0;
-    for (int s = 1; s < 64; s <<= 1) ine += __shfl_xor(ine, s);
+    ine = tree_sum(ine);
     if (lane == 0) {
         p.scratch[blockIdx.x] = ine;
         if (slab == 0) p.counts[k] = cnt;
@@ -180,7 +180,7 @@ __global__ __launch_bounds__(256) void kmeans_finish_kernel(hsimae_kmeans_update
         if (p.bias) {
             double ss = 0.0;
             for (int d = lane; d < D; d += 64) ss = fma((double)c[d], (double)c[d], ss);
-            for (int s = 1; s < 64; s <<= 1) ss += __shfl_xor(ss, s);
+            ss = tree_sum(ss);
             if (lane == 0) p.bias[k] = (float)(0.5 * ss);
         }
         return;
@@ -189,11 +189,11 @@ __global__ __launch_bounds__(256) void kmeans_finish_kernel(hsimae_kmeans_update
     const int parts = K * slabs_of(D);
     double ine = 0.0;
     for (int g = lane; g < parts; g += 64) ine += p.scratch[g];
-    for (int s = 1; s < 64; s <<= 1) ine += __shfl_xor(ine, s);
+    ine = tree_sum(ine);
     long long changed = 0, empty = 0;
     if (p.changed) for (int g = lane; g < HSIMAE_KMEANS_GRID; g += 64) changed += p.changed[g];
     for (int k = lane; k < K; k += 64) empty += p.counts[k] == 0;
-    for (int s = 1; s < 64; s <<= 1) { changed += __shfl_xor(changed, s); empty += __shfl_xor(empty, s); }
+    wave_tree<TreeAdd>(changed, empty);
     if (lane == 0) {
         p.state[0] = ine;
         p.state[1] = (double)changed;
@@ -203,8 +203,6 @@ __global__ __launch_bounds__(256) void kmeans_finish_kernel(hsimae_kmeans_update
         p.state[5] = p.state[6] = p.state[7] = 0.0;
     }
 }
-
-inline bool misaligned(const void* q, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(q) & mask) != 0; }
 
 }  // namespace
 

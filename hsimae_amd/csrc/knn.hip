@@ -16,12 +16,13 @@
 //   knn_vote_kernel       one wave per row: lane j holds neighbour j (rank order), w_j = exp2(((sim_j - sim_0) inv_T) log2 e),
 //                         lane l holds the classes first + l, first + l + 64, ..: score_c = the w_j of class c added in rank
 //                         order from 0, total = lane-strided sum and the xor tree, p_c = score_c * (1 / total); label, confidence
-//                         and margin as class_prob_kernel (prob.hip) writes them.
+//                         and margin by wave_argmax, row_runner_up and write_maps (row_wave.h), as class_prob_kernel's.
 //
 // No atomics anywhere; a row is touched by one wave: two runs are bit-identical.
 #include "common.h"
 #include "dot_tile.h"
 #include "kernels.h"
+#include "row_wave.h"
 
 namespace {
 
@@ -104,7 +105,6 @@ __global__ __launch_bounds__(256) void knn_topk_kernel(hsimae_knn_topk_params p)
 __global__ __launch_bounds__(256) void knn_vote_kernel(hsimae_knn_vote_params p) {
     __shared__ float Sc[4][KNN_MAXC];            // per wave: the scores, then the probabilities; a lane re-reads only its own
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, k = p.k, C = p.C, first = p.first;
-    const float LOG2E = 1.4426950408889634f;
     const int64_t HW = (int64_t)p.H * p.W;
     float* sc = Sc[wave];
     for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < p.Q; r += (int64_t)gridDim.x * 4) {       // wave-uniform
@@ -119,7 +119,7 @@ __global__ __launch_bounds__(256) void knn_vote_kernel(hsimae_knn_vote_params p)
         }
         const bool bad = __ballot(wrong) != 0;
         const float s0 = lane_of(s, 0);
-        const float w = __builtin_amdgcn_exp2f(((s - s0) * p.inv_temperature) * LOG2E);
+        const float w = __builtin_amdgcn_exp2f(((s - s0) * p.inv_temperature) * HS_LOG2E);
         const int cls = (int)lab;
         float sum = 0.f;
         for (int c = first + lane; c - lane < C; c += 64) {                                        // whole rounds: every lane takes part
@@ -130,8 +130,7 @@ __global__ __launch_bounds__(256) void knn_vote_kernel(hsimae_knn_vote_params p)
             }
             if (c < C) { sc[c] = a; sum += a; }
         }
-        for (int t = 1; t < 64; t <<= 1) sum += __shfl_xor(sum, t);
-        const float rs = 1.f / sum;
+        const float rs = 1.f / tree_sum(sum);
         float key = -__builtin_inff();
         int best = 0x7fffffff;
         if (p.probs) for (int c = lane; c < first; c += 64) p.probs[r * p.ldp + c] = 0.f;
@@ -141,28 +140,16 @@ __global__ __launch_bounds__(256) void knn_vote_kernel(hsimae_knn_vote_params p)
             if (p.probs) p.probs[r * p.ldp + c] = pc;
             arg_better(key, best, pc, c);
         }
-        for (int t = 1; t < 64; t <<= 1) {
-            const float k2 = __shfl_xor(key, t);
-            const int i2 = __shfl_xor(best, t);
-            arg_better(key, best, k2, i2);
-        }
-        float second = -__builtin_inff();
-        for (int c = first + lane; c < C; c += 64)
-            if (c != best) second = fmaxf(second, sc[c]);
-        for (int t = 1; t < 64; t <<= 1) second = fmaxf(second, __shfl_xor(second, t));
-        const int64_t pix = p.pixels ? p.pixels[r] : p.p0 + r;
+        wave_argmax(key, best);
+        float second = row_runner_up(sc, 1.f, first, C, lane, best);
+        if (bad) { best = 0; key = second = 0.f; }                                                 // label 0, confidence and margin 0
+        const int64_t pix = row_pixel(p.pixels, p.p0, r, HW);
         if (lane == 0) {
             if (bad) *p.bad = 1;
-            if (pix >= 0 && pix < HW) {
-                p.label_map[pix] = bad ? 0 : best;
-                if (p.conf_map) p.conf_map[pix] = bad ? 0.f : key;
-                if (p.margin_map) p.margin_map[pix] = bad ? 0.f : (C - first == 1 ? key : key - second);
-            }
+            write_maps(p.label_map, p.conf_map, p.margin_map, pix, best, key, second, C - first == 1);
         }
     }
 }
-
-inline bool misaligned(const void* q, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(q) & mask) != 0; }
 
 }  // namespace
 
@@ -171,8 +158,7 @@ int hs_row_normalize(const hsimae_row_normalize_params& p, hipStream_t s) {
     if (p.N > 0 && p.D > 0 && (!p.x || !p.out)) return HS_ENULL;
     if (misaligned(p.x, 3) || misaligned(p.out, 3) || misaligned(p.norms, 3)) return HS_EALIGN;
     if (p.N == 0 || p.D == 0) return HS_OK;
-    const int64_t quads = ((int64_t)p.N + 3) / 4;
-    hipLaunchKernelGGL(row_normalize_kernel, dim3((unsigned)(quads < KNN_MAXNB ? quads : KNN_MAXNB)), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(row_normalize_kernel, dim3(rows_grid(p.N, KNN_MAXNB)), dim3(256), 0, s, p);
     return (int)hipGetLastError();
 }
 
@@ -198,8 +184,7 @@ int hs_knn_vote(const hsimae_knn_vote_params& p, hipStream_t s) {
         misaligned(p.label_map, 7) || misaligned(p.conf_map, 3) || misaligned(p.margin_map, 3) || misaligned(p.probs, 3) ||
         misaligned(p.bad, 3)) return HS_EALIGN;
     if (p.Q == 0) return HS_OK;
-    const int64_t quads = ((int64_t)p.Q + 3) / 4;
-    hipLaunchKernelGGL(knn_vote_kernel, dim3((unsigned)(quads < KNN_MAXNB ? quads : KNN_MAXNB)), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(knn_vote_kernel, dim3(rows_grid(p.Q, KNN_MAXNB)), dim3(256), 0, s, p);
     return (int)hipGetLastError();
 }
 

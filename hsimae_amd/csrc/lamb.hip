@@ -143,7 +143,7 @@ __global__ __launch_bounds__(256) void lamb_ratio_kernel(const uint8_t* group, i
         sp += partials[2 * (t.chunk0 + j)];
         su += partials[2 * (t.chunk0 + j) + 1];
     }
-    for (int o = 1; o < 64; o <<= 1) { sp += __shfl_xor(sp, o); su += __shfl_xor(su, o); }
+    wave_tree<TreeAdd>(sp, su);
     if (lane != 0) return;
     float r = 1.f;
     if ((tab[id].y != 0.f || always_adapt) && sp > 0.0 && su > 0.0) r = (float)sqrt(sp / su);

@@ -7,6 +7,7 @@
 #include <initializer_list>
 #include "common.h"
 #include "kernels.h"
+#include "row_wave.h"
 
 struct GroupTable { hsimae_adamw_group e[HSIMAE_ADAMW_MAX_GROUPS]; };            // by value in the launch: 512 bytes of kernarg
 static_assert(sizeof(GroupTable) == 512, "the table travels as a kernel argument");
@@ -50,10 +51,8 @@ __device__ __forceinline__ void block_sum(double* out, const A&... a) {
     constexpr int K = sizeof...(A);
     __shared__ double wsum[K][4];
     double s[K] = {((a[0] + a[1]) + (a[2] + a[3]))...};
-    for (int o = 1; o < 64; o <<= 1) {
 #pragma unroll
-        for (int k = 0; k < K; ++k) s[k] += __shfl_xor(s[k], o);
-    }
+    for (int k = 0; k < K; ++k) s[k] = tree_sum(s[k]);
     if ((threadIdx.x & 63) == 0) {
 #pragma unroll
         for (int k = 0; k < K; ++k) wsum[k][threadIdx.x >> 6] = s[k];
@@ -65,9 +64,7 @@ __device__ __forceinline__ void block_sum(double* out, const A&... a) {
     }
 }
 
-// ------------------------------------------------------------------ host side
-inline bool misaligned(const void* p, uintptr_t mask) { return ((uintptr_t)p & mask) != 0; }
-
+// ------------------------------------------------------------------ host side (misaligned(): row_wave.h)
 // one id for all elements (no id array) must be a table index, or 2: frozen in any table
 inline bool bad_group_uniform(const void* group, int group_uniform, int ngroups) {
     return !group && group_uniform != 2 && (group_uniform < 0 || group_uniform >= ngroups);

@@ -3,8 +3,8 @@
 // probability and the top-1 / top-2 margin.
 //
 //   class_prob_kernel    one wave per row of logits [N][ld], one launch per view of a chunk: the softmax over the columns
-//                        [first, C) in cls_rows_kernel's sequence (row maximum, exp2((z - m) log2 e), a lane-strided sum and the
-//                        xor tree, e * (1 / s)) stored (view 0) or added (later views) into the caller's acc [N][lda]; the
+//                        [first, C) in row_softmax_stats' sequence (row_wave.h: row maximum, exp2((z - m) log2 e), a lane-strided
+//                        sum and the xor tree), e * (1 / s) stored (view 0) or added (later views) into the caller's acc [N][lda]; the
 //                        last view's wave scales its row by fl(1 / n_views) and writes the label, the confidence and the
 //                        margin at the row's pixel and the mean probabilities in chunk order.
 //
@@ -12,6 +12,7 @@
 // A latency kernel like its neighbour in cls.hip: 8192 rows of 10 - 20 classes per chunk.
 #include "common.h"
 #include "kernels.h"
+#include "row_wave.h"
 
 namespace {
 
@@ -21,19 +22,14 @@ constexpr int PROB_MAXNB = 2048;      // workgroups of 4 waves: one row per wave
 
 __global__ __launch_bounds__(256) void class_prob_kernel(hsimae_class_prob_params p) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, C = p.C, first = p.first;
-    const float LOG2E = 1.4426950408889634f;
     const bool start = p.view == 0, last = p.view == p.n_views - 1, single = p.n_views == 1;
     const float inv_v = 1.f / (float)p.n_views;
     const int64_t HW = (int64_t)p.H * p.W;
     for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < p.N; r += (int64_t)gridDim.x * 4) {       // wave-uniform
         const float* z = p.logits + r * p.ld;
         float* a = p.acc + r * p.lda;
-        float m = -__builtin_inff();
-        for (int c = first + lane; c < C; c += 64) m = fmaxf(m, z[c]);
-        for (int s = 1; s < 64; s <<= 1) m = fmaxf(m, __shfl_xor(m, s));
-        float sum = 0.f;
-        for (int c = first + lane; c < C; c += 64) sum += __builtin_amdgcn_exp2f((z[c] - m) * LOG2E);
-        for (int s = 1; s < 64; s <<= 1) sum += __shfl_xor(sum, s);
+        float m, sum;
+        row_softmax_stats(z, first, C, lane, m, sum);
         const float rs = 1.f / sum;
         // the label's key is the logit with one view (hsimae_class_argmax's label, bit for bit) and the mean with more;
         // `val` carries the mean of the candidate along
@@ -42,7 +38,7 @@ __global__ __launch_bounds__(256) void class_prob_kernel(hsimae_class_prob_param
         if (start) for (int c = lane; c < first; c += 64) a[c] = 0.f;
         if (last && p.probs) for (int c = lane; c < first; c += 64) p.probs[r * p.ldp + c] = 0.f;
         for (int c = first + lane; c < C; c += 64) {                                               // ascending: first of a tie stays
-            const float pc = __builtin_amdgcn_exp2f((z[c] - m) * LOG2E) * rs;
+            const float pc = row_exp(z[c], m) * rs;
             const float t = start ? pc : a[c] + pc;       // view 0 never reads acc
             a[c] = t;
             if (last) {
@@ -54,27 +50,13 @@ __global__ __launch_bounds__(256) void class_prob_kernel(hsimae_class_prob_param
             }
         }
         if (!last) continue;
-        for (int s = 1; s < 64; s <<= 1) {
-            const float k2 = __shfl_xor(key, s), v2 = __shfl_xor(val, s);
-            const int i2 = __shfl_xor(best, s), was = best;
-            arg_better(key, best, k2, i2);
-            if (best != was) val = v2;
-        }
+        const ArgVal top = wave_argmax(key, best, val);
         // the runner-up among the other classes: this lane re-reads the sums it stored itself
-        float second = -__builtin_inff();
-        for (int c = first + lane; c < C; c += 64)
-            if (c != best) second = fmaxf(second, a[c] * inv_v);
-        for (int s = 1; s < 64; s <<= 1) second = fmaxf(second, __shfl_xor(second, s));
-        const int64_t pix = p.pixels ? p.pixels[r] : p.p0 + r;
-        if (lane == 0 && pix >= 0 && pix < HW) {
-            p.label_map[pix] = best;
-            if (p.conf_map) p.conf_map[pix] = val;
-            if (p.margin_map) p.margin_map[pix] = C - first == 1 ? val : val - second;
-        }
+        const float second = row_runner_up(a, inv_v, first, C, lane, top.idx);
+        const int64_t pix = row_pixel(p.pixels, p.p0, r, HW);
+        if (lane == 0) write_maps(p.label_map, p.conf_map, p.margin_map, pix, top.idx, top.val, second, C - first == 1);
     }
 }
-
-inline bool misaligned(const void* q, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(q) & mask) != 0; }
 
 }  // namespace
 
@@ -86,8 +68,7 @@ int hs_class_prob(const hsimae_class_prob_params& p, hipStream_t s) {
     if (misaligned(p.logits, 3) || misaligned(p.acc, 3) || misaligned(p.conf_map, 3) || misaligned(p.margin_map, 3) ||
         misaligned(p.probs, 3) || misaligned(p.pixels, 7) || misaligned(p.label_map, 7)) return HS_EALIGN;
     if (p.N == 0) return HS_OK;
-    const int64_t quads = ((int64_t)p.N + 3) / 4;
-    hipLaunchKernelGGL(class_prob_kernel, dim3((unsigned)(quads < PROB_MAXNB ? quads : PROB_MAXNB)), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(class_prob_kernel, dim3(rows_grid(p.N, PROB_MAXNB)), dim3(256), 0, s, p);
     return (int)hipGetLastError();
 }
 

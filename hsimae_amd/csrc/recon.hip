@@ -6,7 +6,7 @@
 //                             whole contiguous runs.  The lane walks the windows of the chunk that hold its pixel un-reflected
 //                             (at most 9 per axis: the centres are distinct integers within 4 of the pixel) in ascending window
 //                             index and adds the predictions whose mask is set.  A voxel has one owner: no atomics.
-//   recon_finish_kernel       one wave per pixel, the bands lane-strided, fp64 sums through the xor tree (prob.hip's pattern);
+//   recon_finish_kernel       one wave per pixel, the bands lane-strided, fp64 sums through the xor tree (tree_sum, row_wave.h);
 //                             a workgroup's four waves leave one partial of each of the four statistics.
 //   recon_stats_kernel        one workgroup, one wave per statistic: the partials lane-strided in ascending order, then the xor tree.
 //
@@ -15,6 +15,7 @@
 // 132 us, no gain, so these reads are not what bounds the kernel and the plain form stays (profiles/EXPERIMENTS.md).
 #include "common.h"
 #include "kernels.h"
+#include "row_wave.h"
 
 namespace {
 
@@ -69,11 +70,6 @@ __global__ __launch_bounds__(256) void recon_accumulate_kernel(hsimae_recon_accu
     }
 }
 
-__device__ __forceinline__ double tree_sum(double v) {
-    for (int s = 1; s < 64; s <<= 1) v += __shfl_xor(v, s);
-    return v;
-}
-
 template <typename T>
 __global__ __launch_bounds__(256) void recon_finish_kernel(hsimae_recon_finish_params p) {
     __shared__ double part[4][4];
@@ -99,7 +95,7 @@ __global__ __launch_bounds__(256) void recon_finish_kernel(hsimae_recon_finish_p
             }
         }
         se = tree_sum(se); rr = tree_sum(rr); xx = tree_sum(xx);
-        for (int s = 1; s < 64; s <<= 1) m += __shfl_xor(m, s);
+        m = tree_sum(m);
         double rmse = 0., sam = 0.;
         if (m > 0) {
             rmse = sqrt(se / (double)m);
@@ -147,8 +143,6 @@ __global__ __launch_bounds__(256) void recon_stats_kernel(const double* partials
     if (lane == 0) stats[j] = t;
 }
 
-inline bool misaligned(const void* q, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(q) & mask) != 0; }
-
 }  // namespace
 
 int hs_recon_accumulate(const hsimae_recon_accumulate_params& p, hipStream_t s) {
@@ -171,8 +165,7 @@ int hs_recon_finish(const hsimae_recon_finish_params& p, hipStream_t s) {
     if (misaligned(p.scene, p.scene_f64 ? 7 : 3) || misaligned(p.sum, 3) || misaligned(p.cnt, 3) || misaligned(p.recon, 3) ||
         misaligned(p.cover, 3) || misaligned(p.rmse, 3) || misaligned(p.sam, 3) || misaligned(p.partials, 7) ||
         misaligned(p.stats, 7)) return HS_EALIGN;
-    const int64_t quads = ((int64_t)p.H * p.W + 3) / 4;
-    const int grid = (int)(quads < HSIMAE_RECON_GRID ? quads : HSIMAE_RECON_GRID);
+    const int grid = (int)rows_grid((int64_t)p.H * p.W, HSIMAE_RECON_GRID);
     if (p.scene_f64) hipLaunchKernelGGL(recon_finish_kernel<double>, dim3(grid), dim3(256), 0, s, p);
     else hipLaunchKernelGGL(recon_finish_kernel<float>, dim3(grid), dim3(256), 0, s, p);
     hipLaunchKernelGGL(recon_stats_kernel, dim3(1), dim3(256), 0, s, p.partials, grid, p.stats);

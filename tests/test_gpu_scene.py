@@ -1,5 +1,5 @@
 """Whole-scene inference on the GPU: hsimae_scene_windows against the windows recorded from the reference
-(tests/golden/scene_windows.npz), hsimae_class_argmax against torch.argmax, DualViT.predict_scene against HSIViT.forward on
+(tests/golden/scene_windows.npz) and against hsimae_scene_batch, hsimae_class_argmax against torch.argmax, DualViT.predict_scene against HSIViT.forward on
 windows built the reference's way, chunk invariance, the oracle at Base width, and test_model_scene against test_model."""
 import contextlib
 import ctypes as C
@@ -69,6 +69,40 @@ def test_scene_windows_are_bit_exact_with_the_reference(tag, layout):
     out = buf(idx.numel())
     run_windows(scene, idx.numel(), out, pixels=idx.cuda())
     assert torch.equal(out.cpu(), items[idx])
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("Cb", [5, 8])                                  # scalar copy, 16-byte copy
+def test_windows_and_batch_entry_points_cut_the_same_windows(Cb, dtype):
+    """hsimae_scene_windows and hsimae_scene_batch run one cutter: on a 3 x 3 scene (narrower than the 4-pixel pad: the symmetric
+    index wraps more than once) the same pixel list gives the same bits from both, and numpy's.  The last two pixels lie outside
+    the scene: zero windows from both, `bad` from the batch entry point alone.  Nothing behind the window buffers is written."""
+    from hsimae_amd import _lib
+    scene = np.random.default_rng(Cb).standard_normal((3, 3, Cb)).astype(dtype)
+    pad = np.pad(scene, ((4, 4), (4, 4), (0, 0)), "symmetric")
+    pix = [0, 4, 8, -1, 9]
+    want = torch.zeros(5, 9, 9, Cb)
+    for k, p in enumerate(pix[:3]):
+        want[k] = torch.from_numpy(pad[p // 3:p // 3 + 9, p % 3:p % 3 + 9].astype(np.float32))
+    scene_d, pix_d, n = torch.from_numpy(scene).cuda(), torch.tensor(pix).cuda(), 5 * 81 * Cb
+    got = []
+    for batch in (False, True):
+        big = torch.full((n + 64,), -7.0, device="cuda")
+        out = big[:n].view(5, 9, 9, Cb).permute(0, 3, 1, 2).unsqueeze(1)                # band-fastest, as the loaders deliver
+        if batch:
+            items, bad = torch.arange(5).cuda(), torch.zeros(1, dtype=torch.int32, device="cuda")
+            p = _lib.SceneBatchParams(scene=scene_d.data_ptr(), scene_f64=int(dtype == np.float64), H=3, W=3, C=Cb,
+                                      items=items.data_ptr(), N=5, n_items=5, pixels=pix_d.data_ptr(), out=out.data_ptr(),
+                                      sn=out.stride(0), sb=out.stride(2), sh=out.stride(3), sw=out.stride(4), bad=bad.data_ptr())
+            _lib.check(_lib.load().hsimae_scene_batch(C.byref(p), torch.cuda.current_stream().cuda_stream), "hsimae_scene_batch")
+            assert int(bad.item()) == 1
+        else:
+            run_windows(scene_d, 5, out, pixels=pix_d)
+        assert (big[n:] == -7).all(), "canary behind the windows overwritten"
+        got.append(big[:n].view(5, 9, 9, Cb).cpu())
+    assert torch.equal(got[0].view(torch.int32), got[1].view(torch.int32))
+    assert torch.equal(got[0].view(torch.int32), want.view(torch.int32))
+    assert (got[0][3:] == 0).all() and (got[1][3:] == 0).all()
 
 
 def run_argmax(logits, H, W, labels, first=1, pixels=None, p0=0):

@@ -175,7 +175,7 @@ def test_build_info_names_every_ablation_switch_and_the_loader_refuses_variants(
 
 
 def test_shared_device_primitives_are_defined_once():
-    """The device vocabulary the kernel units share has ONE definition each under csrc/ (common.h; the phase counters in phase.h),
+    """The device vocabulary the kernel units share has ONE definition each under csrc/ (common.h; the phase counters in phase.h; the wave-per-row pieces in row_wave.h),
     the names of the per-unit copies it replaced are gone, and `static bool attr_set` (a launcher's own "opt in to dynamic LDS
     once" block instead of common.h's hs_launch_lds) stands only where it was left on purpose: hs_loss in elem.hip, which opts in
     to a fixed 150 KiB and launches with less.  (fused_enc.hip's set_attrs, one flag for the three kernels of a width, is the other
@@ -188,6 +188,13 @@ def test_shared_device_primitives_are_defined_once():
     for gone in ("mfma_k16", "mfma_k16w", "tr4w", "cvt4w", "zero4_", "red8", "redrow", "PHB_DECL", "PHF_FLUSH", "PH2_DECL"):
         assert [f for f, t in text.items() if re.search(r"\b%s\b" % gone, t)] == [], gone
     assert [(f, t.count("static bool attr_set")) for f, t in text.items() if "static bool attr_set" in t] == [("elem.hip", 1)]
+    # what the wave-per-row kernels of the whole-scene units share (row_wave.h), and the one window cutter of scene.hip
+    for name, home in (("wave_tree", "row_wave.h"), ("row_softmax_stats", "row_wave.h"), ("row_runner_up", "row_wave.h"),
+                       ("row_pixel", "row_wave.h"), ("write_maps", "row_wave.h"), ("sym_index", "scene.hip"), ("copy_window", "scene.hip")):
+        defs = [f for f, t in text.items() for _ in re.finditer(r"__device__[^;{}()]*?\b%s\s*\(" % name, t)]
+        assert defs == [home], (name, defs)
+    assert [f for f, t in text.items() if re.search(r"\bbool misaligned\s*\(", t)] == ["row_wave.h"]
+    assert [(f, t.count("__shfl_xor(")) for f, t in text.items() if "__shfl_xor(" in t] == [("row_wave.h", 1)]
     # the phase macros are defined in phase.h alone, and every unit that stamps phases gets them from there
     for f, t in text.items():
         assert (re.search(r"#\s*define\s+PHS?(_\w+)?\(", t) is not None) == (f == "phase.h"), f
