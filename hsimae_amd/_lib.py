@@ -170,6 +170,27 @@ class KmeansUpdateParams(C.Structure):
                 ("c", vp), ("ldc", i32), ("bias", vp), ("counts", vp), ("sums", vp), ("changed", vp), ("scratch", vp), ("state", vp)]
 
 
+class ProbePrepareParams(C.Structure):
+    _fields_ = [("x", vp), ("ldx", i32), ("labels", vp), ("n", i32), ("D", i32), ("C", i32), ("first", i32), ("eps", f32),
+                ("mean", vp), ("rstd", vp), ("xs", vp), ("Kp", i32), ("xt", vp), ("ldn", i32), ("state", vp)]
+
+
+class ProbeStepParams(C.Structure):
+    _fields_ = [("xs", vp), ("xt", vp), ("Kp", i32), ("ldn", i32), ("labels", vp), ("n", i32), ("D", i32), ("C", i32), ("first", i32),
+                ("w", vp), ("m", vp), ("v", vp), ("gt", vp), ("scratch", vp), ("loss_part", vp), ("norm_part", vp),
+                ("lr", f32), ("weight_decay", f32), ("b1", f32), ("b2", f32), ("eps", f32), ("step", i32), ("state", vp), ("loss_hist", vp)]
+
+
+class ProbeLogitsParams(C.Structure):
+    _fields_ = [("x", vp), ("ldx", i32), ("mean", vp), ("rstd", vp), ("w", vp), ("Kp", i32), ("n", i32), ("D", i32), ("C", i32),
+                ("first", i32), ("z", vp), ("ldz", i32)]
+
+
+class ProbeFoldParams(C.Structure):
+    _fields_ = [("w", vp), ("Kp", i32), ("mean", vp), ("rstd", vp), ("D", i32), ("C", i32), ("first", i32), ("weight", vp), ("ldw", i32),
+                ("bias", vp)]
+
+
 class ReconAccumulateParams(C.Structure):
     _fields_ = [("pred_img", vp), ("mask_img", vp), ("n", i32), ("w0", i64), ("rows", vp), ("nrows", i32), ("cols", vp), ("ncols", i32),
                 ("H", i32), ("W", i32), ("C", i32), ("sum", vp), ("cnt", vp)]
@@ -207,6 +228,9 @@ LAMB_CHUNK = 4096       # HSIMAE_LAMB_CHUNK: floats of one tensor behind one wor
 RECON_GRID = 1024       # HSIMAE_RECON_GRID: hsimae_recon_finish needs 4 doubles of scratch for each in `partials`
 KMEANS_GRID = 2048      # HSIMAE_KMEANS_GRID: int32 partial counts hsimae_kmeans_assign writes into `changed`
 KMEANS_STATE = 8        # HSIMAE_KMEANS_STATE: doubles of hsimae_kmeans_update's state block (inertia, changed, iterations, empty, bad)
+PROBE_SEG = 256         # HSIMAE_PROBE_SEG: bank rows behind one gradient partial of hsimae_probe_step
+PROBE_STATE = 8         # HSIMAE_PROBE_STATE: doubles of the probe's state block (loss, iterations, ||dW||^2, bad, valid rows)
+PROBE_ROWS = 64         # HSIMAE_PROBE_ROWS: rows of the probe's w, m, v and gt (at most that many classes)
 EMA_MAX_GRID = 2048     # HSIMAE_EMA_MAX_GRID: workgroups (of 256 threads) hsimae_ema_update / hsimae_ema_swap launch at most
 
 
@@ -284,6 +308,10 @@ SYMBOLS = {
     "hsimae_knn_vote": (C.c_int, [C.POINTER(KnnVoteParams), vp]),
     "hsimae_kmeans_assign": (C.c_int, [C.POINTER(KmeansAssignParams), vp]),
     "hsimae_kmeans_update": (C.c_int, [C.POINTER(KmeansUpdateParams), vp]),
+    "hsimae_probe_prepare": (C.c_int, [C.POINTER(ProbePrepareParams), vp]),
+    "hsimae_probe_step": (C.c_int, [C.POINTER(ProbeStepParams), vp]),
+    "hsimae_probe_logits": (C.c_int, [C.POINTER(ProbeLogitsParams), vp]),
+    "hsimae_probe_fold": (C.c_int, [C.POINTER(ProbeFoldParams), vp]),
     "hsimae_recon_accumulate": (C.c_int, [C.POINTER(ReconAccumulateParams), vp]),
     "hsimae_recon_finish": (C.c_int, [C.POINTER(ReconFinishParams), vp]),
     "hsimae_encode": (C.c_int, [C.POINTER(Config), C.POINTER(IO), vp]),

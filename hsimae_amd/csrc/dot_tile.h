@@ -1,5 +1,6 @@
-// The exact-fp32 64 x 64 dot-product tile shared by knn.hip (knn_topk_kernel) and kmeans.hip (kmeans_assign_kernel), and the
-// wave-per-row normalisation both units apply (row_normalize_kernel, the cosine centroids of kmeans_finish_kernel).
+// The exact-fp32 64 x 64 dot-product tile shared by knn.hip (knn_topk_kernel), kmeans.hip (kmeans_assign_kernel) and probe.hip (the
+// forward and the gradient partials), and the wave-per-row normalisation the first two apply (row_normalize_kernel, the cosine
+// centroids of kmeans_finish_kernel).
 //
 //   A workgroup of 256 threads (4 waves) holds 64 rows of A and 64 rows of B.  K-slabs of 32 columns of both operands are staged
 //   in LDS (fetch_slab / put_slab), every wave forms one 32 x 32 block of dot products on v_mfma_f32_32x32x2_f32: a k-ordered fmaf
@@ -45,8 +46,13 @@ __device__ __forceinline__ void put_slab(float (*dst)[SLD], const SlabRegs& s) {
 
 // The dot products of the A rows a0 .. a0 + 63 with the B rows b0 .. b0 + 63: this wave's 32 x 32 block (A rows qi + .., B rows
 // bj + ..).  On entry ra / rb hold the tile's first slabs; on exit those of the tile (a0, b0 + 64) when B has such rows.
-__device__ __forceinline__ f32x16 dot_tile(float (*As)[SLD], float (*Bs)[SLD], SlabRegs& ra, SlabRegs& rb, const float* A, int64_t a0,
-                                           int64_t arows, int lda, const float* B, int64_t b0, int64_t brows, int ldb, int D) {
+// dot_tile_staged: A holds only DA <= D of the chain's D columns, and stage(slab, k0) turns every fetched A slab (zero from column DA
+// on) into the operand before it reaches LDS (probe.hip standardises feature rows there); the caller stages the first slab itself.
+struct StageAsIs { __device__ __forceinline__ void operator()(SlabRegs&, int) const {} };
+template <class Stage>
+__device__ __forceinline__ f32x16 dot_tile_staged(float (*As)[SLD], float (*Bs)[SLD], SlabRegs& ra, SlabRegs& rb, const float* A,
+                                                  int64_t a0, int64_t arows, int lda, int DA, const float* B, int64_t b0, int64_t brows,
+                                                  int ldb, int D, const Stage& stage) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int qi = (wave & 1) * 32, bj = (wave >> 1) * 32;                 // this wave's 32 x 32 block of the tile
     const int li = lane & 31, lh = lane >> 5;
@@ -61,7 +67,8 @@ __device__ __forceinline__ f32x16 dot_tile(float (*As)[SLD], float (*Bs)[SLD], S
         // the next slab of this tile, or the first of the next tile (it arrives during the tile's epilogue); none after the last
         const bool more = k0 + KS < D;
         if (more || b0 + TB < brows) {
-            ra = fetch_slab(A, a0, arows, lda, more ? k0 + KS : 0, D);
+            ra = fetch_slab(A, a0, arows, lda, more ? k0 + KS : 0, DA);
+            stage(ra, more ? k0 + KS : 0);
             rb = fetch_slab(B, more ? b0 : b0 + TB, brows, ldb, more ? k0 + KS : 0, D);
         }
 #pragma unroll
@@ -69,6 +76,10 @@ __device__ __forceinline__ f32x16 dot_tile(float (*As)[SLD], float (*Bs)[SLD], S
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[qi + li][2 * t + lh], Bs[bj + li][2 * t + lh], acc, 0, 0, 0);
     }
     return acc;
+}
+__device__ __forceinline__ f32x16 dot_tile(float (*As)[SLD], float (*Bs)[SLD], SlabRegs& ra, SlabRegs& rb, const float* A, int64_t a0,
+                                           int64_t arows, int lda, const float* B, int64_t b0, int64_t brows, int ldb, int D) {
+    return dot_tile_staged(As, Bs, ra, rb, A, a0, arows, lda, D, B, b0, brows, ldb, D, StageAsIs{});
 }
 
 // the wave's block into P [A row][B row]; barriers on both sides: every wave has read its last slab, and P is whole afterwards

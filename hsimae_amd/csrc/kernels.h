@@ -56,6 +56,10 @@ int hs_knn_topk(const hsimae_knn_topk_params& p, hipStream_t s);
 int hs_knn_vote(const hsimae_knn_vote_params& p, hipStream_t s);
 int hs_kmeans_assign(const hsimae_kmeans_assign_params& p, hipStream_t s);
 int hs_kmeans_update(const hsimae_kmeans_update_params& p, hipStream_t s);
+int hs_probe_prepare(const hsimae_probe_prepare_params& p, hipStream_t s);
+int hs_probe_step(const hsimae_probe_step_params& p, hipStream_t s);
+int hs_probe_logits(const hsimae_probe_logits_params& p, hipStream_t s);
+int hs_probe_fold(const hsimae_probe_fold_params& p, hipStream_t s);
 int hs_recon_accumulate(const hsimae_recon_accumulate_params& p, hipStream_t s);
 int hs_recon_finish(const hsimae_recon_finish_params& p, hipStream_t s);
 int hs_agg_pool(const float* latent, float* pooled, int N, int T, int L, int D, hipStream_t s);

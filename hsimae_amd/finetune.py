@@ -311,6 +311,45 @@ class DualViT(HSIMAE):
                 knn.check()
         return SceneClassification(*out)
 
+    # ------------------------------------------------------------------ a linear probe on the frozen encoder
+    def probe_scene(self, scene, bank_pixels, bank_labels, pixels=None, bank_flips=(0,), views=(0,), batch_size=8192,
+                    return_probs=False, on_device=False, **probe_kwargs):
+        """classify_scene with a head trained here, on the frozen encoder: a linear probe (probe.LinearProbe: per-column
+        standardised features, full-batch AdamW on the device) fitted on the pooled features of the labelled pixels.  The bank is
+        built as knn_scene builds it: `scene_features` of `bank_pixels` under each flip code of `bank_flips` ("flips" = all four),
+        concatenated as rows, `bank_labels` (one per bank pixel, in [1, num_class)) repeated per code.  The encoder runs once over
+        the bank; no step of the fit touches it.  `probe_kwargs`: LinearProbe's (max_iter, lr, weight_decay, betas, eps,
+        schedule, bn_eps).
+        THIS OVERWRITES THE MODEL'S HEAD: the probe folded back to the raw features (LinearProbe.head) is copied into
+        `cls_head.weight` / `.bias`, so every entry point that serves a trained head (classify_scene, predict_scene, the colour maps,
+        state_dict) serves the probe from then on.  num_class <= 64.
+        -> classify_scene(scene, pixels, views=views)'s SceneClassification with that head; `scene`, `pixels`, `batch_size`,
+        `return_probs`, `on_device`: as classify_scene.  With on_device=True nothing waits for the host.  The fitted probe of the last
+        call stays reachable as `self.last_probe` (`.loss_history`, `.grad_norm`, `.check()`)."""
+        from .probe import LinearProbe
+        bank_flips = scene_views(bank_flips)
+        probe = LinearProbe(self.num_class, first=1, **probe_kwargs)
+        s = scene_array(scene, self.patch_embed.bands, batch_size)[0]
+        dev = gpu_of(self)
+        with torch.no_grad(), torch.cuda.device(dev):
+            s = s.to(dev).contiguous()                     # uploaded once: the bank's passes and the classification share it
+            y = torch.as_tensor(np.asarray(bank_labels) if not isinstance(bank_labels, torch.Tensor) else bank_labels)
+            if y.dim() != 1 or y.dtype.is_floating_point or y.dtype == torch.bool:
+                raise ValueError("bank_labels must be a 1-D array of integer labels")
+            bank = [self.scene_features(s, bank_pixels, batch_size, flip=f, on_device=True) for f in bank_flips]
+            if bank[0].shape[0] != y.numel():
+                raise ValueError(f"{y.numel()} labels for {bank[0].shape[0]} bank pixels")
+            probe.fit(bank[0] if len(bank) == 1 else torch.cat(bank), y.to(dev).repeat(len(bank_flips)))
+            del bank
+            weight, bias = probe.head()
+            self.cls_head.weight.copy_(weight)             # (in-place: the version counters move, so _packed_head repacks)
+            self.cls_head.bias.copy_(bias)
+            self.last_probe = probe
+        out = self.classify_scene(s, pixels, batch_size=batch_size, views=views, return_probs=return_probs, on_device=on_device)
+        if not on_device:
+            probe.check()
+        return out
+
     # ------------------------------------------------------------------ a land-cover map without labels
     def cluster_scene(self, scene, n_clusters, pixels=None, fit_pixels=None, features="encoder", metric=None, flip=0, max_iter=20,
                       n_init=1, generator=None, batch_size=8192, on_device=False, init="random"):

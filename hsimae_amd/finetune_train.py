@@ -403,6 +403,39 @@ def knn_eval_scene(scene, train_index, train_labels, test_gt, gt, pretrained, de
     return _score_and_save(pred, test_gt, gt, n_class, device, save_dir, name, save_images)
 
 
+def linear_probe_scene(scene, train_index, train_labels, test_gt, gt, pretrained, depth=12, dim=96, s_depth=6, bank_flips=(0,),
+                       views=(0,), device="cuda:0", batch_size=8192, save_dir=None, model_name=None, save_images=False,
+                       **probe_kwargs):
+    """The evaluation masked-autoencoder work reports first: a linear classifier on the frozen encoder's pooled features, trained
+    on the device on the cached features of the labelled pixels (HSIViT.probe_scene, probe.LinearProbe), over the whole scene.
+    Inputs as knn_eval_scene's: `scene` the processed [H, W, C] `HSI_data`, `train_index` / `train_labels` the labelled pixels the
+    probe is fitted on, `test_gt` / `gt` as in test_model_scene; `pretrained` the path of a state dict, loaded key-filtered as
+    knn_eval_scene loads it (a pretraining and a fine-tuned checkpoint both work; a fine-tuned head is replaced by the probe).
+    `bank_flips`, `views`, `probe_kwargs` (max_iter, lr, weight_decay, ..): probe_scene's.  The defaults are not tuned on a real scene.
+    With `save_dir` the probed model's state dict (HSIViT's own, as dual_branch_finetuning saves it: encoder as loaded, head = the probe) is
+    written as <save_dir>/<stem of model_name>_probe.pkl, which test_model_scene and the reference's test_model load;
+    model_name defaults to the checkpoint's file name.  save_images=True also writes test_model_scene's two pictures.
+    -> (oa, aa, kappa, per-class recall, prediction map shaped like `gt`), scored as test_model_scene scores."""
+    device = torch.device(device)
+    bank_flips, views = scene_views(bank_flips), scene_views(views)
+    if len(scene.shape) != 3:
+        raise ValueError(f"scene must be [H, W, C], got shape {tuple(scene.shape)}")
+    if save_images and save_dir is None:
+        raise ValueError("save_images=True needs save_dir")
+    c = int(scene.shape[2])
+    n_class = int(np.max(gt) + 1)
+    model = load_matching(eval_vit(9, c, n_class, dim, depth, s_depth, device), pretrained, device, match_shapes=True)
+    pred = model.probe_scene(scene, train_index, train_labels, bank_flips=bank_flips, views=views, batch_size=batch_size,
+                             on_device=True, **probe_kwargs).labels
+    model.last_probe.check()
+    name = os.path.basename(str(pretrained)) if model_name is None else model_name
+    if save_dir is not None:
+        os.makedirs(save_dir, exist_ok=True)
+        stem = name[:-4] if name.endswith(".pkl") else name
+        torch.save(model.state_dict(), os.path.join(save_dir, stem + "_probe.pkl"))
+    return _score_and_save(pred, test_gt, gt, n_class, device, save_dir, name, save_images)
+
+
 def cluster_eval_scene(scene, gt, pretrained, n_clusters=None, depth=12, dim=96, s_depth=6, features="encoder", metric=None, flip=0,
                        max_iter=20, n_init=1, generator=None, init="random", fit_pixels=None, device="cuda:0", batch_size=8192,
                        save_dir=None, model_name=None, save_images=False):

@@ -814,6 +814,100 @@ typedef struct {
 } hsimae_kmeans_update_params;
 int hsimae_kmeans_update(const hsimae_kmeans_update_params* p, void* stream);
 
+/* ------------------------------------------------------------------ linear probe on frozen features (csrc/probe.hip)
+ * ADDED under HSIMAE_VERSION 108 like the entry points above: nothing that 108 already had changes.  Multinomial logistic
+ * regression over the real classes [first, C) (class 0 is "unlabelled" with first = 1, as in hsimae_class_prob) on fp32 feature
+ * rows x [n][ldx] of D columns, standardised per column (MAE's probe: BatchNorm1d(affine=False, eps) ahead of the linear layer),
+ * the bias carried as column D whose feature is the constant 1, trained by full-batch AdamW with decoupled decay (none on the
+ * bias column).  Kp = D + 4 is the operand width (column D = 1, columns D + 1 .. Kp - 1 = 0).  The weights w, and Adam's moments
+ * m and v, are fp32 [64][Kp]; the caller zeroes all three once; the rows below `first` and from C on, and the columns behind D,
+ * are never written and stay 0.  No atomics, no cooperative launch, no grid-wide barrier, no flag, no host wait: every output
+ * element is one chain in a fixed order that does not depend on the grid, so two runs are bit-identical.
+ * Limits of all four: n >= 0, D > 0, D % 4 = 0, 2 <= C, 0 <= first < C, a leading dimension below its width, Kp != D + 4 ->
+ * HSIMAE_EDIMS; C > 64, D > 4096 or n > 2^20 -> HSIMAE_EUNSUPPORTED; params NULL, or with n > 0 a required pointer NULL ->
+ * HSIMAE_ENULL; a matrix not 16-byte aligned or with a leading dimension that is no multiple of 4, another pointer not aligned
+ * to its element -> HSIMAE_EALIGN; n = 0 -> HSIMAE_OK and no launch (the dimension checks come first).  A refusal writes nothing.
+ *
+ * hsimae_probe_prepare (two launches): a bank row i is valid when labels[i] (int64 [n]) lies in [first, C); any other row is
+ *   counted in `bad` and is inert: it enters no statistic, its rows of xs and xt are 0 (column D too), so it adds exact zeros to
+ *   every later sum.  nv = the number of valid rows.  Per column d, one thread, fp64, the valid rows in ascending order from 0:
+ *     sum_d = x_0d + x_1d + ..;  mu = sum_d / nv;  ss_d = fma(x_id - mu, x_id - mu, ss_d);  var = ss_d / nv (population variance)
+ *     mean[d] = fp32(mu);  rstd[d] = fp32(1 / sqrt(var + (double)eps))            (nv = 0: mean 0, rstd 0)
+ *   xs fp32 [n][Kp]: xs[i][d] = fl(fl(x[i][d] - mean[d]) * rstd[d]), xs[i][D] = 1, 0 behind; xt fp32 [Kp][ldn] its transpose with
+ *   zeros in the columns n .. roundup(n, 4) - 1 (ldn >= roundup(n, 4); columns behind that are neither written nor read).
+ *   state fp64 [HSIMAE_PROBE_STATE] = {0, 0, 0, bad, nv, 0, 0, 0}.  eps must be a positive finite number, else HSIMAE_EDIMS.
+ *
+ * hsimae_probe_step: iteration `step` = 1, 2, .. (an ARGUMENT: the host counts, and AdamW's bias corrections 1 / (1 - b1^step) and
+ *   1 / sqrt(1 - b2^step) are formed on the host in fp64 and rounded once, as hsimae_adamw_step forms them), four launches:
+ *   forward   one workgroup per 64 rows: z_ic = the exact-fp32 fmaf chain from +0 over k = 0 .. Kp - 1 of xs[i][k] w[c][k]
+ *             (hsimae_knn_topk's dot tile); per row, one wave: m = max of z over [first, C), e_c = exp2((z_c - m) log2 e), sum =
+ *             the e_c added by the xor tree over the lanes (lane = c - first), p_c = e_c * (1 / sum);
+ *             g_ic = (p_ic - [c = labels[i]]) * fp32(1 / nv), written transposed into gt fp32 [64][ldn]: 0 for c < first, c >= C,
+ *             an invalid row and the columns n .. roundup(n, 4) - 1.  The row's loss = log(sum) - (z_iy - m) in fp64; a wave adds
+ *             its 16 rows in ascending order, the four waves are added in order: loss_part fp64 [ceil(n / 64)].
+ *   gradient  the rows are cut into S = ceil(n / HSIMAE_PROBE_SEG) segments; workgroup (64 columns of Kp, segment s):
+ *             dW_s[c][k] = the fmaf chain from +0 over the segment's rows i ascending of gt[c][i] xt[k][i] -> scratch fp32 [S][64][Kp].
+ *   update    per element (c, k), first <= c < C, k <= D: dW = scratch[0][c][k] + scratch[1][c][k] + .. in ascending s (fp32, from
+ *             the first term); torch.optim.AdamW's element with lr, weight_decay (0 for k = D), b1, b2, eps, in hsimae_adamw_step's
+ *             operation order; per workgroup of 256 elements the fp64 sum of dW^2 (the optimizers' fixed-order block sum).
+ *   finish    one wave: lane l adds loss_part[l], [l + 64], .. in order, then the xor tree; the same for the dW^2 partials:
+ *             state = {loss / nv (the mean cross-entropy BEFORE this update), step, ||dW||^2, bad, nv, 0, 0, 0} (bad and nv kept);
+ *             loss_hist[step - 1] = fp32 of that loss when loss_hist is not NULL.
+ *   norm_part fp64 [ceil(64 Kp / 256)].  step < 1, or lr, weight_decay, eps negative or NaN, b1 or b2 outside [0, 1) -> HSIMAE_EDIMS.
+ *
+ * hsimae_probe_logits: z fp32 [n][ldz] = the forward tile alone for any rows x [n][ldx]: every row is standardised while it is
+ *   staged (fl(fl(x - mean) * rstd), column D = 1) and meets w in the same chain, so the logits of the bank equal the forward's
+ *   bit for bit.  Columns c < first receive 0 (never -inf), columns C .. ldz - 1 are untouched.  ldz < C -> HSIMAE_EDIMS.
+ *
+ * hsimae_probe_fold: the head in the model's terms, for rows of raw features: weight fp32 [C][ldw], weight[c][d] = fl(w[c][d] *
+ *   rstd[d]); bias fp32 [C], bias[c] = fp32(w[c][D] - sum_d w[c][d] mean[d] rstd[d]), the products and the sum in fp64 over
+ *   ascending d from 0 (one thread).  Rows below `first` are 0.  ldw < D -> HSIMAE_EDIMS. */
+#define HSIMAE_PROBE_SEG 256         /* bank rows behind one gradient partial: a constant, so no sum depends on the grid */
+#define HSIMAE_PROBE_STATE 8         /* doubles in `state` */
+#define HSIMAE_PROBE_ROWS 64         /* rows of w, m, v and gt: C at most */
+typedef struct {
+    const float* x; int32_t ldx;
+    const int64_t* labels;
+    int32_t n, D, C, first;
+    float eps;
+    float* mean; float* rstd;
+    float* xs; int32_t Kp;
+    float* xt; int32_t ldn;
+    double* state;
+} hsimae_probe_prepare_params;
+int hsimae_probe_prepare(const hsimae_probe_prepare_params* p, void* stream);
+
+typedef struct {
+    const float* xs; const float* xt; int32_t Kp, ldn;
+    const int64_t* labels;
+    int32_t n, D, C, first;
+    float* w; float* m; float* v;
+    float* gt; float* scratch;
+    double* loss_part; double* norm_part;
+    float lr, weight_decay, b1, b2, eps;
+    int32_t step;
+    double* state; float* loss_hist;
+} hsimae_probe_step_params;
+int hsimae_probe_step(const hsimae_probe_step_params* p, void* stream);
+
+typedef struct {
+    const float* x; int32_t ldx;
+    const float* mean; const float* rstd;
+    const float* w; int32_t Kp;
+    int32_t n, D, C, first;
+    float* z; int32_t ldz;
+} hsimae_probe_logits_params;
+int hsimae_probe_logits(const hsimae_probe_logits_params* p, void* stream);
+
+typedef struct {
+    const float* w; int32_t Kp;
+    const float* mean; const float* rstd;
+    int32_t D, C, first;
+    float* weight; int32_t ldw;
+    float* bias;
+} hsimae_probe_fold_params;
+int hsimae_probe_fold(const hsimae_probe_fold_params* p, void* stream);
+
 /* ------------------------------------------------------------------ masked reconstruction of a whole scene (csrc/recon.hip)
  * ADDED under HSIMAE_VERSION 108 like the entry points above: nothing that 108 already had changes.  The way back from the
  * windows hsimae_forward reconstructs to the scene they were cut from, and the error maps and sums behind PSNR and the spectral
