@@ -145,6 +145,12 @@ class ClassProbParams(C.Structure):
                 ("label_map", vp), ("conf_map", vp), ("margin_map", vp), ("probs", vp), ("ldp", i32)]
 
 
+class ProbFilterParams(C.Structure):
+    _fields_ = [("probs", vp), ("ldp", i32), ("n", i32), ("C", i32), ("first", i32), ("H", i32), ("W", i32), ("row_of", vp),
+                ("guide", vp), ("G", i32), ("guide_scale", vp), ("radius", i32), ("a_s", f32), ("a_r", f32),
+                ("out_probs", vp), ("ldo", i32), ("label_map", vp), ("conf_map", vp), ("margin_map", vp)]
+
+
 class RowNormalizeParams(C.Structure):
     _fields_ = [("x", vp), ("ld", i32), ("N", i32), ("D", i32), ("out", vp), ("ldo", i32), ("norms", vp)]
 
@@ -303,6 +309,7 @@ SYMBOLS = {
     "hsimae_confusion_map": (C.c_int, [vp, vp, vp, vp, i64, i32, vp, vp, vp]),
     "hsimae_scores": (C.c_int, [vp, i32, vp, vp]),
     "hsimae_class_prob": (C.c_int, [C.POINTER(ClassProbParams), vp]),
+    "hsimae_prob_filter": (C.c_int, [C.POINTER(ProbFilterParams), vp]),
     "hsimae_row_normalize": (C.c_int, [C.POINTER(RowNormalizeParams), vp]),
     "hsimae_knn_topk": (C.c_int, [C.POINTER(KnnTopkParams), vp]),
     "hsimae_knn_vote": (C.c_int, [C.POINTER(KnnVoteParams), vp]),

@@ -33,7 +33,9 @@ from .finetune import DualViT, HSIViT, scene_views
 from .optim import FusedAdamW, FusedLAMB, weights_state_dict
 from .pretrain import seed_everything
 from .scene_data import SceneCubes, device_scene, unlabeled_pixels
+from .scene_pass import as_scene
 from .sched import CosineLRScheduler
+from .smooth import edge_filter_of, scene_guide
 
 
 class HSIdataset:
@@ -328,6 +330,14 @@ def test_model(data_cubes, test_gt, gt, save_dir, model_name, depth=12, dim=96, 
     return _score_and_save(pred.view(np.asarray(gt).shape), test_gt, gt, n_class, device, save_dir, model_name, save_images)
 
 
+def _smoothed_labels(filt, res, scene):
+    """The label map of a whole-scene result (on the device, with its probabilities) after `filt`, guided by the first principal
+    component of the device-resident `scene` it was computed from."""
+    H, W = (int(v) for v in res.labels.shape)
+    guide = None if filt.sigma_r is None else scene_guide(scene)
+    return filt.apply(res.probs, H, W, guide, first=1).labels
+
+
 def _scene_scores(pred, test_gt, gt, n_class, device, want_masked=False):
     """Model_Finetuning.py:285-290 on the device: the prediction map zeroed where `gt` is 0, counted against `test_gt`.
     want_masked=True: -> (scores, that zeroed map)."""
@@ -356,12 +366,15 @@ def _score_and_save(pred, test_gt, gt, n_class, device, save_dir, model_name, sa
 
 
 def test_model_scene(scene, test_gt, gt, save_dir, model_name, depth=12, dim=96, s_depth=6, device="cuda:0", batch_size=8192,
-                     views=(0,), save_images=False):
+                     views=(0,), save_images=False, smooth=None):
     """`test_model` from the scene itself: `scene` is the [H, W, C] `HSI_data` the reference cuts `data_cubes` from
     (Utils/Preprocessing.py:189-213, after GWPCA / norm), fp32 or fp64.  The same model, loaded the same way; the windows are
     cut on the device (HSIViT.predict_scene, at most `batch_size` pixels per chunk) instead of being built on the host.
     `views` other than (0,): the label of the class probabilities averaged over these flips of every window
     (HSIViT.classify_scene; "flips" = all four).  save_images=True also writes the reference's two colour-map PNGs.
+    `smooth`: None (the default) changes nothing; an EdgeFilter (True: the default one) filters the class-probability maps with
+    the scene's first principal component as the guide before the argmax (smooth.EdgeFilter, smooth.scene_guide), and the
+    smoothed map is what is scored, pictured and returned.
     -> (oa, aa, kappa, per-class recall, prediction map shaped like `gt`), as test_model returns them."""
     device = torch.device(device)
     views = scene_views(views)
@@ -371,7 +384,12 @@ def test_model_scene(scene, test_gt, gt, save_dir, model_name, depth=12, dim=96,
     n_class = int(np.max(gt) + 1)
     model = load_matching(eval_vit(9, c, n_class, dim, depth, s_depth, device), os.path.join(save_dir, model_name), device,
                           match_shapes=False)
-    if views != (0,) or save_images:
+    filt = edge_filter_of(smooth)
+    if filt is not None:
+        scene = as_scene(scene).to(device)                 # uploaded once: the classification and the guide share it
+        res = model.classify_scene(scene, batch_size=batch_size, views=views, return_probs=True, on_device=True)
+        pred = _smoothed_labels(filt, res, scene)
+    elif views != (0,) or save_images:
         pred = model.classify_scene(scene, batch_size=batch_size, views=views, on_device=True).labels
     else:
         pred = model.predict_scene(scene, batch_size=batch_size, on_device=True)
@@ -379,17 +397,19 @@ def test_model_scene(scene, test_gt, gt, save_dir, model_name, depth=12, dim=96,
 
 
 def knn_eval_scene(scene, train_index, train_labels, test_gt, gt, pretrained, depth=12, dim=96, s_depth=6, k=20, temperature=0.07,
-                   bank_flips=(0,), device="cuda:0", batch_size=8192, save_dir=None, model_name=None, save_images=False):
+                   bank_flips=(0,), device="cuda:0", batch_size=8192, save_dir=None, model_name=None, save_images=False, smooth=None):
     """The evaluation of a checkpoint that needs no fine-tuning: a weighted k-NN classifier on the frozen encoder's pooled features
     (Wu et al. 2018; DINO's knn_classifier), over the whole scene.  Inputs are what get_scene_set_dual returns: `scene` the
     processed [H, W, C] `HSI_data`, `train_index` / `train_labels` the labelled pixels that form the bank, `test_gt` / `gt` as in
     test_model_scene.  `pretrained`: the path of a state dict, loaded key-filtered as dual_branch_finetuning loads it: a
     pretraining checkpoint (HSIMAE) and a fine-tuned one (DualViT) both work, the classification head is never used.
     `k`, `temperature`, `bank_flips`: HSIViT.knn_scene's.  save_images=True writes test_model_scene's two pictures into
-    <save_dir>/<stem of model_name>/ (model_name defaults to the checkpoint's file name).
+    <save_dir>/<stem of model_name>/ (model_name defaults to the checkpoint's file name).  `smooth`: test_model_scene's, applied to
+    the vote's class probabilities.
     -> (oa, aa, kappa, per-class recall, prediction map shaped like `gt`), scored as test_model_scene scores."""
     device = torch.device(device)
     bank_flips = scene_views(bank_flips)
+    filt = edge_filter_of(smooth)
     if len(scene.shape) != 3:
         raise ValueError(f"scene must be [H, W, C], got shape {tuple(scene.shape)}")
     if save_images and save_dir is None:
@@ -397,15 +417,18 @@ def knn_eval_scene(scene, train_index, train_labels, test_gt, gt, pretrained, de
     c = int(scene.shape[2])
     n_class = int(np.max(gt) + 1)
     model = load_matching(eval_vit(9, c, n_class, dim, depth, s_depth, device), pretrained, device, match_shapes=True)
-    pred = model.knn_scene(scene, train_index, train_labels, k=k, temperature=temperature, bank_flips=bank_flips,
-                           batch_size=batch_size, on_device=True).labels
+    if filt is not None:
+        scene = as_scene(scene).to(device)                 # uploaded once: the classification and the guide share it
+    res = model.knn_scene(scene, train_index, train_labels, k=k, temperature=temperature, bank_flips=bank_flips,
+                          batch_size=batch_size, return_probs=filt is not None, on_device=True)
+    pred = res.labels if filt is None else _smoothed_labels(filt, res, scene)
     name = os.path.basename(str(pretrained)) if model_name is None else model_name
     return _score_and_save(pred, test_gt, gt, n_class, device, save_dir, name, save_images)
 
 
 def linear_probe_scene(scene, train_index, train_labels, test_gt, gt, pretrained, depth=12, dim=96, s_depth=6, bank_flips=(0,),
                        views=(0,), device="cuda:0", batch_size=8192, save_dir=None, model_name=None, save_images=False,
-                       **probe_kwargs):
+                       smooth=None, **probe_kwargs):
     """The evaluation masked-autoencoder work reports first: a linear classifier on the frozen encoder's pooled features, trained
     on the device on the cached features of the labelled pixels (HSIViT.probe_scene, probe.LinearProbe), over the whole scene.
     Inputs as knn_eval_scene's: `scene` the processed [H, W, C] `HSI_data`, `train_index` / `train_labels` the labelled pixels the
@@ -415,9 +438,11 @@ def linear_probe_scene(scene, train_index, train_labels, test_gt, gt, pretrained
     With `save_dir` the probed model's state dict (HSIViT's own, as dual_branch_finetuning saves it: encoder as loaded, head = the probe) is
     written as <save_dir>/<stem of model_name>_probe.pkl, which test_model_scene and the reference's test_model load;
     model_name defaults to the checkpoint's file name.  save_images=True also writes test_model_scene's two pictures.
+    `smooth`: test_model_scene's, applied to the probe's class probabilities.
     -> (oa, aa, kappa, per-class recall, prediction map shaped like `gt`), scored as test_model_scene scores."""
     device = torch.device(device)
     bank_flips, views = scene_views(bank_flips), scene_views(views)
+    filt = edge_filter_of(smooth)
     if len(scene.shape) != 3:
         raise ValueError(f"scene must be [H, W, C], got shape {tuple(scene.shape)}")
     if save_images and save_dir is None:
@@ -425,8 +450,11 @@ def linear_probe_scene(scene, train_index, train_labels, test_gt, gt, pretrained
     c = int(scene.shape[2])
     n_class = int(np.max(gt) + 1)
     model = load_matching(eval_vit(9, c, n_class, dim, depth, s_depth, device), pretrained, device, match_shapes=True)
-    pred = model.probe_scene(scene, train_index, train_labels, bank_flips=bank_flips, views=views, batch_size=batch_size,
-                             on_device=True, **probe_kwargs).labels
+    if filt is not None:
+        scene = as_scene(scene).to(device)                 # uploaded once: the classification and the guide share it
+    res = model.probe_scene(scene, train_index, train_labels, bank_flips=bank_flips, views=views, batch_size=batch_size,
+                            return_probs=filt is not None, on_device=True, **probe_kwargs)
+    pred = res.labels if filt is None else _smoothed_labels(filt, res, scene)
     model.last_probe.check()
     name = os.path.basename(str(pretrained)) if model_name is None else model_name
     if save_dir is not None:

@@ -682,6 +682,50 @@ typedef struct {
 } hsimae_class_prob_params;
 int hsimae_class_prob(const hsimae_class_prob_params* p, void* stream);
 
+/* ------------------------------------------------------------------ edge-preserving smoothing of the probability maps (csrc/smooth.hip)
+ * ADDED under HSIMAE_VERSION 108 like the entry points above: nothing that 108 already had changes.  The joint bilateral filter
+ * of Kang, Li and Benediktsson (EPF, IEEE TGRS 2014) over all class planes of a scene in one launch, and from the filtered
+ * probabilities the products of hsimae_class_prob.
+ *   probs    fp32 [n][ldp], the probabilities of n pixels (hsimae_class_prob's, hsimae_knn_vote's, a softmax); only the columns
+ *            [first, C) of rows that a pixel points to are ever read;
+ *   row_of   int32 [H * W] or NULL: row_of[pix] = the row of `probs` that belongs to pixel pix, negative (or >= n) = the pixel
+ *            has no row.  NULL: row = pixel (pixels n .. H W - 1 have none);
+ *   guide    fp32 [H * W][G], 1 <= G <= 4, and guide_scale, G fp32 factors IN DEVICE MEMORY (1 / (max - min) per channel);
+ *            both may be NULL with a_r = 0 and are then never read.  The guide is read only at pixels that have a row;
+ *   a_s, a_r fp32 of log2 e / (2 sigma_s^2) and log2 e / (2 sigma_r^2); a_r = 0 switches the range term off.
+ * Per output pixel i that has a row, in this order (every operation fp32):
+ *   for dy = -radius .. radius, for dx = -radius .. radius, j = i + (dy, dx); a tap outside the scene or without a row is
+ *   skipped (never read, no reflection);
+ *     d2 = 0; for g = 0 .. G - 1: d = fl(fl(I_j,g - I_i,g) * scale_g), d2 = fmaf(d, d, d2)            (a_r != 0 only)
+ *     arg = fl(a_s * (dy^2 + dx^2)); arg = fmaf(a_r, d2, arg) (a_r != 0 only); w = exp2(-arg) (v_exp_f32); the centre has w = 1
+ *     wsum = fl(wsum + w); acc_c = fmaf(w, p_j,c, acc_c) for first <= c < C
+ *   out_c = fl(acc_c * fl(1 / wsum)) for first <= c < C, exactly 0 for c < first.
+ *   out_probs fp32 [n][ldo] or NULL: out_c for c < C at the pixel's row (the input's row order); columns [C, ldo) and rows
+ *            that no pixel points to are never touched.  Must not overlap `probs`;
+ *   label_map int64 [H * W], required: argmax of out over [first, C), ties to the lowest index, NaN counts as the maximum;
+ *   conf_map fp32 [H * W] or NULL: out[label];  margin_map fp32 [H * W] or NULL: out[label] - the largest other out_c,
+ *            c >= first (out[label] itself when C - first = 1).
+ * A pixel without a row writes nothing: the caller initialises the maps.  Two pixels must not share a row.
+ * One workgroup per 16 x 16 tile, no host wait, no atomics: two runs are bit-identical.
+ * Refusals: params NULL -> HSIMAE_ENULL; H or W <= 0, H W >= 2^31, n < 0, C < 2, first outside [0, C), ldp < C, out_probs given
+ * with ldo < C, G outside [1, 4], radius outside [1, 8], a_s or a_r negative, NaN or infinite, out_probs overlapping probs ->
+ * HSIMAE_EDIMS; C > 1024, or more than 65535 tiles along H or W -> HSIMAE_EUNSUPPORTED; probs or label_map NULL, or guide or
+ * guide_scale NULL with a_r != 0 -> HSIMAE_ENULL; a pointer not aligned to its element -> HSIMAE_EALIGN.
+ * n = 0 -> HSIMAE_OK, nothing written. */
+typedef struct {
+    const float* probs; int32_t ldp;
+    int32_t n, C, first;
+    int32_t H, W;
+    const int32_t* row_of;
+    const float* guide; int32_t G;
+    const float* guide_scale;
+    int32_t radius;
+    float a_s, a_r;
+    float* out_probs; int32_t ldo;
+    int64_t* label_map; float* conf_map; float* margin_map;
+} hsimae_prob_filter_params;
+int hsimae_prob_filter(const hsimae_prob_filter_params* p, void* stream);
+
 /* ------------------------------------------------------------------ k-NN evaluation of frozen features (csrc/knn.hip)
  * ADDED under HSIMAE_VERSION 108 like the entry points above: nothing that 108 already had changes.  The weighted k-NN classifier a
  * pretrained encoder is judged by without fine-tuning (Wu et al. 2018; DINO's knn_classifier): L2-normalised features, the k
