@@ -27,6 +27,7 @@ from .knn import KNNClassifier  # noqa: F401
 from .cluster import KMeans, SceneClustering  # noqa: F401
 from .probe import LinearProbe  # noqa: F401
 from .smooth import EdgeFilter, as_guide, scene_guide, smooth_classification  # noqa: F401
+from .segment import SceneSegments, Superpixels, scene_segments, segment_classification  # noqa: F401
 from .recon import SceneReconstruction, reconstruct_scene, recon_eval_scene, window_centres  # noqa: F401
 from .colormap import label_to_colormap, save_label_png  # noqa: F401
 

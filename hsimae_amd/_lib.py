@@ -151,6 +151,17 @@ class ProbFilterParams(C.Structure):
                 ("out_probs", vp), ("ldo", i32), ("label_map", vp), ("conf_map", vp), ("margin_map", vp)]
 
 
+class SlicParams(C.Structure):
+    _fields_ = [("guide", vp), ("guide_scale", vp), ("G", i32), ("H", i32), ("W", i32), ("size", i32), ("w", f32), ("init", i32),
+                ("rounds", i32), ("centres", vp), ("centres_tmp", vp), ("counts", vp), ("labels", vp), ("dist", vp)]
+
+
+class SegmentVoteParams(C.Structure):
+    _fields_ = [("probs", vp), ("ldp", i32), ("n", i32), ("C", i32), ("first", i32), ("row_of", vp), ("labels", vp), ("H", i32),
+                ("W", i32), ("size", i32), ("mode", i32), ("fill", i32), ("out_probs", vp), ("ldo", i32), ("seg_count", vp),
+                ("label_map", vp), ("conf_map", vp), ("margin_map", vp)]
+
+
 class RowNormalizeParams(C.Structure):
     _fields_ = [("x", vp), ("ld", i32), ("N", i32), ("D", i32), ("out", vp), ("ldo", i32), ("norms", vp)]
 
@@ -310,6 +321,8 @@ SYMBOLS = {
     "hsimae_scores": (C.c_int, [vp, i32, vp, vp]),
     "hsimae_class_prob": (C.c_int, [C.POINTER(ClassProbParams), vp]),
     "hsimae_prob_filter": (C.c_int, [C.POINTER(ProbFilterParams), vp]),
+    "hsimae_slic": (C.c_int, [C.POINTER(SlicParams), vp]),
+    "hsimae_segment_vote": (C.c_int, [C.POINTER(SegmentVoteParams), vp]),
     "hsimae_row_normalize": (C.c_int, [C.POINTER(RowNormalizeParams), vp]),
     "hsimae_knn_topk": (C.c_int, [C.POINTER(KnnTopkParams), vp]),
     "hsimae_knn_vote": (C.c_int, [C.POINTER(KnnVoteParams), vp]),

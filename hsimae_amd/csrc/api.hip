@@ -463,6 +463,7 @@ extern "C" unsigned hs_variant_bits_kmeans();
 extern "C" unsigned hs_variant_bits_recon();
 extern "C" unsigned hs_variant_bits_probe();
 extern "C" unsigned hs_variant_bits_smooth();
+extern "C" unsigned hs_variant_bits_slic();
 #ifndef HS_KERNEL_SOURCE_HASH
 #define HS_KERNEL_SOURCE_HASH 0ULL
 #endif
@@ -480,7 +481,7 @@ int hsimae_version(void) { return HSIMAE_VERSION; }
 int hsimae_build_info(hsimae_build_info_t* out) {
     if (!out) return HSIMAE_ENULL;
     out->abi_version = HSIMAE_VERSION;
-    out->variant_bits = hs_variant_bits() | hs_variant_bits_gemm() | hs_variant_bits_attn() | hs_variant_bits_attn_wide() | hs_variant_bits_wgrad() | hs_variant_bits_elem() | hs_variant_bits_pack() | hs_variant_bits_fused_dec() | hs_variant_bits_fused_enc() | hs_variant_bits_loader() | hs_variant_bits_scene() | hs_variant_bits_gwpca() | hs_variant_bits_cls() | hs_variant_bits_clip() | hs_variant_bits_lamb() | hs_variant_bits_ema() | hs_variant_bits_prob() | hs_variant_bits_knn() | hs_variant_bits_kmeans() | hs_variant_bits_recon() | hs_variant_bits_probe() | hs_variant_bits_smooth();
+    out->variant_bits = hs_variant_bits() | hs_variant_bits_gemm() | hs_variant_bits_attn() | hs_variant_bits_attn_wide() | hs_variant_bits_wgrad() | hs_variant_bits_elem() | hs_variant_bits_pack() | hs_variant_bits_fused_dec() | hs_variant_bits_fused_enc() | hs_variant_bits_loader() | hs_variant_bits_scene() | hs_variant_bits_gwpca() | hs_variant_bits_cls() | hs_variant_bits_clip() | hs_variant_bits_lamb() | hs_variant_bits_ema() | hs_variant_bits_prob() | hs_variant_bits_knn() | hs_variant_bits_kmeans() | hs_variant_bits_recon() | hs_variant_bits_probe() | hs_variant_bits_smooth() | hs_variant_bits_slic();
     out->kernel_source_hash = HS_KERNEL_SOURCE_HASH;
     out->flags_hash = HS_BUILD_FLAGS_HASH;
     out->default_flags = HS_BUILD_DEFAULT_FLAGS;
@@ -987,6 +988,8 @@ int hsimae_confusion_map(const int64_t* gt_map, const int64_t* mask_map, const i
 int hsimae_scores(const int64_t* cm, int32_t C, double* out, void* stream) { return hs_scores(cm, C, out, S(stream)); }
 int hsimae_class_prob(const hsimae_class_prob_params* p, void* stream) { return p ? hs_class_prob(*p, S(stream)) : HSIMAE_ENULL; }
 int hsimae_prob_filter(const hsimae_prob_filter_params* p, void* stream) { return p ? hs_prob_filter(*p, S(stream)) : HSIMAE_ENULL; }
+int hsimae_slic(const hsimae_slic_params* p, void* stream) { return p ? hs_slic(*p, S(stream)) : HSIMAE_ENULL; }
+int hsimae_segment_vote(const hsimae_segment_vote_params* p, void* stream) { return p ? hs_segment_vote(*p, S(stream)) : HSIMAE_ENULL; }
 int hsimae_row_normalize(const hsimae_row_normalize_params* p, void* stream) { return p ? hs_row_normalize(*p, S(stream)) : HSIMAE_ENULL; }
 int hsimae_knn_topk(const hsimae_knn_topk_params* p, void* stream) { return p ? hs_knn_topk(*p, S(stream)) : HSIMAE_ENULL; }
 int hsimae_knn_vote(const hsimae_knn_vote_params* p, void* stream) { return p ? hs_knn_vote(*p, S(stream)) : HSIMAE_ENULL; }

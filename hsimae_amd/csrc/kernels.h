@@ -52,6 +52,8 @@ int hs_confusion_map(const int64_t* gt_map, const int64_t* mask_map, const int64
 int hs_scores(const int64_t* cm, int C, double* out, hipStream_t s);
 int hs_class_prob(const hsimae_class_prob_params& p, hipStream_t s);
 int hs_prob_filter(const hsimae_prob_filter_params& p, hipStream_t s);
+int hs_slic(const hsimae_slic_params& p, hipStream_t s);
+int hs_segment_vote(const hsimae_segment_vote_params& p, hipStream_t s);
 int hs_row_normalize(const hsimae_row_normalize_params& p, hipStream_t s);
 int hs_knn_topk(const hsimae_knn_topk_params& p, hipStream_t s);
 int hs_knn_vote(const hsimae_knn_vote_params& p, hipStream_t s);

@@ -35,7 +35,7 @@ from .pretrain import seed_everything
 from .scene_data import SceneCubes, device_scene, unlabeled_pixels
 from .scene_pass import as_scene
 from .sched import CosineLRScheduler
-from .smooth import edge_filter_of, scene_guide
+from .segment import spatial_labels, spatial_step_of
 
 
 class HSIdataset:
@@ -330,14 +330,6 @@ def test_model(data_cubes, test_gt, gt, save_dir, model_name, depth=12, dim=96, 
     return _score_and_save(pred.view(np.asarray(gt).shape), test_gt, gt, n_class, device, save_dir, model_name, save_images)
 
 
-def _smoothed_labels(filt, res, scene):
-    """The label map of a whole-scene result (on the device, with its probabilities) after `filt`, guided by the first principal
-    component of the device-resident `scene` it was computed from."""
-    H, W = (int(v) for v in res.labels.shape)
-    guide = None if filt.sigma_r is None else scene_guide(scene)
-    return filt.apply(res.probs, H, W, guide, first=1).labels
-
-
 def _scene_scores(pred, test_gt, gt, n_class, device, want_masked=False):
     """Model_Finetuning.py:285-290 on the device: the prediction map zeroed where `gt` is 0, counted against `test_gt`.
     want_masked=True: -> (scores, that zeroed map)."""
@@ -373,8 +365,9 @@ def test_model_scene(scene, test_gt, gt, save_dir, model_name, depth=12, dim=96,
     `views` other than (0,): the label of the class probabilities averaged over these flips of every window
     (HSIViT.classify_scene; "flips" = all four).  save_images=True also writes the reference's two colour-map PNGs.
     `smooth`: None (the default) changes nothing; an EdgeFilter (True: the default one) filters the class-probability maps with
-    the scene's first principal component as the guide before the argmax (smooth.EdgeFilter, smooth.scene_guide), and the
-    smoothed map is what is scored, pictured and returned.
+    the scene's first principal component as the guide before the argmax (smooth.EdgeFilter, smooth.scene_guide); a Superpixels
+    segments the scene's first three principal components and lets every superpixel decide by its mean class probabilities
+    (segment.Superpixels, segment.segment_vote).  The map after that step is what is scored, pictured and returned.
     -> (oa, aa, kappa, per-class recall, prediction map shaped like `gt`), as test_model returns them."""
     device = torch.device(device)
     views = scene_views(views)
@@ -384,11 +377,11 @@ def test_model_scene(scene, test_gt, gt, save_dir, model_name, depth=12, dim=96,
     n_class = int(np.max(gt) + 1)
     model = load_matching(eval_vit(9, c, n_class, dim, depth, s_depth, device), os.path.join(save_dir, model_name), device,
                           match_shapes=False)
-    filt = edge_filter_of(smooth)
+    filt = spatial_step_of(smooth)
     if filt is not None:
         scene = as_scene(scene).to(device)                 # uploaded once: the classification and the guide share it
         res = model.classify_scene(scene, batch_size=batch_size, views=views, return_probs=True, on_device=True)
-        pred = _smoothed_labels(filt, res, scene)
+        pred = spatial_labels(filt, res, scene)
     elif views != (0,) or save_images:
         pred = model.classify_scene(scene, batch_size=batch_size, views=views, on_device=True).labels
     else:
@@ -409,7 +402,7 @@ def knn_eval_scene(scene, train_index, train_labels, test_gt, gt, pretrained, de
     -> (oa, aa, kappa, per-class recall, prediction map shaped like `gt`), scored as test_model_scene scores."""
     device = torch.device(device)
     bank_flips = scene_views(bank_flips)
-    filt = edge_filter_of(smooth)
+    filt = spatial_step_of(smooth)
     if len(scene.shape) != 3:
         raise ValueError(f"scene must be [H, W, C], got shape {tuple(scene.shape)}")
     if save_images and save_dir is None:
@@ -421,7 +414,7 @@ def knn_eval_scene(scene, train_index, train_labels, test_gt, gt, pretrained, de
         scene = as_scene(scene).to(device)                 # uploaded once: the classification and the guide share it
     res = model.knn_scene(scene, train_index, train_labels, k=k, temperature=temperature, bank_flips=bank_flips,
                           batch_size=batch_size, return_probs=filt is not None, on_device=True)
-    pred = res.labels if filt is None else _smoothed_labels(filt, res, scene)
+    pred = res.labels if filt is None else spatial_labels(filt, res, scene)
     name = os.path.basename(str(pretrained)) if model_name is None else model_name
     return _score_and_save(pred, test_gt, gt, n_class, device, save_dir, name, save_images)
 
@@ -442,7 +435,7 @@ def linear_probe_scene(scene, train_index, train_labels, test_gt, gt, pretrained
     -> (oa, aa, kappa, per-class recall, prediction map shaped like `gt`), scored as test_model_scene scores."""
     device = torch.device(device)
     bank_flips, views = scene_views(bank_flips), scene_views(views)
-    filt = edge_filter_of(smooth)
+    filt = spatial_step_of(smooth)
     if len(scene.shape) != 3:
         raise ValueError(f"scene must be [H, W, C], got shape {tuple(scene.shape)}")
     if save_images and save_dir is None:
@@ -454,7 +447,7 @@ def linear_probe_scene(scene, train_index, train_labels, test_gt, gt, pretrained
         scene = as_scene(scene).to(device)                 # uploaded once: the classification and the guide share it
     res = model.probe_scene(scene, train_index, train_labels, bank_flips=bank_flips, views=views, batch_size=batch_size,
                             return_probs=filt is not None, on_device=True, **probe_kwargs)
-    pred = res.labels if filt is None else _smoothed_labels(filt, res, scene)
+    pred = res.labels if filt is None else spatial_labels(filt, res, scene)
     model.last_probe.check()
     name = os.path.basename(str(pretrained)) if model_name is None else model_name
     if save_dir is not None:

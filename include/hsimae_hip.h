@@ -726,6 +726,78 @@ typedef struct {
 } hsimae_prob_filter_params;
 int hsimae_prob_filter(const hsimae_prob_filter_params* p, void* stream);
 
+/* ------------------------------------------------------------------ superpixels and object-level class maps (csrc/slic.hip)
+ * ADDED under HSIMAE_VERSION 108 like the entry points above: nothing that 108 already had changes.  SLIC (Achanta et al., TPAMI
+ * 2012) in gSLIC's gather form (Ren and Reid 2011) over a guide image, and the vote of every superpixel over the class
+ * probabilities of its pixels.
+ *
+ * hsimae_slic.  guide fp32 [H * W][G], 1 <= G <= 4, and guide_scale, G fp32 factors IN DEVICE MEMORY (hsimae_prob_filter's pair).
+ *   Grid: ny = ceil(H / size), nx = ceil(W / size), K = ny nx centres, centre k = i nx + j; the home cell of pixel (y, x) is
+ *   (y ny / H, x nx / W) in integer arithmetic.  A centre is 8 floats: G features, y, x, pad (the pad keeps what it held).
+ *   init = 1: centre (i, j) is placed at pixel y = (2 i + 1) H / (2 ny), x = (2 j + 1) W / (2 nx) (integer division) with that
+ *   pixel's features fl(scale_g I_g) and pad 0; no gradient perturbation.  init = 0: `centres` is read as given.
+ *   Distance of pixel p = (y, x) to a centre c, every operation fp32, in this order:
+ *     d = 0; for g = 0 .. G - 1: t = fl(fl(scale_g I_g(p)) - c_g), d = fmaf(t, t, d);
+ *     dy = fl(y - c_y), dx = fl(x - c_x), s = fmaf(dx, dx, fl(dy dy)), d = fmaf(w, s, d)        w = fp32(compactness^2 / size^2).
+ *   Assign: a pixel compares the centres of the 3 x 3 cells around its home cell in ascending k, cells outside the grid left
+ *   out; the smallest d wins, a tie stays with the lower k, a NaN d loses to every number, and if all are NaN the home cell's
+ *   centre wins (with distance NaN).
+ *   Update: a centre becomes the mean (G features fl(scale_g I_g), y, x) of the pixels assigned to it: fp64 sums, one ascending-x
+ *   chain per scene row, then the row partials in ascending y; one fp64 division, one rounding to fp32.  A centre with no pixel
+ *   keeps its bits.
+ *   `rounds` times assign + update (one launch each, reading one centre buffer and writing the other), then one final assign:
+ *   labels int32 [H * W] = k, dist fp32 [H * W] or NULL = the winning d, counts int32 [K] or NULL = the pixels that carry label k.
+ *   The centres end in `centres` whatever the parity of `rounds`; centres_tmp is scratch of the same size (may be NULL with rounds = 0).
+ *   Connectivity is not enforced.  Every label of a pixel is one of the 3 x 3 cells around its home cell.
+ *   No atomics, no host wait: two runs are bit-identical.
+ *   Refusals: params NULL -> HSIMAE_ENULL; H or W <= 0, H W >= 2^31, G outside [1, 4], size outside [2, 32], rounds < 0, init not
+ *   0 or 1, w negative, NaN or infinite, an output overlapping an input or another output -> HSIMAE_EDIMS; guide, guide_scale,
+ *   centres or labels NULL, centres_tmp NULL with rounds > 0 -> HSIMAE_ENULL; a pointer not aligned to its element -> HSIMAE_EALIGN.
+ *
+ * hsimae_segment_vote.  labels int32 [H * W]: hsimae_slic's map for the same H, W and size (the vote relies on its locality: a
+ *   pixel whose label is not one of the 3 x 3 cells around its home cell belongs to no segment here).  probs fp32 [n][ldp],
+ *   row_of int32 [H * W] or NULL, first, C: as in hsimae_prob_filter; a pixel that has a row is "classified".
+ *   Per segment k with at least one classified pixel (cnt of them), v_c for first <= c < C:
+ *     mode 0: v_c = fp32(sum / cnt), the fp64 sum of probs[row, c] over its classified pixels in hsimae_slic's order (one
+ *             ascending-x chain per scene row, then the rows in ascending y), one fp64 division;
+ *     mode 1: v_c = fp32(m_c / cnt) in fp64, m_c = the classified pixels whose own argmax over [first, C) is c (ties to the
+ *             lowest index, NaN counts as the maximum).
+ *   label = argmax_c v_c (ties to the lowest index, NaN counts as the maximum), conf = v_label, margin = v_label - the largest
+ *   other v_c (v_label itself when C - first = 1): written to label_map int64 [H * W] (required), conf_map, margin_map fp32
+ *   [H * W] (or NULL) at the segment's classified pixels, and with fill = 1 at its other pixels too.
+ *   out_probs fp32 [K][ldo] or NULL: v_c for c < C (0 below `first`) in row k; seg_count int32 [K] or NULL: cnt.
+ *   A segment without a classified pixel writes only its seg_count (0): its pixels keep what the maps held, its out_probs row too.
+ *   One workgroup per segment, no atomics, no host wait: two runs are bit-identical.
+ *   Refusals: params NULL -> HSIMAE_ENULL; H or W <= 0, H W >= 2^31, n < 0, C < 2, first outside [0, C), ldp < C, out_probs given
+ *   with ldo < C, size outside [2, 32], mode or fill not 0 or 1, an output overlapping an input or another output ->
+ *   HSIMAE_EDIMS; C > 1024 -> HSIMAE_EUNSUPPORTED; probs, labels or label_map NULL -> HSIMAE_ENULL; a pointer not aligned to its
+ *   element -> HSIMAE_EALIGN. */
+typedef struct {
+    const float* guide;
+    const float* guide_scale;
+    int32_t G, H, W, size;
+    float w;
+    int32_t init, rounds;
+    float* centres;
+    float* centres_tmp;
+    int32_t* counts;
+    int32_t* labels;
+    float* dist;
+} hsimae_slic_params;
+int hsimae_slic(const hsimae_slic_params* p, void* stream);
+
+typedef struct {
+    const float* probs; int32_t ldp;
+    int32_t n, C, first;
+    const int32_t* row_of;
+    const int32_t* labels;
+    int32_t H, W, size, mode, fill;
+    float* out_probs; int32_t ldo;
+    int32_t* seg_count;
+    int64_t* label_map; float* conf_map; float* margin_map;
+} hsimae_segment_vote_params;
+int hsimae_segment_vote(const hsimae_segment_vote_params* p, void* stream);
+
 /* ------------------------------------------------------------------ k-NN evaluation of frozen features (csrc/knn.hip)
  * ADDED under HSIMAE_VERSION 108 like the entry points above: nothing that 108 already had changes.  The weighted k-NN classifier a
  * pretrained encoder is judged by without fine-tuning (Wu et al. 2018; DINO's knn_classifier): L2-normalised features, the k
