@@ -59,13 +59,17 @@ uint32_t sched_from_env() {
     if (!off("HSIMAE_DEC_SLAB")) b |= SC_DEC_SLAB;
     if (!off("HSIMAE_WGRAD_PLANAR")) b |= SC_PLANAR;
     if (!off("HSIMAE_FUSED_ATTN_BLOCK256_BWD")) b |= SC_ATTN_BLOCK256_BWD;
+    if (!off("HSIMAE_WGRAD_PAIR")) b |= SC_WGRAD_PAIR;
+    if (!off("HSIMAE_DEC_REDUCE_ONCE")) b |= SC_DEC_REDUCE_ONCE;
     return b;
 }
-struct SchedRec { uint32_t enc = 0, dec = 0; bool has_enc = false, has_dec = false; uint64_t gen = 0; };
+struct SchedRec { uint32_t enc = 0, dec = 0; bool has_enc = false, has_dec = false; uint64_t gen = 0; int64_t bytes = 0; };
 std::mutex g_sched_mu;
 std::unordered_map<const void*, SchedRec> g_sched;          // keyed by the workspace arena the forward filled
 uint64_t g_sched_gen = 0;
-void record_sched(const void* ws, bool enc, bool dec, uint32_t bits) {
+// bytes: the carve of the pass (Ws::bytes).  An allocator hands the address of a freed arena out again, often to a pass of another
+// shape: a record only speaks for a backward whose carve is the one the forward filled.
+void record_sched(const void* ws, int64_t bytes, bool enc, bool dec, uint32_t bits) {
     std::lock_guard<std::mutex> lk(g_sched_mu);
     // A process that keeps handing new arena addresses (caching allocator churn): drop the OLDEST half — never the entry being
     // recorded, and not the recent ones, whose backward may still be pending (clearing the whole map made a live
@@ -80,6 +84,7 @@ void record_sched(const void* ws, bool enc, bool dec, uint32_t bits) {
     }
     SchedRec& r = g_sched[ws];
     r.gen = ++g_sched_gen;
+    if (r.bytes != bytes) { r.has_enc = r.has_dec = false; r.bytes = bytes; }
     if (enc) {
         r.enc = bits; r.has_enc = true;
         // an encoder-only forward re-fills the arena: a decoder record of an EARLIER pass no longer describes what is in it
@@ -87,10 +92,11 @@ void record_sched(const void* ws, bool enc, bool dec, uint32_t bits) {
     }
     if (dec) { r.dec = bits; r.has_dec = true; }
 }
-int lookup_sched(const void* ws, bool need_enc, bool need_dec, uint32_t& enc, uint32_t& dec) {
+int lookup_sched(const void* ws, int64_t bytes, bool need_enc, bool need_dec, uint32_t& enc, uint32_t& dec) {
     std::lock_guard<std::mutex> lk(g_sched_mu);
     auto it = g_sched.find(ws);
-    if (it == g_sched.end() || (need_enc && !it->second.has_enc) || (need_dec && !it->second.has_dec)) return HSIMAE_ENOFORWARD;
+    if (it == g_sched.end() || it->second.bytes != bytes || (need_enc && !it->second.has_enc) || (need_dec && !it->second.has_dec))
+        return HSIMAE_ENOFORWARD;
     enc = it->second.enc; dec = it->second.dec;
     return HSIMAE_OK;
 }
@@ -251,11 +257,41 @@ int block_fwd(const BlkP& P, const BlockPlan& pl, const float* x_in, const BlkBu
     return hs_gemm(p, A_BF16, E_RES_F32, s);
 }
 
-// One Block backward: data grads (7 launches) + all weight/bias grads of the block (1 launch).
+// The weight-gradient launch of up to two consecutive blocks of a stack (BlockPlan::wgrad_pair), and of decoder_embed with the first
+// fusion pair: block_bwd deposits its 7 tasks here instead of launching, the stack's loop launches when the second block has
+// deposited or the stack ends, and reports the ranges the launch completed, in the order they were noted (back to front).  Every
+// task shares M.  The operands that are per-stream scratch alternate between two sets (plan.h Ws::scb), so the stream's order alone
+// keeps them alive until the launch.
+struct WgPair {
+    WgradParams g; int nblk = 0, nrange = 0; int64_t off[3], end[3];
+    WgPair() { std::memset(&g, 0, sizeof(g)); }
+    void note(int64_t o, int64_t e) { off[nrange] = o; end[nrange] = e; ++nrange; }
+};
+// launch what is pending on `s` and report its ranges (emit NULL: the caller reports them later)
+int wgpair_flush(WgPair& pr, int concurrent, hipStream_t s, Emitter* emit) {
+    if (pr.g.ntasks) {
+        pr.g.msplit = wgrad_msplit(wg_tiles(pr.g, 128), pr.g.M, concurrent);
+        CK(hs_wgrad(pr.g, s));
+    }
+    if (emit)
+        for (int i = 0; i < pr.nrange; ++i) CK((*emit)(pr.off[i], pr.end[i], s));
+    pr = WgPair();
+    return HSIMAE_OK;
+}
+// block [off, end) of a stack has run its block_bwd on `s`: launch and report now, or with the next block (pairing, not the last)
+int wgpair_block_done(WgPair& pr, bool pairing, bool last, int64_t off, int64_t end, int concurrent, hipStream_t s, Emitter* emit) {
+    pr.note(off, end);
+    ++pr.nblk;
+    if (pairing && pr.nblk < 2 && !last) return HSIMAE_OK;
+    return wgpair_flush(pr, concurrent, s, emit);
+}
+
+// One Block backward: data grads (7 launches) + all weight/bias grads of the block (1 launch; pend: deposited there, see WgPair).
 int block_bwd(const BlkP& P, const BlockPlan& pl, const BlkOff& o, float* grads, const float* x_in, const BlkBuf& b, int mode,
               int len_l, float* G0, const Scr& w, float* dx_out, int accumulate, hipStream_t s, int concurrent = 1,
-              const float* rs_a = nullptr, const float* rs_m = nullptr, int64_t* det_acc = nullptr) {
+              const float* rs_a = nullptr, const float* rs_m = nullptr, int64_t* det_acc = nullptr, WgradParams* pend = nullptr) {
     float* G1 = w.G1;
+    if (pend && !pl.wgrad_pair) return HSIMAE_EUNSUPPORTED;
     GemmParams p = gp();
     const int d = pl.d, dp = pl.dp, heads = pl.heads, h = pl.h, hp = pl.hp, Ts = pl.Ts, nsamples = pl.nsamples;
     const int64_t M = pl.M;
@@ -303,7 +339,9 @@ int block_bwd(const BlkP& P, const BlockPlan& pl, const BlkOff& o, float* grads,
     // (Round 4 measured the same work as two launches, each right behind the kernel that produced its operands: + 0.3 ms per step,
     //  removed in round 5.)
     auto run_wgrad = [&]() -> int {
-        WgradParams g; std::memset(&g, 0, sizeof(g));
+        WgradParams own; std::memset(&own, 0, sizeof(own));
+        WgradParams& g = pend ? *pend : own;
+        if (g.ntasks + 7 > 16) return HSIMAE_EDIMS;
         auto task = [&](int, const void* dO, int ldo, const hs_bf16* A, int lda, int N, int K, int64_t dW, int64_t db) {
             WgradTask& t = g.t[g.ntasks++];
             t.dO = dO; t.dO_f32 = 0; t.ldo = ldo; t.A = A; t.lda = lda; t.N = N; t.K = K; t.dW = grads + dW; t.ldw = K;
@@ -325,6 +363,7 @@ int block_bwd(const BlkP& P, const BlockPlan& pl, const BlkOff& o, float* grads,
 #endif
         { task(6, w.g0b, dp, b.g, pl.planar ? hp64 : hp, d, h, o.w2w, o.w2b); g.t[g.ntasks - 1].A_plane_rows = prow; }
         g.M = (int)M; g.det_base = grads; g.det_acc = det_acc;
+        if (pend) return HSIMAE_OK;                              // (128-tiles: no slab)
         g.slab = pl.wgrad_slab ? w.slab : nullptr;               // this stream's slab (NULL: float atomics on dW also in the 256 x 256-tile launches)
         g.msplit = wgrad_msplit(wg_tiles(g, 128), M, concurrent);
         return hs_wgrad(g, s);
@@ -556,7 +595,7 @@ static int forward_impl(const hsimae_config* cfg, const hsimae_io* io, void* str
     hipStream_t s = S(stream);
     const Geo& g = c.g; const float* P = io->params; const Ws& w = c.w;
     const uint32_t sc = sched_from_env();             // the pass's schedule: read here, recorded for the backward (plan.h SC_*)
-    record_sched(io->workspace, true, !encoder_only, sc);
+    record_sched(io->workspace, c.w.bytes, true, !encoder_only, sc);
     const BlockPlan enc = enc_plan(c, sc);
 
     MaskParams m; m.noise1 = io->noise1; m.noise2 = io->noise2; m.N = c.N; m.T = g.T; m.L = 9; m.len_t = c.len_t;
@@ -636,7 +675,7 @@ int hsimae_decode(const hsimae_config* cfg, const hsimae_io* io, const float* la
     hipStream_t s = S(stream);
     const Geo& g = c.g; const float* P = io->params; const Ws& w = c.w;
     const uint32_t sc = sched_from_env();
-    record_sched(io->workspace, false, true, sc);     // (the decoder's part only: an encoder pass in the same arena keeps its own record)
+    record_sched(io->workspace, c.w.bytes, false, true, sc);     // (the decoder's part only: an encoder pass in the same arena keeps its own record)
     GemmParams p = gp();                      // decoder_embed (Models.py:579)
     const float* lat_in = latent;
     if (g.Dp != g.D) {      // rows stored wider than the model: stage the caller's [Me][D] latent into a padded buffer (pad columns are zeros)
@@ -652,53 +691,68 @@ int hsimae_decode(const hsimae_config* cfg, const hsimae_io* io, const float* la
 
 // Backward of the encoder stacks + patch embedding, from d(x of the last encoder block) in w.G0.  Shared by
 // hsimae_backward (after the decoder) and hsimae_encode_backward (after `norm`).
-static int encoder_backward(const Ctx& c, const hsimae_io* io, float* grads, hipStream_t s, Emitter& emit, uint32_t sc) {
+// first: what the caller already deposited for the first fusion-block launch (decoder_embed's task and range), else empty.
+static int encoder_backward(const Ctx& c, const hsimae_io* io, float* grads, hipStream_t s, Emitter& emit, uint32_t sc, WgPair& first) {
     const Geo& g = c.g; const float* P = io->params; const Ws& w = c.w; const PLayout& L = c.L;
     const BlockPlan enc = enc_plan(c, sc);
-    for (int i = g.nfus - 1; i >= 0; --i) {
+    // paired weight-gradient launches: block k of a stack (counted from its last) leaves its operands in scratch set k % 2
+    const bool pairing = enc.wgrad_pair;
+    float* dx = w.G0;               // d(x0) once the blocks are through
+    for (int i = g.nfus - 1, k = 0; i >= 0; --i, ++k) {
         BlkP bp = resolve(L.bf[i], c.W.bf[i], P, io->wpk, c.W, g.h);
         const float* xin = (i > 0) ? w.bf[i - 1].x2 : (g.has_axis ? w.b2[g.sdepth - 1].x2 : w.x0);
         const DropRs rf = drop_rs(io, (g.has_axis ? 2 * g.sdepth : 0) + i, c.Me);
-        CK(block_bwd(bp, enc, L.bf[i], grads, xin, w.bf[i], 0, c.len_l, w.G0, w.sc, w.G0, 0, s, 1, rf.a, rf.m, io->det_acc));
-        CK(emit(L.bf[i].n1w, L.bf[i].end, s));
+        CK(block_bwd(bp, enc, L.bf[i], grads, xin, w.bf[i], 0, c.len_l, w.G0, (pairing && (k & 1)) ? w.scb : w.sc, w.G0, 0, s, 1, rf.a, rf.m,
+                     io->det_acc, pairing ? &first.g : nullptr));
+        CK(wgpair_block_done(first, pairing, i == 0, L.bf[i].n1w, L.bf[i].end, 1, s, &emit));
     }
     if (g.has_axis) {
-        // d(x1 + x2) feeds both stacks (Models.py:564); the spectral stack's backward runs on the side stream
+        // d(x1 + x2) in G0 feeds both stacks (Models.py:564) and neither overwrites it: the spatial stack's dX goes to G2, the spectral
+        // stack's, which runs on the side stream, to G3; the spatial stack's last step accumulates onto G3 after the join
         Side& sd = side();
         const bool forked = sd.ok && g.sdepth > 1;
-        CK((int)hipMemcpyAsync(w.G2, w.G0, c.Me * g.Dp * 4, hipMemcpyDeviceToDevice, s));
         if (forked) {
             CK((int)hipEventRecord(sd.fork, s));
             CK((int)hipStreamWaitEvent(sd.s, sd.fork, 0));
         }
         hipStream_t s2 = forked ? sd.s : s;
-        const Scr& scr2 = forked ? w.sc2 : w.sc;
+        // (pairing on one stream: the spectral stack's pending operands must outlive the spatial block that follows, so it takes the
+        //  side stream's sets there too)
+        const Scr& scr2 = (forked || pairing) ? w.sc2 : w.sc;
         // with a bucket stream every block's range is reported as soon as its kernels are enqueued (the consumer waits
         // for the right stream through an event); without one the side stream's ranges wait for the join
         const bool per_block = emit.bucket != nullptr || !forked;
-        for (int i = g.sdepth - 1; i >= 0; --i) {
+        Emitter* em = per_block ? &emit : nullptr;
+        const int conc = forked ? 2 : 1, top = g.sdepth - 1;
+        WgPair pr1, pr2;
+        for (int i = top, k = 0; i >= 0; --i, ++k) {
+            const bool alt = pairing && (k & 1);
             BlkP b2 = resolve(L.b2[i], c.W.b2[i], P, io->wpk, c.W, g.h);
             const DropRs r1 = drop_rs(io, i, c.Me), r2d = drop_rs(io, g.sdepth + i, c.Me);
             const float* xin2 = (i > 0) ? w.b2[i - 1].x2 : w.x0;
-            CK(block_bwd(b2, enc, L.b2[i], grads, xin2, w.b2[i], 2, c.len_l, w.G0, scr2, w.G0, 0, s2, forked ? 2 : 1, r2d.a, r2d.m, io->det_acc));
-            if (per_block) CK(emit(L.b2[i].n1w, L.b2[i].end, s2));
+            CK(block_bwd(b2, enc, L.b2[i], grads, xin2, w.b2[i], 2, c.len_l, i == top ? w.G0 : w.G3, alt ? w.sc2b : scr2, w.G3, 0, s2, conc,
+                         r2d.a, r2d.m, io->det_acc, pairing ? &pr2.g : nullptr));
+            CK(wgpair_block_done(pr2, pairing, i == 0, L.b2[i].n1w, L.b2[i].end, conc, s2, em));
             if (i == 0 && forked) {                 // the spatial stack's last step accumulates onto the spectral dX
                 CK((int)hipEventRecord(sd.join, sd.s));
                 CK((int)hipStreamWaitEvent(s, sd.join, 0));
             }
             BlkP b1 = resolve(L.b1[i], c.W.b1[i], P, io->wpk, c.W, g.h);
             const float* xin1 = (i > 0) ? w.b1[i - 1].x2 : w.x0;
-            float* out = (i == 0) ? w.G0 : w.G2;
-            CK(block_bwd(b1, enc, L.b1[i], grads, xin1, w.b1[i], 1, c.len_l, w.G2, w.sc, out, i == 0, s, forked ? 2 : 1, r1.a, r1.m, io->det_acc));
-            if (per_block) CK(emit(L.b1[i].n1w, L.b1[i].end, s));
+            float* out = (i == 0) ? w.G3 : w.G2;
+            CK(block_bwd(b1, enc, L.b1[i], grads, xin1, w.b1[i], 1, c.len_l, i == top ? w.G0 : w.G2, alt ? w.scb : w.sc, out, i == 0, s, conc,
+                         r1.a, r1.m, io->det_acc, pairing ? &pr1.g : nullptr));
+            CK(wgpair_block_done(pr1, pairing, i == 0, L.b1[i].n1w, L.b1[i].end, conc, s, em));
         }
         if (!per_block) {     // back-to-front, all complete on the caller's stream by now
             for (int i = g.sdepth - 1; i >= 0; --i) CK(emit(L.b2[i].n1w, L.b2[i].end, s));
             for (int i = g.sdepth - 1; i >= 0; --i) CK(emit(L.b1[i].n1w, L.b1[i].end, s));
         }
+        dx = w.G3;
     }
+    if (first.g.ntasks || first.nrange) CK(wgpair_flush(first, 1, s, &emit));      // (no fusion block took the caller's deposit)
     // patch_embed.proj: only the kept tokens carry gradient (Models.py:528); no input gradient
-    CK(wgrad_one(w.G0, true, g.Dp, w.a_pe, 96, g.D, 72, c.Me, (g.D + 127) / 128, grads, L.pew, L.peb, io->det_acc, s));
+    CK(wgrad_one(dx, true, g.Dp, w.a_pe, 96, g.D, 72, c.Me, (g.D + 127) / 128, grads, L.pew, L.peb, io->det_acc, s));
     CK(emit(0, L.peb + g.D, s));
     return HSIMAE_OK;
 }
@@ -706,7 +760,9 @@ static int encoder_backward(const Ctx& c, const hsimae_io* io, float* grads, hip
 // Backward of the decoder from dL/dpred (bf16 [Md][96] in w.dpred) down to dL/d(latent) in w.du [Me][D]
 // (autograd of Models.py:573-601): decoder_pred / decoder_norm, the decoder blocks, the sequence assembly and
 // decoder_embed (its weight gradient included).  Shared by hsimae_backward and hsimae_decode_backward.
-static int decoder_backward(const Ctx& c, const hsimae_io* io, float* grads, hipStream_t s, Emitter& emit, uint32_t sc) {
+// fold: decoder_embed's weight gradient becomes a task of that pending launch (same M as the encoder blocks; both operands are bf16
+// and stay untouched to the end of the pass) instead of a launch of its own here.
+static int decoder_backward(const Ctx& c, const hsimae_io* io, float* grads, hipStream_t s, Emitter& emit, uint32_t sc, WgPair* fold) {
     const Geo& g = c.g; const float* P = io->params; const Ws& w = c.w; const PLayout& L = c.L;
     const float* zlast = w.bd[g.ddepth - 1].x2;
     GemmParams p = gp();
@@ -721,9 +777,26 @@ static int decoder_backward(const Ctx& c, const hsimae_io* io, float* grads, hip
 
     const DecPlan dec = plan_dec(c.g.Dd, c.g.Hd, c.g.hdec, c.g.TL, sc);
     const BlockPlan lay = dec_block_plan(c, sc);
+    // one reduce launch for up to kDecReduceBlocks blocks, each with its own slab; their ranges are reported after it
+    const bool once = dec.reduce_once && w.dec_slabs != nullptr;
+    DecBlockGrads rg[kDecReduceBlocks]; float* rslab[kDecReduceBlocks]; int rblk[kDecReduceBlocks]; int nr = 0;
     for (int i = g.ddepth - 1; i >= 0; --i) {
         BlkP bp = resolve(L.bd[i], c.W.bd[i], P, io->wpk, c.W, g.hdec);
         const float* xin = (i == 0) ? w.yfull : w.bd[i - 1].x2;
+        if (dec.fused && once) {
+            DecBlockBwd d;
+            d.x = xin; d.x1 = w.bd[i].x1; d.dy = w.G0; d.dx1_tmp = w.G1; d.dx = w.G0; d.o = w.bd[i].o; d.lse = w.bd[i].lse;
+            d.nsamples = c.N; d.Ts = g.TL; d.slab = dec_slab(w.slab, w.dec_slabs, nr); d.defer_reduce = true;
+            rg[nr] = dec_grads(grads, L.bd[i], HsDet{grads, reinterpret_cast<long long*>(io->det_acc)});
+            rslab[nr] = d.slab; rblk[nr] = i;
+            CK(hs_dec_block_bwd(bp, rg[nr], d, s));
+            if (++nr == kDecReduceBlocks || i == 0) {
+                CK(hs_dec_dw_reduce(rg, rslab, nr, c.N, g.hdec, s));
+                for (int k = 0; k < nr; ++k) CK(emit(L.bd[rblk[k]].n1w, L.bd[rblk[k]].end, s));
+                nr = 0;
+            }
+            continue;
+        }
         if (dec.fused) {
             // MLP half then attention half, both persistent with the block's weight gradients held in registers
             // (measured equal to "row-tile kernel + wgrad operands through HBM" at d = 64, with 0.7 GB less traffic)
@@ -744,6 +817,14 @@ static int decoder_backward(const Ctx& c, const hsimae_io* io, float* grads, hip
     p = gp();
     p.A = w.dyb; p.lda = g.Ddp; p.M = (int)c.Me; p.N = g.Dp; p.K = g.Ddp; p.n_valid = g.D; p.W = io->wpk + c.W.deT; p.out = w.du; p.ldo = g.Dp;
     CK(hs_gemm(p, A_BF16, E_F32, s));
+    if (fold) {
+        WgradParams& q = fold->g;
+        WgradTask& t = q.t[q.ntasks++];
+        t.dO = w.dyb; t.dO_f32 = 0; t.ldo = g.Ddp; t.A = w.lat; t.lda = g.Dp; t.N = g.Dd; t.K = g.D;
+        t.dW = grads + L.dew; t.ldw = g.D; t.db = grads + L.deb; t.dO_rowscale = nullptr;
+        q.M = (int)c.Me; q.det_base = grads; q.det_acc = io->det_acc;
+        return HSIMAE_OK;
+    }
     return wgrad_one(w.dyb, false, g.Ddp, w.lat, g.Dp, g.Dd, g.D, c.Me, ((g.Dd + 127) / 128) * ((g.D + 127) / 128), grads, L.dew, L.deb,
                      io->det_acc, s);
 }
@@ -767,7 +848,7 @@ static int begin_backward(BwdPass& b, const hsimae_config* cfg, const hsimae_io*
                           hsimae_bucket_cb cb, void* user, void* stream) {
     CK(make_ctx(cfg, io, b.c, true));
     if (!grads || !have_args || ((stacks & DECODER) && !io->ids_restore)) return HSIMAE_ENULL;
-    CK(lookup_sched(io->workspace, (stacks & ENCODER) != 0, (stacks & DECODER) != 0, b.sc_enc, b.sc_dec));
+    CK(lookup_sched(io->workspace, b.c.w.bytes, (stacks & ENCODER) != 0, (stacks & DECODER) != 0, b.sc_enc, b.sc_dec));
     b.s = S(stream);
     if (io->det_acc) CK((int)hipMemsetAsync(io->det_acc, 0, (size_t)b.c.L.total * 8, b.s));
     b.emit = Emitter{cb, user, cb ? S(io->bucket_stream) : nullptr, 0, grads, io->det_acc};
@@ -778,10 +859,14 @@ int hsimae_backward(const hsimae_config* cfg, const hsimae_io* io, float* grads,
                     void* stream) {
     BwdPass b; CK(begin_backward(b, cfg, io, ENCODER | DECODER, true, grads, cb, user, stream));
     const Ctx& c = b.c; const Geo& g = c.g; const PLayout& L = c.L;
-    CK(decoder_backward(c, io, grads, b.s, b.emit, b.sc_dec));
+    // where the fusion blocks pair their weight-gradient launches, the first of them takes decoder_embed's along
+    WgPair first;
+    const bool fold = g.nfus > 0 && enc_plan(c, b.sc_enc).wgrad_pair;
+    CK(decoder_backward(c, io, grads, b.s, b.emit, b.sc_dec, fold ? &first : nullptr));
     CK(norm_backward(c, io, c.w.du, grads, b.s));
-    CK(b.emit(L.nw, L.deb + g.Dd, b.s));
-    return encoder_backward(c, io, grads, b.s, b.emit, b.sc_enc);
+    if (fold) first.note(L.nw, L.deb + g.Dd);         // reported after that launch, still ahead of the fusion blocks' ranges
+    else CK(b.emit(L.nw, L.deb + g.Dd, b.s));
+    return encoder_backward(c, io, grads, b.s, b.emit, b.sc_enc, first);
 }
 
 int hsimae_decode_backward(const hsimae_config* cfg, const hsimae_io* io, const float* dpred, float* dlatent, float* grads,
@@ -789,7 +874,7 @@ int hsimae_decode_backward(const hsimae_config* cfg, const hsimae_io* io, const 
     BwdPass b; CK(begin_backward(b, cfg, io, DECODER, dpred && dlatent, grads, cb, user, stream));
     const Ctx& c = b.c; const Geo& g = c.g; const Ws& w = c.w; const PLayout& L = c.L; hipStream_t s = b.s;
     CK(hs_rows_pad_bf16(dpred, w.dpred, c.Md, 72, 96, s));
-    CK(decoder_backward(c, io, grads, s, b.emit, b.sc_dec));
+    CK(decoder_backward(c, io, grads, s, b.emit, b.sc_dec, nullptr));
     CK(b.emit(L.dew, L.deb + g.Dd, s));
     return (int)hipMemcpy2DAsync(dlatent, (size_t)g.D * 4, w.du, (size_t)g.Dp * 4, (size_t)g.D * 4, (size_t)c.Me, hipMemcpyDeviceToDevice, s);
 }
@@ -805,7 +890,8 @@ int hsimae_encode_backward(const hsimae_config* cfg, const hsimae_io* io, const 
     }
     CK(norm_backward(c, io, dlat, grads, s));
     CK(b.emit(L.nw, L.nb + g.D, s));
-    return encoder_backward(c, io, grads, s, b.emit, b.sc_enc);
+    WgPair first;
+    return encoder_backward(c, io, grads, s, b.emit, b.sc_enc, first);
 }
 
 // ---------------------------------------------------------------------- per-kernel entry points

@@ -1853,12 +1853,14 @@ __global__ __launch_bounds__(512, 2) void dec_bwd_attn_kernel(DecBwdAttnArgs p) 
 // Sums the workgroups' weight-gradient partials of one decoder block ([workgroup][slot][thread], written by the two
 // persistent backward kernels) and adds them into the block's dW tensors: workgroup = slot, thread = the committing thread
 // of the backward kernels (same index map as their atomic commits).  Reads are coalesced 2-KB rows; the sum runs in a fixed
-// order, so these gradients are bit-reproducible without the fixed-point shadow buffer.
-struct DecDwReduceArgs {
-    const float* slab; int nwg; int h;
+// order, so these gradients are bit-reproducible without the fixed-point shadow buffer.  One launch takes up to kDecReduceBlocks
+// blocks, each with a slab of its own: blockIdx.y picks the block, and what a block's sums are does not depend on the others.
+struct DecDwReduceBlk {
+    const float* slab;
     float *g_w1w, *g_w3w, *g_w2w, *g_qw, *g_kw, *g_vw, *g_pw;
     float *g_n2w, *g_n2b, *g_w2b, *g_w1b, *g_w3b, *g_n1w, *g_n1b, *g_pb, *g_qb, *g_kb, *g_vb;
 };
+struct DecDwReduceArgs { int nwg; int h; DecDwReduceBlk b[hsplan::kDecReduceBlocks]; };
 // fixed-order sum of src[w * stride], w < nwg, with 16 loads in flight per thread (the kernel is a pure latency-bound gather)
 __device__ __forceinline__ float slab_sum(const float* src, size_t stride, int nwg) {
     float acc[16];
@@ -1876,7 +1878,8 @@ __device__ __forceinline__ float slab_sum(const float* src, size_t stride, int n
         for (int i = 0; i < o; ++i) acc[i] += acc[i + o];
     return acc[0];
 }
-__global__ __launch_bounds__(NT_) void dec_dw_reduce_kernel(DecDwReduceArgs p) {
+__global__ __launch_bounds__(NT_) void dec_dw_reduce_kernel(DecDwReduceArgs a) {
+    const DecDwReduceBlk& p = a.b[blockIdx.y];
     const int slot = blockIdx.x, tid = threadIdx.x;
     if (slot >= kDwSlots) {                               // the bias / LayerNorm vectors: [workgroup][kVec]
         // the bias / LayerNorm vectors: one WAVE per output element (9 vectors of 64 and 2 of 192 = 960 elements, 8 per
@@ -1895,10 +1898,10 @@ __global__ __launch_bounds__(NT_) void dec_dw_reduce_kernel(DecDwReduceArgs p) {
 #pragma unroll
         for (int i = 1; i < 11; ++i) if (which == i) { o = off[i]; d = dst[i]; }
         const bool wide = which == 3 || which == 4;
-        if (wide && c >= p.h) return;                    // w1b / w3b: padded to 192, valid below the hidden width
+        if (wide && c >= a.h) return;                    // w1b / w3b: padded to 192, valid below the hidden width
         const float* src = p.slab + kSlabTileFloats + o + c;
         float v = 0.f;
-        for (int w = lane; w < p.nwg; w += 64) {
+        for (int w = lane; w < a.nwg; w += 64) {
             const float* q = src + (size_t)w * kVec;
             v += q[0];
         }
@@ -1906,17 +1909,17 @@ __global__ __launch_bounds__(NT_) void dec_dw_reduce_kernel(DecDwReduceArgs p) {
         if (lane == 0) d[c] += v;
         return;
     }
-    const float v = slab_sum(p.slab + (size_t)slot * NT_ + tid, (size_t)kDwSlots * NT_, p.nwg);
+    const float v = slab_sum(p.slab + (size_t)slot * NT_ + tid, (size_t)kDwSlots * NT_, a.nwg);
     const int lane = tid & 63, c16 = lane & 15, g = lane >> 4, wave = tid >> 6;
     if (slot < kDwSlotsMlp) {
         const int r = slot & 3, k2 = (slot >> 2) & 1, ct = slot >> 3, t = ct % 3, c = ct / 3;
         const int nt12 = (wave >> 1) * 3 + t, mat = nt12 >> 2, nt = nt12 & 3;
         const int n = nt * 16 + g * 4 + r, k = ((wave & 1) * 2 + k2) * 16 + c16;
         if (mat == 0) {                                   // dW2[d][h]: row n (model dim), column c*64 + k (hidden)
-            if (c * 64 + k < p.h) p.g_w2w[(size_t)n * p.h + c * 64 + k] += v;
+            if (c * 64 + k < a.h) p.g_w2w[(size_t)n * a.h + c * 64 + k] += v;
         } else {                                          // dW1 / dW3 [h][d]: row c*64 + n (hidden), column k
             float* dst = mat == 1 ? p.g_w1w : p.g_w3w;
-            if (c * 64 + n < p.h) dst[(size_t)(c * 64 + n) * D + k] += v;
+            if (c * 64 + n < a.h) dst[(size_t)(c * 64 + n) * D + k] += v;
         }
     } else {
         const int a = slot - kDwSlotsMlp;
@@ -1947,6 +1950,9 @@ int launch_attn_fwd(const DecAttnFwdArgs& a, hipStream_t s) {
 
 }  // namespace
 
+// workgroups of the two backward kernels (persistent: one per CU) = partials per slab
+static int dec_bwd_grid(int nsamples) { return nsamples < 256 ? nsamples : 256; }
+
 template <int MT>
 int launch_bwd(const DecBwdMlpArgs& a, const DecBwdAttnArgs& b, hipStream_t s) {
     using L = DL<MT>;
@@ -1955,17 +1961,9 @@ int launch_bwd(const DecBwdMlpArgs& a, const DecBwdAttnArgs& b, hipStream_t s) {
     static_assert(3 * IMG >= L::R * LX * 4, "fp32 staging tile must fit over Gc|DH1|DH3");
     static_assert(LDS_A - 5 * IMG >= 16 * IR * 2, "image overrun of the unguarded du2 product must stay inside the allocation");
     constexpr int LDS_B = L::BWD_ATTN_LDS;
-    const int grid = a.nsamples < 256 ? a.nsamples : 256;      // persistent: one workgroup per CU
+    const int grid = dec_bwd_grid(a.nsamples);
     hs_enqueue_lds<dec_bwd_mlp_kernel<MT>>(dim3(grid), dim3(NT_), LDS_A, s, a);
     hs_enqueue_lds<dec_bwd_attn_kernel<MT>>(dim3(grid), dim3(NT_), LDS_B, s, b);
-    if (a.slab) {
-        DecDwReduceArgs r;
-        r.slab = a.slab; r.nwg = grid; r.h = a.w.h;
-        r.g_w1w = a.g_w1w; r.g_w3w = a.g_w3w; r.g_w2w = a.g_w2w; r.g_qw = b.g_qw; r.g_kw = b.g_kw; r.g_vw = b.g_vw; r.g_pw = b.g_pw;
-        r.g_n2w = a.g_n2w; r.g_n2b = a.g_n2b; r.g_w2b = a.g_w2b; r.g_w1b = a.g_w1b; r.g_w3b = a.g_w3b;
-        r.g_n1w = b.g_n1w; r.g_n1b = b.g_n1b; r.g_pb = b.g_pb; r.g_qb = b.g_qb; r.g_kb = b.g_kb; r.g_vb = b.g_vb;
-        hipLaunchKernelGGL(dec_dw_reduce_kernel, dim3(kDwSlots + (9 * D + 2 * HPD + NT_ / 64 - 1) / (NT_ / 64)), dim3(NT_), 0, s, r);
-    }
     return (int)hipGetLastError();
 }
 
@@ -1985,6 +1983,23 @@ static DecW dec_w(const BlockW& b) {
     return w;
 }
 
+int hs_dec_dw_reduce(const DecBlockGrads* g, float* const* slabs, int nblocks, int nsamples, int h, hipStream_t s) {
+    if (nblocks < 1 || nblocks > hsplan::kDecReduceBlocks) return HS_EUNSUPPORTED;
+    DecDwReduceArgs r;
+    std::memset(&r, 0, sizeof(r));
+    r.nwg = dec_bwd_grid(nsamples); r.h = h;
+    for (int i = 0; i < nblocks; ++i) {
+        DecDwReduceBlk& b = r.b[i];
+        const DecBlockGrads& q = g[i];
+        b.slab = slabs[i];
+        b.g_w1w = q.w1w; b.g_w3w = q.w3w; b.g_w2w = q.w2w; b.g_qw = q.qw; b.g_kw = q.kw; b.g_vw = q.vw; b.g_pw = q.pw;
+        b.g_n2w = q.n2w; b.g_n2b = q.n2b; b.g_w2b = q.w2b; b.g_w1b = q.w1b; b.g_w3b = q.w3b;
+        b.g_n1w = q.n1w; b.g_n1b = q.n1b; b.g_pb = q.pb; b.g_qb = q.qb; b.g_kb = q.kb; b.g_vb = q.vb;
+    }
+    hipLaunchKernelGGL(dec_dw_reduce_kernel, dim3(kDwSlots + (9 * D + 2 * HPD + NT_ / 64 - 1) / (NT_ / 64), nblocks), dim3(NT_), 0, s, r);
+    return (int)hipGetLastError();
+}
+
 int hs_dec_block_bwd(const BlockW& bp, const DecBlockGrads& g, const DecBlockBwd& p, hipStream_t s) {
     DecBwdMlpArgs a;
     a.x1 = p.x1; a.dy = p.dy; a.dx1 = p.dx1_tmp; a.nsamples = p.nsamples; a.Ts = p.Ts; a.w = dec_w(bp); a.w2T = bp.w2T; a.w13T = bp.w13T;
@@ -1997,9 +2012,11 @@ int hs_dec_block_bwd(const BlockW& bp, const DecBlockGrads& g, const DecBlockBwd
     b.g_n1w = g.n1w; b.g_n1b = g.n1b; b.g_qw = g.qw; b.g_qb = g.qb; b.g_kw = g.kw; b.g_kb = g.kb; b.g_vw = g.vw;
     b.g_vb = g.vb; b.g_pw = g.pw; b.g_pb = g.pb; b.det = g.det; b.slab = p.slab;
     const int mt = (p.Ts + 15) / 16;
-    if (mt <= 4) return launch_bwd<4>(a, b, s);
-    if (mt <= 7) return launch_bwd<7>(a, b, s);
-    return HS_EUNSUPPORTED;
+    if (mt > 7) return HS_EUNSUPPORTED;
+    if (const int rc = mt <= 4 ? launch_bwd<4>(a, b, s) : launch_bwd<7>(a, b, s)) return rc;
+    // the slab's partials into the gradients: here, or by the caller's one hs_dec_dw_reduce over several blocks
+    if (!p.slab || p.defer_reduce) return HS_OK;
+    return hs_dec_dw_reduce(&g, &p.slab, 1, p.nsamples, bp.h, s);
 }
 
 // attention half of the block only (x1 = x + proj(attention(LN1 x)); O and logsumexp kept for the backward)

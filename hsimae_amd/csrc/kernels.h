@@ -99,8 +99,12 @@ constexpr long long kDecSlabFloats = HSIMAE_DEC_BLOCK_SLAB_FLOATS;
 struct DecBlockBwd {
     const float *x, *x1, *dy; float *dx1_tmp, *dx; const hs_bf16* o; const float* lse;
     int nsamples, Ts; float* slab = nullptr;
+    bool defer_reduce = false;    // slab given: leave its partials for the caller's hs_dec_dw_reduce
 };
 int hs_dec_block_bwd(const BlockW& w, const DecBlockGrads& g, const DecBlockBwd& p, hipStream_t s);
+// The reduce launch of up to hsplan::kDecReduceBlocks blocks whose hs_dec_block_bwd ran with defer_reduce, each into its own slab,
+// at the same nsamples: g[i] / slabs[i] of block i.  A block's sums are what its own reduce launch gives, bit for bit.
+int hs_dec_dw_reduce(const DecBlockGrads* g, float* const* slabs, int nblocks, int nsamples, int h, hipStream_t s);
 
 // ------------------------------------------------------------------ attn.hip / attn_wide.hip (attention half of an encoder Block)
 // blk128_* at D = 128 (8 heads of 16), blk256_* at D = 256 (16 heads of 16), <= 32 tokens: LN1 + q|k|v + attention + projection +

@@ -217,10 +217,16 @@ struct Scr { float* G1; float* du; hs_bf16* dh13; hs_bf16* dob; hs_bf16* dqkv; h
 
 struct Ws {
     Scr sc, sc2;                      // sc2: encoder-sized second set for the side stream (spectral stack)
+    // Second operand set of each stream for the paired weight-gradient launches (wgrad_pairable below): the launch of two encoder
+    // blocks reads dqkv / g0b / g1b / dh13 of both, so consecutive blocks of a stack alternate between sc and scb (sc2 and sc2b).
+    // G1 / du / dob / slab are shared with the first set: no weight-gradient task of the fused path reads them.
+    Scr scb, sc2b;
     hs_bf16* a_pe; float* x0;
     std::vector<BlkBuf> b1, b2, bf, bd;
     hs_bf16* lat; float* y; float* yfull; hs_bf16* zn; float* pred; hs_bf16* dpred; float* partial;
     float *G0, *G1, *G2, *du; hs_bf16 *dh13, *dob, *dqkv, *dyb;
+    float* G3;                        // the spectral stack's own dX: both axis stacks read d(x1 + x2) from G0, neither writes it
+    float* dec_slabs;                 // one more slab per decoder block after the first (dec_slab below), NULL without the fused decoder
     float* slab;                      // weight-gradient partials of the persistent kernels: [workgroup][slot][thread] (slab_bytes())
     int64_t bytes;
 };
@@ -239,6 +245,9 @@ inline int64_t slab_bytes(const Geo& g, bool side_stream) {
     return std::max<int64_t>(wg, HSIMAE_DEC_BLOCK_SLAB_FLOATS * 4);
 }
 
+inline bool mlp_fusable(int d, int hidden);
+inline bool dec_fusable(int d, int heads, int hidden, int Ts);
+constexpr int kDecReduceBlocks = 8;        // decoder blocks one dec_dw_reduce launch takes (fused_dec.hip)
 inline void carve(const Geo& g, int N, int K, char* base, Ws& w) {
     int64_t cur = 0;
     auto take = [&](int64_t bytes) { char* p = base ? base + cur : nullptr; cur += (bytes + 255) & ~255ll; return p; };
@@ -283,6 +292,20 @@ inline void carve(const Geo& g, int N, int K, char* base, Ws& w) {
     w.slab = (float*)take(slab_bytes(g, false));
     w.sc.slab = w.slab;
     w.sc2.slab = slab_bytes(g, true) ? (float*)take(slab_bytes(g, true)) : nullptr;      // (NULL: that launch commits with atomics)
+    // only the 128-tile fused path pairs its launches (plan_block: wgrad_pair), and only encoder blocks do
+    w.scb = w.sc; w.sc2b = w.sc2;
+    if (mlp_fusable(g.D, g.h) && g.Dp < 256) {
+        auto second = [&](Scr& b) {
+            b.dh13 = (hs_bf16*)take((Me + kPlanePadRows) * 2 * rup(g.hp, 64) * 2); b.dqkv = (hs_bf16*)take(Me * g.Dp * 3 * 2);
+            b.g0b = (hs_bf16*)take(Me * g.Dp * 2); b.g1b = (hs_bf16*)take(Me * g.Dp * 2);
+        };
+        second(w.scb);
+        if (g.has_axis) second(w.sc2b);
+    }
+    w.G3 = g.has_axis ? (float*)take(Me * g.Dp * 4) : nullptr;
+    // the fused decoder backward: every block of a reduce launch keeps its partials until that launch (block i % 8: w.slab for 0)
+    const int nslab = std::min(g.ddepth, kDecReduceBlocks);
+    w.dec_slabs = (dec_fusable(g.Dd, g.Hd, g.hdec, g.TL) && nslab > 1) ? (float*)take((nslab - 1) * HSIMAE_DEC_BLOCK_SLAB_FLOATS * 4) : nullptr;
     w.bytes = cur;
 }
 
@@ -497,6 +520,8 @@ enum : uint32_t {
     SC_DEC_SLAB = 1u << 12,        // HSIMAE_DEC_SLAB=0 clears: float atomics in the fused decoder backward
     SC_PLANAR = 1u << 13,          // HSIMAE_WGRAD_PLANAR=0 clears: g / dh1|dh3 of the fused MLP backward row-major instead of 64-column planes
     SC_ATTN_BLOCK256_BWD = 1u << 14,   // HSIMAE_FUSED_ATTN_BLOCK256_BWD=0 clears: blk256_bwd (three launches instead)
+    SC_WGRAD_PAIR = 1u << 15,      // HSIMAE_WGRAD_PAIR=0 clears: one weight-gradient launch per encoder block instead of one per two
+    SC_DEC_REDUCE_ONCE = 1u << 16, // HSIMAE_DEC_REDUCE_ONCE=0 clears: one slab reduce per fused decoder block instead of one per 8
 };
 
 // Shapes the fused kernels are instantiated for.  Each kernel unit ties its template constants to these with static_assert and
@@ -513,7 +538,7 @@ inline bool attn128_fusable(int d, int heads, int Ts) { return d == kAttn128D &&
 inline bool attn256_fusable(int d, int heads, int Ts, int nsamples) {
     return d == kAttn256D && heads == kAttn256Heads && Ts >= 1 && Ts <= kAttnMaxTs && (int64_t)nsamples * Ts * 3 * kAttn256D < (1ll << 31);
 }
-inline bool mlp_fusable(int d, int hidden) { return mlp_shape(d, rup(hidden, 32)); }
+inline bool mlp_fusable(int d, int hidden) { return mlp_shape(d, rup(hidden, 32)); }   // (declared above carve())
 inline bool dec_fusable(int d, int heads, int hidden, int Ts) {
     return d == kDecD && heads == kDecHeads && rup(hidden, 32) == kDecHp && hidden % 4 == 0 && Ts <= kDecMaxTs && Ts >= kDecMinTs;
 }
@@ -539,6 +564,7 @@ struct BlockPlan {
     LnBwd ln1_bwd, ln2_bwd;
     bool planar; int plane_rows;     // g / dh1|dh3 as 64-column planes of plane_rows rows (hsimae_wgrad_task), 0 = row-major
     bool wgrad_slab;         // the 256 x 256-tile weight-gradient launches commit through the stream's slab
+    bool wgrad_pair;         // the weight gradients of two consecutive blocks of a stack as one launch (api.hip WgPair)
 };
 
 // fp8: enc_linears_fp8 for encoder stacks, false for the decoder.  Where a fused bf16 kernel covers the shape it is kept: it beats
@@ -571,6 +597,10 @@ inline BlockPlan plan_block(int d, int heads, int hidden, int Ts, int nsamples, 
     p.planar = p.mlp_fused && on(SC_PLANAR) && M % 32 == 0 && (M + kPlanePadRows) * 2 * (int64_t)(rup(p.hp, 64) + 256) * 2 < (1ll << 32);
     p.plane_rows = p.planar ? (int)M + HS_PLANE_PAD_ROWS : 0;
     p.wgrad_slab = on(SC_WGRAD_SLAB);
+    // Every operand of the block's 7 tasks is then a bf16 buffer that lives until the next block but one of its stream (Ws::scb) or to
+    // the end of the pass, and every matrix is narrower than 256: 128-tiles, 13 per block, so two blocks fit one launch of at most
+    // 16 tasks whose grid wgrad_msplit keeps to the same workgroup count with half the row slices.
+    p.wgrad_pair = on(SC_WGRAD_PAIR) && p.mlp_fused && p.attn_bwd != ATTN_BWD_LAYERED && p.attn_bwd != ATTN_BWD_BLK256 && p.dp < 256;
     return p;
 }
 
@@ -578,10 +608,16 @@ inline BlockPlan plan_block(int d, int heads, int hidden, int Ts, int nsamples, 
 // forward as the attention half (q / k / v in registers, 16 waves per CU) + the row-panel MLP half enc_mlp_fwd_kernel<64, 192>
 // (default since round 3) instead of the one-kernel form; slab: the fused backward commits its in-register weight gradients
 // through the slab + one reduce launch instead of float atomics.
-struct DecPlan { bool fused, split, slab; };
+// reduce_once: the blocks' partials stay in a slab each (Ws::dec_slabs) and one reduce launch takes up to kDecReduceBlocks of them.
+struct DecPlan { bool fused, split, slab, reduce_once; };
 inline DecPlan plan_dec(int Dd, int heads, int hidden, int TL, uint32_t sc) {
-    return DecPlan{(sc & SC_FUSED_DEC) && dec_fusable(Dd, heads, hidden, TL), (sc & SC_DEC_SPLIT) && mlp_fusable(Dd, hidden),
-                   (sc & SC_DEC_SLAB) != 0};
+    const bool fused = (sc & SC_FUSED_DEC) && dec_fusable(Dd, heads, hidden, TL), slab = (sc & SC_DEC_SLAB) != 0;
+    return DecPlan{fused, (sc & SC_DEC_SPLIT) && mlp_fusable(Dd, hidden), slab, fused && slab && (sc & SC_DEC_REDUCE_ONCE)};
+}
+// slab of decoder block i of a pass (carve(): w.slab, then w.dec_slabs)
+inline float* dec_slab(float* slab0, float* more, int i) {
+    const int k = i % kDecReduceBlocks;
+    return (k == 0 || !more) ? slab0 : more + (int64_t)(k - 1) * HSIMAE_DEC_BLOCK_SLAB_FLOATS;
 }
 
 // ------------------------------------------------------------------ bodies of the host-only C entry points

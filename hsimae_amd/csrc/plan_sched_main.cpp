@@ -6,10 +6,11 @@
 // stdin, one query per line; stdout, binary int32:
 //   B d heads hidden Ts nsamples M fp8 sc0 count -> out[count][3], the plans of the schedule words sc0 .. sc0 + count - 1:
 //       [0] attn_fwd | save_qkv << 2 | mlp_fused << 3 | gemm_fp8 << 4 | attn_bwd << 5 | proj_bwd_fused << 7 | ln1_bwd << 8 |
-//           ln2_bwd << 10 | planar << 12 | wgrad_slab << 13 | (the shape fields echo the arguments) << 14
+//           ln2_bwd << 10 | planar << 12 | wgrad_slab << 13 | (the shape fields echo the arguments) << 14 | wgrad_pair << 15
 //       [1] plane_rows   [2] dp << 16 | hp
 //   D Dd heads hidden TL sc0 count                -> out[count]: fused | split << 1 | slab << 2
 //   F model_prec D sc                             -> out[1]: enc_linears_fp8
+//   S tiles M concurrent                          -> out[1]: wgrad_msplit, the row split api.hip passes for a launch of `tiles` 128-tiles
 //   P                                             -> out[1]: HS_PLANE_PAD_ROWS
 //   G akind epi prec bm kc N0 N1 K0 K1            -> out[(N1 - N0) / 16 + 1][(K1 - K0) / 32 + 1][5]: plan_gemm at N = N0, N0 + 16 .. N1 and
 //                                                    K = K0, K0 + 32 .. K1: return code, kc, bm, f8, nch
@@ -37,7 +38,7 @@ int main() {
                 const BlockPlan p = plan_block((int)d, (int)heads, (int)hidden, (int)Ts, (int)ns, M, fp8 != 0, (uint32_t)(sc0 + i));
                 const bool echo = p.d == d && p.heads == heads && p.h == hidden && p.Ts == Ts && p.nsamples == ns && p.M == M;
                 out[i * 3] = p.attn_fwd | p.save_qkv << 2 | p.mlp_fused << 3 | p.gemm_fp8 << 4 | p.attn_bwd << 5 | p.proj_bwd_fused << 7 |
-                             p.ln1_bwd << 8 | p.ln2_bwd << 10 | p.planar << 12 | p.wgrad_slab << 13 | echo << 14;
+                             p.ln1_bwd << 8 | p.ln2_bwd << 10 | p.planar << 12 | p.wgrad_slab << 13 | echo << 14 | p.wgrad_pair << 15;
                 out[i * 3 + 1] = p.plane_rows;
                 out[i * 3 + 2] = p.dp << 16 | p.hp;
             }
@@ -49,6 +50,8 @@ int main() {
             }
         } else if (std::sscanf(line, "F %lld %lld %lld", &fp8, &d, &sc0) == 3) {
             out.push_back(enc_linears_fp8((int)fp8, (int)d, (uint32_t)sc0));
+        } else if (long long tiles, conc; std::sscanf(line, "S %lld %lld %lld", &tiles, &M, &conc) == 3) {
+            out.push_back(wgrad_msplit((int)tiles, M, (int)conc));
         } else if (line[0] == 'P') {
             out.push_back(HS_PLANE_PAD_ROWS);
         } else if (int akind, epi, prec, bm, kc, N0, N1, K0, K1;
