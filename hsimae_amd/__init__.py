@@ -19,13 +19,14 @@ from .data import HSIdataset4PT, DeviceLoader  # noqa: F401
 from .sched import CosineLRScheduler  # noqa: F401
 from .pretrain import mask_pretraining  # noqa: F401
 from .finetune import DualViT, HSIViT  # noqa: F401
-from .finetune_train import dual_branch_finetuning, dual_branch_finetuning_scene, test_model, test_model_scene, knn_eval_scene, cluster_eval_scene, linear_probe_scene  # noqa: F401
+from .finetune_train import dual_branch_finetuning, dual_branch_finetuning_scene, test_model, test_model_scene, knn_eval_scene, cluster_eval_scene, linear_probe_scene, svm_eval_scene  # noqa: F401
 from .scene_data import SceneCubes, get_scene_set_dual, split_labeled, tile_origins, unlabeled_pixels  # noqa: F401
 from .gwpca import GWPCA, apply_gwpca  # noqa: F401
 from .classify import ClassLoss, ScoreMeter  # noqa: F401
 from .knn import KNNClassifier  # noqa: F401
 from .cluster import KMeans, SceneClustering  # noqa: F401
 from .probe import LinearProbe  # noqa: F401
+from .svm import RBFSVM, reference_grid  # noqa: F401
 from .smooth import EdgeFilter, as_guide, scene_guide, smooth_classification  # noqa: F401
 from .segment import SceneSegments, Superpixels, scene_segments, segment_classification  # noqa: F401
 from .recon import SceneReconstruction, reconstruct_scene, recon_eval_scene, window_centres  # noqa: F401

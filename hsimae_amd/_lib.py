@@ -258,6 +258,34 @@ class BuildInfo(C.Structure):
 
 BUCKET_CB = C.CFUNCTYPE(None, i32, i64, i64, vp)
 
+class SvmGramParams(C.Structure):
+    _fields_ = [("x", vp), ("ldx", i32), ("M", i32), ("D", i32), ("n_gamma", i32), ("gamma", f32 * 16), ("K", vp), ("ldk", i32),
+                ("sumsq", vp)]
+
+
+class SvmProblem(C.Structure):
+    _fields_ = [("k_index", i64), ("C", C.c_double), ("a0", i64), ("na", i64), ("b0", i64), ("nb", i64), ("out_offset", i64),
+                ("reserved", i64)]
+
+
+class SvmSolveParams(C.Structure):
+    _fields_ = [("K", vp), ("ldk", i32), ("M", i32), ("n_k", i32), ("table", vp), ("n_problems", i32), ("resume", i32),
+                ("max_iter", i32), ("eps", C.c_double), ("alpha", vp), ("grad", vp), ("alpha_len", i64), ("state", vp)]
+
+
+class SvmPackParams(C.Structure):
+    _fields_ = [("table", vp), ("first_problem", i32), ("n_class", i32), ("alpha", vp), ("alpha_len", i64), ("state", vp),
+                ("x", vp), ("ldx", i32), ("M", i32), ("D", i32), ("sumsq", vp), ("sv_index", vp), ("sv_start", vp),
+                ("coef", vp), ("ldc", i32), ("rho", vp), ("sv", vp), ("ldsv", i32), ("sv_sumsq", vp)]
+
+
+class SvmPredictParams(C.Structure):
+    _fields_ = [("q", vp), ("ldq", i32), ("Q", i32), ("D", i32), ("sv", vp), ("ldsv", i32), ("sv_sumsq", vp), ("sv_start", vp),
+                ("S_max", i32), ("coef", vp), ("ldc", i32), ("rho", vp), ("n_class", i32), ("first", i32), ("gamma", f32),
+                ("H", i32), ("W", i32), ("p0", i64), ("pixels", vp), ("label_map", vp), ("conf_map", vp), ("margin_map", vp),
+                ("probs", vp), ("ldp", i32), ("decision", vp), ("ldd", i32), ("outside", vp)]
+
+
 # name -> (restype, argtypes); also the list the CPU test checks against include/hsimae_hip.h
 SYMBOLS = {
     "hsimae_version": (C.c_int, []),
@@ -332,6 +360,10 @@ SYMBOLS = {
     "hsimae_probe_step": (C.c_int, [C.POINTER(ProbeStepParams), vp]),
     "hsimae_probe_logits": (C.c_int, [C.POINTER(ProbeLogitsParams), vp]),
     "hsimae_probe_fold": (C.c_int, [C.POINTER(ProbeFoldParams), vp]),
+    "hsimae_svm_gram": (C.c_int, [C.POINTER(SvmGramParams), vp]),
+    "hsimae_svm_solve": (C.c_int, [C.POINTER(SvmSolveParams), vp]),
+    "hsimae_svm_pack": (C.c_int, [C.POINTER(SvmPackParams), vp]),
+    "hsimae_svm_predict": (C.c_int, [C.POINTER(SvmPredictParams), vp]),
     "hsimae_recon_accumulate": (C.c_int, [C.POINTER(ReconAccumulateParams), vp]),
     "hsimae_recon_finish": (C.c_int, [C.POINTER(ReconFinishParams), vp]),
     "hsimae_encode": (C.c_int, [C.POINTER(Config), C.POINTER(IO), vp]),

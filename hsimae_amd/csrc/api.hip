@@ -503,6 +503,7 @@ extern "C" unsigned hs_variant_bits_recon();
 extern "C" unsigned hs_variant_bits_probe();
 extern "C" unsigned hs_variant_bits_smooth();
 extern "C" unsigned hs_variant_bits_slic();
+extern "C" unsigned hs_variant_bits_svm();
 #ifndef HS_KERNEL_SOURCE_HASH
 #define HS_KERNEL_SOURCE_HASH 0ULL
 #endif
@@ -520,7 +521,7 @@ int hsimae_version(void) { return HSIMAE_VERSION; }
 int hsimae_build_info(hsimae_build_info_t* out) {
     if (!out) return HSIMAE_ENULL;
     out->abi_version = HSIMAE_VERSION;
-    out->variant_bits = hs_variant_bits() | hs_variant_bits_gemm() | hs_variant_bits_attn() | hs_variant_bits_attn_wide() | hs_variant_bits_wgrad() | hs_variant_bits_elem() | hs_variant_bits_pack() | hs_variant_bits_fused_dec() | hs_variant_bits_fused_enc() | hs_variant_bits_loader() | hs_variant_bits_scene() | hs_variant_bits_gwpca() | hs_variant_bits_cls() | hs_variant_bits_clip() | hs_variant_bits_lamb() | hs_variant_bits_ema() | hs_variant_bits_prob() | hs_variant_bits_knn() | hs_variant_bits_kmeans() | hs_variant_bits_recon() | hs_variant_bits_probe() | hs_variant_bits_smooth() | hs_variant_bits_slic();
+    out->variant_bits = hs_variant_bits() | hs_variant_bits_gemm() | hs_variant_bits_attn() | hs_variant_bits_attn_wide() | hs_variant_bits_wgrad() | hs_variant_bits_elem() | hs_variant_bits_pack() | hs_variant_bits_fused_dec() | hs_variant_bits_fused_enc() | hs_variant_bits_loader() | hs_variant_bits_scene() | hs_variant_bits_gwpca() | hs_variant_bits_cls() | hs_variant_bits_clip() | hs_variant_bits_lamb() | hs_variant_bits_ema() | hs_variant_bits_prob() | hs_variant_bits_knn() | hs_variant_bits_kmeans() | hs_variant_bits_recon() | hs_variant_bits_probe() | hs_variant_bits_smooth() | hs_variant_bits_slic() | hs_variant_bits_svm();
     out->kernel_source_hash = HS_KERNEL_SOURCE_HASH;
     out->flags_hash = HS_BUILD_FLAGS_HASH;
     out->default_flags = HS_BUILD_DEFAULT_FLAGS;
@@ -1085,6 +1086,10 @@ int hsimae_probe_prepare(const hsimae_probe_prepare_params* p, void* stream) { r
 int hsimae_probe_step(const hsimae_probe_step_params* p, void* stream) { return p ? hs_probe_step(*p, S(stream)) : HSIMAE_ENULL; }
 int hsimae_probe_logits(const hsimae_probe_logits_params* p, void* stream) { return p ? hs_probe_logits(*p, S(stream)) : HSIMAE_ENULL; }
 int hsimae_probe_fold(const hsimae_probe_fold_params* p, void* stream) { return p ? hs_probe_fold(*p, S(stream)) : HSIMAE_ENULL; }
+int hsimae_svm_gram(const hsimae_svm_gram_params* p, void* stream) { return p ? hs_svm_gram(*p, S(stream)) : HSIMAE_ENULL; }
+int hsimae_svm_solve(const hsimae_svm_solve_params* p, void* stream) { return p ? hs_svm_solve(*p, S(stream)) : HSIMAE_ENULL; }
+int hsimae_svm_pack(const hsimae_svm_pack_params* p, void* stream) { return p ? hs_svm_pack(*p, S(stream)) : HSIMAE_ENULL; }
+int hsimae_svm_predict(const hsimae_svm_predict_params* p, void* stream) { return p ? hs_svm_predict(*p, S(stream)) : HSIMAE_ENULL; }
 int hsimae_recon_accumulate(const hsimae_recon_accumulate_params* p, void* stream) { return p ? hs_recon_accumulate(*p, S(stream)) : HSIMAE_ENULL; }
 int hsimae_recon_finish(const hsimae_recon_finish_params* p, void* stream) { return p ? hs_recon_finish(*p, S(stream)) : HSIMAE_ENULL; }
 int hsimae_ln_bwd(const hsimae_lnbwd_params* p, void* stream) { return p ? hs_ln_bwd(*p, S(stream)) : HSIMAE_ENULL; }

@@ -63,6 +63,10 @@ int hs_probe_prepare(const hsimae_probe_prepare_params& p, hipStream_t s);
 int hs_probe_step(const hsimae_probe_step_params& p, hipStream_t s);
 int hs_probe_logits(const hsimae_probe_logits_params& p, hipStream_t s);
 int hs_probe_fold(const hsimae_probe_fold_params& p, hipStream_t s);
+int hs_svm_gram(const hsimae_svm_gram_params& p, hipStream_t s);
+int hs_svm_solve(const hsimae_svm_solve_params& p, hipStream_t s);
+int hs_svm_pack(const hsimae_svm_pack_params& p, hipStream_t s);
+int hs_svm_predict(const hsimae_svm_predict_params& p, hipStream_t s);
 int hs_recon_accumulate(const hsimae_recon_accumulate_params& p, hipStream_t s);
 int hs_recon_finish(const hsimae_recon_finish_params& p, hipStream_t s);
 int hs_agg_pool(const float* latent, float* pooled, int N, int T, int L, int D, hipStream_t s);

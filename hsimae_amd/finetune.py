@@ -311,6 +311,87 @@ class DualViT(HSIMAE):
                 knn.check()
         return SceneClassification(*out)
 
+    # ------------------------------------------------------------------ an RBF support-vector machine on features or spectra
+    def svm_scene(self, scene, bank_pixels, bank_labels, pixels=None, features="encoder", C=1.0, gamma="scale", search=False,
+                  bank_flips=(0,), batch_size=8192, return_probs=False, on_device=False):
+        """knn_scene with an RBF-kernel support-vector machine in place of the vote (svm.RBFSVM: sklearn's SVC(kernel='rbf'),
+        one-vs-one): the baseline hyperspectral papers report next to their deep models, and the non-linear counterpart of the
+        linear probe.  features="encoder": the bank is built as knn_scene builds it (`scene_features` of `bank_pixels` under
+        each flip code of `bank_flips`, `bank_labels` in [1, num_class) repeated per code) and the queries go through the
+        encoder in knn_scene's chunks and groups of KNN_GROUP_ROWS rows.  features="spectra": cluster_scene's rows, the scene's
+        own [H * W, C] as fp32 (C zero-padded to the next multiple of 4), with no encoder pass (`bank_flips` is ignored): the
+        reference's Compared_Methods/svm_rbf.py on centre-pixel spectra.  `C`, `gamma`: RBFSVM's (gamma="scale" reads one
+        number from the device).  search=True: RBFSVM.fit_reference, the reference's two-stage grid search (it draws its
+        splits from numpy's global generator and refits on a training half; `C` and `gamma` are then ignored).  At most 8192
+        bank rows and 32 classes.  The defaults are not tuned on a real scene.
+        -> SceneClassification like classify_scene's; confidence, margin and probs are SHARES OF THE PAIRWISE VOTES, not Platt
+        probabilities.  On the CPU after one wait for the copies; on_device=True: all stay on the model's device, and with
+        features="spectra", a float `gamma` and search=False nothing waits for the host (the pixel lists are checked on the host
+        and uploaded from pinned memory; the encoder path uploads its lists as knn_scene does).  The fitted
+        model of the last call stays reachable as `self.last_svm`."""
+        from .svm import RBFSVM
+        if features not in ("encoder", "spectra"):
+            raise ValueError(f'features must be "encoder" or "spectra", got {features!r}')
+        bank_flips = scene_views(bank_flips) if features == "encoder" else (0,)
+        y = torch.as_tensor(np.asarray(bank_labels) if not isinstance(bank_labels, torch.Tensor) else bank_labels)
+        if y.dim() != 1 or y.dtype.is_floating_point or y.dtype == torch.bool:
+            raise ValueError("bank_labels must be a 1-D array of integer labels")
+        svm = RBFSVM(self.num_class, first=1, C=C, gamma=gamma)
+        dev = gpu_of(self)
+
+        def up(t):                                         # a host list to the device without a wait (pinned, asynchronous)
+            return t if t.is_cuda else t.contiguous().pin_memory().to(dev, non_blocking=True)
+        if features == "encoder":
+            sp = self._scene_pass(scene, pixels, batch_size)
+            H, W, n_total = sp.H, sp.W, sp.n_total
+        else:
+            s = as_scene(scene)
+            H, W, Cb = (int(v) for v in s.shape)
+            pix = None if pixels is None else pixel_indices(pixels, H * W)
+            bank_pix = pixel_indices(bank_pixels, H * W, "bank_pixels", allow_empty=False)
+            n_total = H * W if pix is None else pix.numel()
+        with torch.no_grad(), torch.cuda.device(dev):
+            if features == "encoder":
+                bank = [self.scene_features(sp.scene, bank_pixels, batch_size, flip=f, on_device=True) for f in bank_flips]
+                bank = bank[0] if len(bank) == 1 else torch.cat(bank)
+            else:
+                rows = (s if s.is_cuda else up(s)).reshape(H * W, Cb).to(torch.float32)
+                if Cb % 4:
+                    rows = torch.nn.functional.pad(rows, (0, 4 - Cb % 4))
+                bank = rows[up(bank_pix)]
+            if bank.shape[0] != y.numel() * len(bank_flips):
+                raise ValueError(f"{y.numel()} labels for {bank.shape[0] // len(bank_flips)} bank pixels")
+            yb = up(y).repeat(len(bank_flips))
+            if search:
+                svm.fit_reference(bank, yb)
+            else:
+                svm.fit(bank, yb)
+            del bank
+            self.last_svm = svm
+            n_px = H * W
+            labels = torch.zeros(n_px, dtype=torch.int64, device=dev)
+            conf = torch.zeros(n_px, dtype=torch.float32, device=dev)
+            margin = torch.zeros(n_px, dtype=torch.float32, device=dev)
+            probs = torch.empty(n_total, self.num_class, dtype=torch.float32, device=dev) if return_probs else None
+            if features == "spectra":
+                pix_d = None if pix is None else up(pix)
+                svm.predict_into(rows if pix is None else rows[pix_d], H, W, pix_d, labels, conf, margin, probs)
+            else:
+                group = max(1, self.KNN_GROUP_ROWS // sp.chunk) * sp.chunk
+                feats = torch.empty(min(group, n_total), sp.T * self.dim, dtype=torch.float32, device=dev)
+                flips = torch.zeros(sp.chunk, dtype=torch.uint8, device=dev)
+                for g0 in range(0, n_total, group):
+                    gn = min(group, n_total - g0)
+                    for k0, n in sp.chunks(g0, g0 + gn):
+                        sp.cut(k0, n, flips)
+                        sp.pooled_into(feats[k0 - g0:k0 - g0 + n], n)
+                    svm.predict_into(feats[:gn], H, W, sp.items[g0:g0 + gn], labels, conf, margin,
+                                     None if probs is None else probs[g0:g0 + gn])
+            out = to_host([labels.view(H, W), conf.view(H, W), margin.view(H, W), probs], on_device)
+            if not on_device:
+                svm.check()
+        return SceneClassification(*out)
+
     # ------------------------------------------------------------------ a linear probe on the frozen encoder
     def probe_scene(self, scene, bank_pixels, bank_labels, pixels=None, bank_flips=(0,), views=(0,), batch_size=8192,
                     return_probs=False, on_device=False, **probe_kwargs):

@@ -419,6 +419,44 @@ def knn_eval_scene(scene, train_index, train_labels, test_gt, gt, pretrained, de
     return _score_and_save(pred, test_gt, gt, n_class, device, save_dir, name, save_images)
 
 
+def svm_eval_scene(scene, train_index, train_labels, test_gt, gt, pretrained=None, features="spectra", search=True, C=1.0,
+                   gamma="scale", depth=12, dim=96, s_depth=6, bank_flips=(0,), device="cuda:0", batch_size=8192, save_dir=None,
+                   model_name=None, save_images=False, smooth=None):
+    """The baseline the reference reports next to its deep models (Compared_Methods/svm_rbf.py): an RBF-kernel support-vector
+    machine, over the whole scene, on the device (HSIViT.svm_scene, svm.RBFSVM).  Inputs as knn_eval_scene's: `scene` the
+    processed [H, W, C] `HSI_data`, `train_index` / `train_labels` the labelled pixels the machine is fitted on (at most 8192),
+    `test_gt` / `gt` as in test_model_scene.  features="spectra" (the reference's baseline: centre-pixel spectra, no encoder;
+    `pretrained` may be None: a model is then built for the band count only and never run) or "encoder" (the frozen encoder's
+    pooled features: `pretrained` is the path of a state dict, loaded as knn_eval_scene loads it).  search=True runs the
+    reference's two-stage grid search over C and gamma (RBFSVM.fit_reference; it draws its splits from numpy's global
+    generator); search=False fits once at `C`, `gamma`.  None of these defaults is tuned on a real scene.  save_images=True
+    writes test_model_scene's two pictures into <save_dir>/<stem of model_name>/ (model_name defaults to the checkpoint's
+    file name, or "svm_rbf.pkl").  `smooth`: test_model_scene's (None, True, an EdgeFilter or a Superpixels), applied to the
+    machine's vote shares.
+    -> (oa, aa, kappa, per-class recall, prediction map shaped like `gt`), scored as test_model_scene scores."""
+    device = torch.device(device)
+    filt = spatial_step_of(smooth)
+    if len(scene.shape) != 3:
+        raise ValueError(f"scene must be [H, W, C], got shape {tuple(scene.shape)}")
+    if save_images and save_dir is None:
+        raise ValueError("save_images=True needs save_dir")
+    if features == "encoder" and pretrained is None:
+        raise ValueError('features="encoder" needs a pretrained checkpoint')
+    c = int(scene.shape[2])
+    n_class = int(np.max(gt) + 1)
+    model = eval_vit(9, c + (-c) % 8, n_class, dim, depth, s_depth, device)          # (spectra: any band count; never run)
+    if pretrained is not None:
+        model = load_matching(model, pretrained, device, match_shapes=True)
+    if filt is not None:
+        scene = as_scene(scene).to(device)                 # uploaded once: the classification and the guide share it
+    res = model.svm_scene(scene, train_index, train_labels, features=features, C=C, gamma=gamma, search=search,
+                          bank_flips=bank_flips, batch_size=batch_size, return_probs=filt is not None, on_device=True)
+    model.last_svm.check()
+    pred = res.labels if filt is None else spatial_labels(filt, res, scene)
+    name = model_name or (os.path.basename(str(pretrained)) if pretrained is not None else "svm_rbf.pkl")
+    return _score_and_save(pred, test_gt, gt, n_class, device, save_dir, name, save_images)
+
+
 def linear_probe_scene(scene, train_index, train_labels, test_gt, gt, pretrained, depth=12, dim=96, s_depth=6, bank_flips=(0,),
                        views=(0,), device="cuda:0", batch_size=8192, save_dir=None, model_name=None, save_images=False,
                        smooth=None, **probe_kwargs):

@@ -1024,6 +1024,140 @@ typedef struct {
 } hsimae_probe_fold_params;
 int hsimae_probe_fold(const hsimae_probe_fold_params* p, void* stream);
 
+/* ------------------------------------------------------------------ RBF support-vector classifier (csrc/svm.hip)
+ * ADDED under HSIMAE_VERSION 108 like the entry points above: nothing that 108 already had changes.  C-SVC in libsvm's dual form
+ * with the kernel K_ts = exp(-gamma ||x_t - x_s||^2), one-vs-one over the class pairs (a, b), a < b, in the order (0, 1), (0, 2),
+ * .., (1, 2), ..: rows of class a carry y = +1, rows of class b y = -1; minimise 1/2 a'Qa - e'a, Q_ts = y_t y_s K_ts, 0 <= a <= C,
+ * y'a = 0.  The bank rows are sorted by class, so every class is one contiguous row range.  Four entry points: the kernel matrices,
+ * the solver (one launch for any number of problems), the compact model, the prediction.  No atomics, no grid-wide barrier,
+ * nothing waits for the host: two runs are bit-identical.  Common refusals: params NULL, or with work to do a required pointer
+ * NULL -> HSIMAE_ENULL; a negative count or a leading dimension below its width -> HSIMAE_EDIMS; a matrix not 16-byte aligned or
+ * with a leading dimension that is no multiple of 4, another pointer not aligned to its element -> HSIMAE_EALIGN.  A refusal
+ * writes nothing.
+ *
+ * hsimae_svm_gram: x fp32 [M][ldx], D columns (D > 0, D % 4 = 0, else HSIMAE_EDIMS; D > 4096, M > HSIMAE_SVM_MAX_ROWS or n_gamma >
+ *   HSIMAE_SVM_MAX_GAMMAS -> HSIMAE_EUNSUPPORTED; n_gamma < 1, a gamma that is not a positive finite number -> HSIMAE_EDIMS) ->
+ *   K fp32 [n_gamma][M][ldk] and sumsq fp32 [M] (required).  In this order:
+ *     dot_ts  = hsimae_knn_topk's exact-fp32 fmaf chain from +0 over the columns 0 .. D - 1
+ *     n_t     = dot_tt: THE SAME chain (the diagonal of the row's own tile), not the lane-strided sum of hsimae_row_normalize, so
+ *               that two equal rows have n_t = n_s = dot_ts bit for bit and d2 = 0 exactly -> sumsq
+ *     d2_ts   = fmaf(-2, dot_ts, fl(n_t + n_s)), a negative value replaced by 0 (a NaN stays)
+ *     g2      = fl(gamma * fl32(log2 e))
+ *     K_ts    = exp2(fl(-g2 * d2_ts))   (v_exp_f32);   K_tt = 1 is written as a constant, for a NaN row too
+ *   Only the tiles on and above the diagonal are computed; a tile writes K_ts and K_st from the same value: K is symmetric bit
+ *   for bit.  A NaN row makes its row and its column NaN (the diagonal element excepted) and nothing else.  M = 0 -> HSIMAE_OK.
+ *
+ * hsimae_svm_solve: `table` holds n_problems rows of the struct hsimae_svm_problem below, in device memory, all fields 8 bytes.  Problem r: kernel
+ *   matrix k_index (< n_k) of K fp32 [n_k][M][ldk], box constant C, the rows a0 .. a0 + na - 1 (y = +1) then b0 .. b0 + nb - 1
+ *   (y = -1), n = na + nb local variables t = 0 .. n - 1 in that order.  One workgroup of 256 threads per problem runs libsvm's SMO
+ *   with second-order working-set selection (Fan, Chen and Lin 2005, WSS 2), no shrinking, no cache: alpha and the gradient G are
+ *   fp64 in LDS for the whole solve (16 n bytes + 128 bytes of reduction scratch: n <= HSIMAE_SVM_MAX_ROWS = 8192 is 128 KiB of the
+ *   160 KiB a gfx950 workgroup may hold); the kernel rows K_i and K_j are read from memory in every iteration.  Per iteration:
+ *     1. i = argmax over I_up = {y_t = +1, alpha_t < C} u {y_t = -1, alpha_t > 0} of -y_t G_t = G_max; m2 = max over I_low =
+ *        {y_t = +1, alpha_t > 0} u {y_t = -1, alpha_t < C} of y_t G_t (a maximum of -0 is +0: m2 + 0);  gap = G_max + m2.  gap < eps, or no i -> converged.
+ *        Otherwise `max_iter` iterations done in this call -> stop, not converged.
+ *     2. j = argmax over t in I_low with b = G_max + y_t G_t > 0 of (b * b) / a, a = 2 - 2 K_it (fp64 of the fp32 K), a <= 0
+ *        replaced by 1e-12.  No j -> converged.
+ *     3. libsvm's Solver::Solve two-variable update with its clipping to the box, Q_ij = y_i y_j K_ij, Q_ii = Q_jj = 1.
+ *     4. G_t = G_t + (Q_ti * d_i + Q_tj * d_j) for every t, d = the change of alpha_i, alpha_j.
+ *   Every argmax: the larger value wins, of equals the lower t, a NaN never wins: per thread over t = tid, tid + 256, .., then the
+ *   xor tree over the 64 lanes (partner lane ^ 1, .. ^ 32) and the four waves in ascending order, all by that one rule, which is
+ *   associative: the result is that of a serial scan.  Every fp64 operation is a single correctly rounded IEEE operation (no fused
+ *   multiply-add, contraction off); no floating-point sum is reduced across threads.
+ *   rho as libsvm's calculate_rho, one thread over t ascending: the mean of y_t G_t over the free variables (0 < alpha_t < C), else
+ *   the midpoint of max{y_t G_t: at the bound on the I_up-only side} and min{.. on the I_low-only side}.
+ *   Outputs of problem r: alpha fp64 [n] at alpha + out_offset, G fp64 [n] at grad + out_offset, state fp64 [HSIMAE_SVM_STATE] at
+ *   state + 8 r = {iterations, converged, gap, n_sv (alpha_t > 0), n_bounded (alpha_t >= C), rho, 0, 0}.  converged: 1 yes, 0 no
+ *   (max_iter), -1 the table row is refused (k_index outside [0, n_k), a negative field, a range beyond M, n > M, out_offset + n >
+ *   alpha_len, C not a positive finite number): nothing but the state is written; -2 na = 0 or nb = 0: alpha = 0, G = -1, rho = 0; -3 an alpha or a G that is not finite when the
+ *   problem stopped (a NaN or an infinity in K: no NaN ever wins an argmax, so the solve ends early and says so here).
+ *   resume = 0: start from alpha = 0, G = -1.  resume != 0: start from alpha and grad as they are and add to state[0]; `max_iter`
+ *   counts the iterations of THIS call, so r iterations in one call equal r calls of one iteration bit for bit.
+ *   n_problems = 0 -> HSIMAE_OK; M < 1, M > HSIMAE_SVM_MAX_ROWS -> HSIMAE_EDIMS / HSIMAE_EUNSUPPORTED; max_iter < 0, eps not a
+ *   positive finite number, alpha_len < 0 -> HSIMAE_EDIMS.
+ *
+ * hsimae_svm_pack: the n_class (n_class - 1) / 2 problems table[first_problem ..] of ONE model (pair order as above, class c =
+ *   rows a0 / b0 of its pairs) into libsvm's compact form, one workgroup per class:
+ *     sv_index int32 [M]: the bank rows with alpha > 0 in any of their pairs, ascending (so grouped by class); sv_start int32
+ *     [n_class + 1]: where each class starts in that list, sv_start[n_class] = S;  coef fp32 [n_class - 1][ldc]: for support row s
+ *     of class c, coef[j][s] = fp32(y alpha) of c's pair with class j (j < c) or j + 1 (j >= c), y = +1 when c is the lower class;
+ *     rho fp32 [P] = fp32(state rho);  sv fp32 [S][ldsv] and sv_sumsq fp32 [S]: the support rows of x and their sumsq gathered.
+ *   Entries behind S are not written.  A refused or out-of-range table row makes S = 0.  2 <= n_class <= HSIMAE_SVM_MAX_CLASSES.
+ *
+ * hsimae_svm_predict: for the rows q fp32 [Q][ldq], a workgroup owns 64 rows and walks the S = sv_start[n_class] (at most S_max)
+ *   support rows in tiles of 64 in ascending order.  Per tile: qn = sum of squares of the query row (hsimae_row_normalize's
+ *   lane-strided chain and xor tree: NOT the dot tile's chain, so a query equal to a support row gives a K next to 1, not exactly
+ *   1 as in hsimae_svm_gram), the dot tile, d2 / g2 / exp2 as hsimae_svm_gram (no constant on a diagonal), then for every
+ *   pair p = (a, b): dec_p = fmaf(coef, K, dec_p) over the tile's support rows of class a (coef[b - 1]) then of class b (coef[a])
+ *   in ascending order, from +0 (LDS, [pair][row]; thread = (row, pairs p with p % 4 = wave)).  After the last tile, per row:
+ *   d_p = dec_p - rho_p (fp32); d_p > 0 votes for a, else for b; label = first + the class with most votes, ties to the lower
+ *   class; share_c = fp32(votes_c) / fp32(P).  At the row's pixel (`pixels[r]`, or p0 + r; nothing is written for a pixel outside
+ *   [0, H * W)): label_map int64, conf_map fp32 or NULL = the winner's share, margin_map fp32 or NULL = that minus the largest
+ *   other share.  probs fp32 [Q][ldp] or NULL: 0 below `first`, share_c at first + c (ldp >= first + n_class).  These are SHARES OF
+ *   THE PAIRWISE CONTESTS, not Platt probabilities.  decision fp32 [Q][ldd] or NULL: d_p.  outside int32 [HSIMAE_SVM_GRID] or
+ *   NULL: entry g = the rows of workgroup g whose pixel lay outside (0 for workgroups that do not exist).
+ *   LDS: 16.9 KiB of slabs, norms and class starts + 256 P bytes of decision sums: n_class <= HSIMAE_SVM_MAX_CLASSES = 32 (P = 496: 140.5 KiB). */
+#define HSIMAE_SVM_MAX_ROWS 8192     /* rows of a Gram matrix, variables of one problem */
+#define HSIMAE_SVM_MAX_GAMMAS 16
+#define HSIMAE_SVM_MAX_CLASSES 32    /* real classes of hsimae_svm_pack / hsimae_svm_predict */
+#define HSIMAE_SVM_STATE 8           /* doubles per problem in `state` */
+#define HSIMAE_SVM_GRID 2048         /* workgroups of hsimae_svm_predict at most (a stride loop beyond); ints in `outside` */
+typedef struct {
+    const float* x; int32_t ldx;
+    int32_t M, D, n_gamma;
+    float gamma[HSIMAE_SVM_MAX_GAMMAS];
+    float* K; int32_t ldk;
+    float* sumsq;
+} hsimae_svm_gram_params;
+int hsimae_svm_gram(const hsimae_svm_gram_params* p, void* stream);
+
+typedef struct {
+    int64_t k_index; double C;
+    int64_t a0, na, b0, nb, out_offset, reserved;
+} hsimae_svm_problem;
+
+typedef struct {
+    const float* K; int32_t ldk;
+    int32_t M, n_k;
+    const hsimae_svm_problem* table; int32_t n_problems;
+    int32_t resume, max_iter;
+    double eps;
+    double* alpha; double* grad; int64_t alpha_len;
+    double* state;
+} hsimae_svm_solve_params;
+int hsimae_svm_solve(const hsimae_svm_solve_params* p, void* stream);
+
+typedef struct {
+    const hsimae_svm_problem* table; int32_t first_problem, n_class;
+    const double* alpha; int64_t alpha_len; const double* state;
+    const float* x; int32_t ldx;
+    int32_t M, D;
+    const float* sumsq;
+    int32_t* sv_index; int32_t* sv_start;
+    float* coef; int32_t ldc;
+    float* rho;
+    float* sv; int32_t ldsv;
+    float* sv_sumsq;
+} hsimae_svm_pack_params;
+int hsimae_svm_pack(const hsimae_svm_pack_params* p, void* stream);
+
+typedef struct {
+    const float* q; int32_t ldq;
+    int32_t Q, D;
+    const float* sv; int32_t ldsv;
+    const float* sv_sumsq; const int32_t* sv_start; int32_t S_max;
+    const float* coef; int32_t ldc;
+    const float* rho;
+    int32_t n_class, first;
+    float gamma;
+    int32_t H, W; int64_t p0; const int64_t* pixels;
+    int64_t* label_map; float* conf_map; float* margin_map;
+    float* probs; int32_t ldp;
+    float* decision; int32_t ldd;
+    int32_t* outside;
+} hsimae_svm_predict_params;
+int hsimae_svm_predict(const hsimae_svm_predict_params* p, void* stream);
+
 /* ------------------------------------------------------------------ masked reconstruction of a whole scene (csrc/recon.hip)
  * ADDED under HSIMAE_VERSION 108 like the entry points above: nothing that 108 already had changes.  The way back from the
  * windows hsimae_forward reconstructs to the scene they were cut from, and the error maps and sums behind PSNR and the spectral
